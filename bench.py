@@ -6,6 +6,11 @@
 One "step" = forward + backward + (gradient all-reduce) + AdamW step over one synthetic 4096-token batch per GPU
 (config C2 of SURVEY 8d: text only, causal, base + LM head + embeddings frozen, LoRA on model.layers, norm weights
 trainable).  Weights are random-init at Llama-3.1-8B dimensions (no checkpoints offline).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times `--steps` steps and prints the line.  `--full` adds what takes runs of its own: the live GEMM /
+attention rooflines (traced eager steps after the timed ones), the other single-GPU workloads of BASELINE.json (`configs`) and the CPU
+oracle baseline (`cpu_baseline`).  `--dump-outputs DIR` writes what the last timed step computed as float32 .npy files (dump_outputs);
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -60,6 +65,9 @@ def build_model(cfg_name: str, seq: int, rank: int, device, config: str = "text"
     if config == "int8":
         quantize_linear_(model.layers, "int8", dynamic_int8_act=True)  # quantise, then adapt (train_metamathqa.py:178-179)
     if rank > 0:
+        # the adapters draw A from the default generators, which PyTorch seeds at random per process on the GPU: seeded here, every run
+        # (and every rank) starts from the same factors
+        torch.manual_seed(1234)
         apply_linear_adapter_(model.layers, "lora", rank=rank, alpha=float(rank))
     with torch.no_grad():
         for n, p in model.named_parameters():
@@ -162,9 +170,42 @@ def _roofline(args, config: str, kind: str, st: dict, S: int) -> dict:
             "gemm_ms_per_step": round(st["ms"], 2)}
 
 
-def run_workload(args, config: str, device, world: int, rank: int, steps: int, warmup: int, seq: int | None = None, head_compact: bool | None = None) -> dict:
-    """Build the model of one BASELINE configuration, capture its step, time `steps` steps after `warmup`, then trace one eager step with
-    HIP events around every GEMM launch (bf16 and i8 kernels separately).  Returns the raw numbers; main() formats them."""
+DUMP_ELEMENTS = 4 << 20  # positions sampled from the trainable parameters: 16 MB per float32 array, well inside the 64 MB of a dump
+
+
+def dump_outputs(path: str, loss, model) -> None:
+    """What the last timed step hands its caller, as float32 .npy files under `path`: the loss (loss.npy), and at the same fixed, seeded
+    positions of the trainable parameters (concatenated in named_parameters order; every position when there are at most DUMP_ELEMENTS)
+    their updated values (params.npy) and the gradients the update used (grads.npy, read where the trainable arena keeps them: llx/arena.py;
+    not written when the step drops a gradient after the update, as the eager --no-arena step does)."""
+    import numpy as np
+
+    params = [p for _, p in model.named_parameters() if p.requires_grad]
+    arena = getattr(model, "_llx_arena", None)
+    grads = [arena.grad_view(p) if arena is not None and arena.contains(p) else p.grad for p in params]
+    total = sum(p.numel() for p in params)
+    idx = np.unique(np.random.default_rng(0).integers(0, total, DUMP_ELEMENTS)) if total > DUMP_ELEMENTS else np.arange(total)
+
+    def sample(tensors):
+        out, base = [], 0
+        for t in tensors:
+            lo, hi = np.searchsorted(idx, (base, base + t.numel()))
+            out.append(t.detach().reshape(-1)[torch.from_numpy(idx[lo:hi] - base).to(t.device)].float().cpu())
+            base += t.numel()
+        return torch.cat(out).numpy()
+
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), np.float32(float(loss.detach())))
+    np.save(os.path.join(path, "params.npy"), sample(params))
+    if all(g is not None for g in grads):
+        np.save(os.path.join(path, "grads.npy"), sample(grads))
+
+
+def run_workload(args, config: str, device, world: int, rank: int, steps: int, warmup: int, seq: int | None = None, head_compact: bool | None = None,
+                 dump: str | None = None) -> dict:
+    """Build the model of one BASELINE configuration, capture its step, time `steps` steps after `warmup` (rank 0 writes the outputs of the
+    last one under `dump` when given), then with --full trace eager steps with HIP events around every GEMM launch (bf16 and i8 kernels
+    separately).  Returns the raw numbers; main() formats them."""
     from llx import kernels as K
     from llx import ops as llx_ops
     from llx.dp import GradBuckets
@@ -341,15 +382,17 @@ def run_workload(args, config: str, device, world: int, rank: int, steps: int, w
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+    if dump is not None and rank == 0:
+        dump_outputs(dump, loss, model)  # before any traced step moves the parameters on
 
-    # ---- live roofline of the GEMM kernels: one more step with HIP events around every launch (on the launch stream).
+    # ---- live roofline of the GEMM kernels (--full): more steps with HIP events around every launch (on the launch stream).
     # Every rank runs the step (it contains the gradient exchange); only rank 0 records events.
     gemm_stats = {}
     attn_stats = {}
     # Three traced steps, the one with the median GEMM time is reported: a single eager step is one sample per launch, and an eager step
     # starts every kernel behind a host-side gap (clock and cache state differ from the graph replay's: 0.47-0.51 from run to run).
     traces = []
-    for _ in range(3):
+    for _ in range(3 if args.full else 0):
         if rank == 0:
             K.GEMM_TRACE = []
             K.ATTN_TRACE = []
@@ -361,7 +404,7 @@ def run_workload(args, config: str, device, world: int, rank: int, steps: int, w
             traces.append((sum(e[0].elapsed_time(e[1]) for e in K.GEMM_TRACE), K.GEMM_TRACE, K.ATTN_TRACE))
             K.GEMM_TRACE = None
             K.ATTN_TRACE = None
-    if rank == 0:
+    if traces:
         _, tr, at = sorted(traces, key=lambda t: t[0])[1]
         for kind in ("fwd", "bwd"):
             sel = [e for e in at if e[2] == kind]
@@ -390,11 +433,12 @@ def run_workload(args, config: str, device, world: int, rank: int, steps: int, w
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s peak (a float4 copy reaches ~6.3 TB/s)
 
 
-def run_decode(args, device, steps: int, warmup: int, contexts=(4096, 8192)) -> dict:
+def run_decode(args, device, steps: int, warmup: int, contexts=(4096, 8192), dump: str | None = None) -> dict:
     """single-token decode of the 8B model against its KV cache (modelling/llama.py:76-90,126-127,189-207) - one hipGraph
     replay per token (embedding, 32 x [norm+q|k|v+RoPE+cache write, split-cache attention, wo+residual, norm+gate|up+SwiGLU, w2+residual],
     norm+head).  HBM-bound: every weight byte and every live K/V byte is read once per token; reported as ms/token and as the
-    fraction of the 8 TB/s HBM peak those algorithmic bytes make of the measured time."""
+    fraction of the 8 TB/s HBM peak those algorithmic bytes make of the measured time.  `dump`: the logits of the last timed replay
+    (the last context) go to `dump`/logits.npy as float32."""
     model, cfg = build_model(args.model, max(contexts), 0, device, "text")
     model.requires_grad_(False)
     model.eval()
@@ -439,6 +483,11 @@ def run_decode(args, device, steps: int, warmup: int, contexts=(4096, 8192)) -> 
                                 "roofline": {"bound": "hbm", "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
                                              "traffic": None, "algorithmic_bytes": weight_bytes + kv_bytes},
                                 "finite_logits": bool(torch.isfinite(logits.float()).all())}
+    if dump is not None:
+        import numpy as np
+
+        os.makedirs(dump, exist_ok=True)
+        np.save(os.path.join(dump, "logits.npy"), logits.float().cpu().numpy())
     del model, graph, logits
     import gc
 
@@ -494,12 +543,20 @@ def main():
     ap.add_argument("--trainable", default="lora", choices=["lora", "reference"],
                     help="lora: adapters + layer norms (SURVEY 8d C2, the headline); reference: also tok_embeddings / norm / output, the reference "
                          "scripts' default trainable set (train_metamathqa.py:177-180) - weight gradients of the embedding and the LM head")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also trace eager steps for the GEMM / attention rooflines, time the other single-GPU workloads after the headline run "
+                         "(N=1, text only) and the CPU oracle baseline; a plain run times the headline workload only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/*.npy (float32; a fixed, seeded "
+                                                          "sample of the trainable parameters and their gradients, and the loss; "
+                                                          "--config decode: the logits)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel eagerly instead of replaying a captured hipGraph (single GPU)")
     ap.add_argument("--no-arena", action="store_true", help="keep the trainable tensors separate (per-tensor AdamW launches; A/B of llx/arena.py)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the int8 / audio / packed workloads timed after the headline run (N=1, text only)")
-    ap.add_argument("--extra-steps", type=int, default=6, help="timed steps of each extra workload (after 2 warm-up steps)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the int8 / audio / packed workloads timed after the headline run")
+    ap.add_argument("--extra-steps", type=int, default=6, help="with --full: timed steps of each extra workload (after 2 warm-up steps)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -524,16 +581,17 @@ def main():
 
     S = args.seq
     if args.config == "decode":  # inference extra, its own line: ms per decoded token against the HBM roofline
-        d = run_decode(args, device, args.steps, args.warmup)
+        d = run_decode(args, device, args.steps, args.warmup, dump=args.dump_outputs)
         best = d["ctx4096"]
         print(json.dumps({"metric": "decode tokens/sec Llama-3.1-8B batch 1, KV cache 4096 (ms/token at 4096 and 8192)", "value": best["tokens_per_s"], "unit": "tokens/s",
                           "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": best["ms_per_token"], "higher_is_better": True, "scaling": "weak",
                           "vs_baseline": None, "dtype": "bf16", "data": "synthetic", "config": {"workload": d["workload"]}, "roofline": best["roofline"], "decode": d}),
               flush=True)
         return
-    r = run_workload(args, args.config, device, world, rank, args.steps, args.warmup)
+    r = run_workload(args, args.config, device, world, rank, args.steps, args.warmup, dump=args.dump_outputs)
     extras = {}
-    if world == 1 and args.config == "text" and args.trainable == "lora" and not args.no_extras and os.environ.get("LLX_FORCE_DP") != "1":
+    if (args.full and world == 1 and args.config == "text" and args.trainable == "lora" and not args.no_extras
+            and os.environ.get("LLX_FORCE_DP") != "1"):
         # the other single-GPU workloads of BASELINE.json, a few replays each in the same process (reported under "configs")
         # (+ the per-GPU shape of configs[4]: 4096 audio + 4096 text tokens, S = 8192, when the headline runs at its default length)
         for cfg, sq in (("int8", None), ("audio", None), ("packed", None)) + ((("audio_s8192", 8192),) if args.seq == 4096 and args.model == "llama31_8b" else ()):
@@ -585,7 +643,7 @@ def main():
                 out[k] = sm[k]
         if extras:
             out["configs"] = extras
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(S, args.rank)
         result_line = json.dumps(out)
     else:

@@ -1,4 +1,5 @@
-"""bench.py contract: one JSON line with the required keys (tiny plumbing configs on the GPU; the CPU test only checks the CLI)."""
+"""bench.py contract: one JSON line with the required keys, --dump-outputs (tiny plumbing configs on the GPU; the CPU test only checks the
+CLI)."""
 import json
 import os
 import subprocess
@@ -14,12 +15,13 @@ REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 def test_cli_help():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "--gpus" in out.stdout and "--steps" in out.stdout and "--warmup" in out.stdout
+    assert "--full" in out.stdout and "--dump-outputs" in out.stdout
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("extra", [[], ["--config", "int8"], ["--config", "audio", "--no-graph"], ["--config", "packed"]])
 def test_tiny_bench_line(cuda, extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--model", "tiny", "--seq", "512", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--model", "tiny", "--seq", "512", "--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = out.stdout.strip().splitlines()[-1]
@@ -34,6 +36,33 @@ def test_tiny_bench_line(cuda, extra):
         assert d["roofline_i8"]["peak"] == 5000.0 and d["roofline_i8"]["unit"] == "TOP/s" and d["roofline_i8"]["traffic"] is None
     assert r["traffic"] is None  # no PMC file exists for a tiny plumbing workload
     assert "workload" in d["config"] and "model" not in d["config"]
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_dumped_outputs(cuda, tmp_path):
+    """A plain run times the headline workload only; --dump-outputs writes the last timed step's loss, parameters and gradients, and
+    --full (traced steps after the timed ones) changes none of them."""
+    import numpy as np
+
+    dumps = []
+    for extra in ([], ["--full", "--no-extras", "--no-cpu-baseline"]):
+        d = tmp_path / f"out{len(dumps)}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--model", "tiny", "--seq", "512", "--steps", "4", "--warmup", "2",
+               "--dump-outputs", str(d)] + extra
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads(out.stdout.strip().splitlines()[-1])
+        assert REQUIRED - {"roofline"} <= line.keys(), REQUIRED - line.keys()
+        assert line["steps"] == 4 and line["warmup"] == 2 and line["unit"] == "tokens/s" and line["dtype"] == "bf16" and line["higher_is_better"] is True
+        assert abs(line["value"] - 512 / (line["ms_per_step"] * 1e-3)) < 0.02 * line["value"]
+        assert not {"configs", "cpu_baseline"} & line.keys() and ("roofline" in line) == bool(extra)
+        arrays = {f.name: np.load(f) for f in d.iterdir()}
+        assert sorted(arrays) == ["grads.npy", "loss.npy", "params.npy"] and all(a.dtype == np.float32 for a in arrays.values())
+        assert arrays["params.npy"].shape == arrays["grads.npy"].shape and np.isfinite(arrays["grads.npy"]).all() and arrays["grads.npy"].any()
+        assert abs(float(arrays["loss.npy"]) - line["config"]["loss"]) < 1e-4
+        dumps.append(arrays)
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
 
 
 @pytest.mark.gpu

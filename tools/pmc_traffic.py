@@ -42,7 +42,7 @@ def main():
             continue
         per = (2.0 * ft[kind] + wt[kind]) * 1024.0 / n
         out = {"source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over python3 bench.py --config {config} --seq {seq} "
-                         "--steps 1 --warmup 1 --no-graph --no-extras --no-cpu-baseline; " + ("i8" if kind == "i8" else "bf16") + " gemm_nt_kernel launches only",
+                         "--steps 1 --warmup 1 --no-graph --full --no-extras --no-cpu-baseline; " + ("i8" if kind == "i8" else "bf16") + " gemm_nt_kernel launches only",
                "gemm_launches": n, "FETCH_SIZE_KB_sum": ft[kind], "WRITE_SIZE_KB_sum": wt[kind],
                "correction": "gfx950 FETCH_SIZE counts 64 B per 128-B request: read bytes = 2 x FETCH_SIZE (MI355X_MICROARCH.md, HBM); WRITE_SIZE exact",
                "hbm_bytes_per_launch": per}
