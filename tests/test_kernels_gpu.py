@@ -10,6 +10,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import ref as O  # noqa: E402  (test-only import of the oracle)
+from tests import attn_cases as C  # noqa: E402
 
 
 def _bf(x):
@@ -447,6 +448,9 @@ def test_attention_fwd_bwd(K, cuda, B, S, H, KVH, kind):
     o, lse = K.attn_fwd(qd, kd, vd, ms)
     # P is rounded to bf16 before P.V: 2^-8 relative on O(1) values
     torch.testing.assert_close(o.cpu().float(), ref.detach(), atol=2e-2, rtol=2e-2)
+    # the lse handed to the backward (log2 units of the scaled scores) against the float64 logsumexp in nats
+    le = C.lse_rel(lse.cpu(), torch.logsumexp(C.scores64(q, k, mask), dim=-1))
+    assert le <= C.LSE_REL, f"lse error {le:.3e}"
     dq, dk, dv = torch.empty_like(qd), torch.empty_like(kd), torch.empty_like(vd)
     K.attn_bwd(qd, kd, vd, o, dod, lse, dq, dk, dv, ms)
     torch.testing.assert_close(dq.cpu().float(), qr.grad, atol=4e-2, rtol=4e-2)
@@ -504,6 +508,8 @@ def test_attention_random_shapes(K, cuda):
         o, lse = K.attn_fwd(q, k, v, ms)
         tag = (it, B, S, H, KVH, kind)
         torch.testing.assert_close(o.float(), ref.detach(), atol=2e-2, rtol=2e-2, msg=lambda m: f"{tag}: {m}")
+        le = C.lse_rel(lse, torch.logsumexp(C.scores64(q, k, mask.to(cuda)), dim=-1))
+        assert le <= C.LSE_REL, f"{tag}: lse error {le:.3e}"
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         K.attn_bwd(q, k, v, o, do, lse, dq, dk, dv, ms)
         for name, got, want in (("dq", dq, qr.grad), ("dk", dk, kr.grad), ("dv", dv, vr.grad)):
