@@ -15,7 +15,6 @@
 //                   come from the row-major LDS tile through ds_read_b64_tr_b16)
 // K/V tiles are double-buffered in LDS by global_load_lds with the bank swizzle applied on the source address.
 #include "common.h"
-#include <stdlib.h>
 #include <mutex>
 #include <type_traits>
 
@@ -47,6 +46,7 @@ struct AttnFwdArgs {
 // ask for ~60 GB/s at this kernel's MFMA rate, ONE 8-wave workgroup (256 query rows sharing every tile) for half of that.
 template <bool GENERAL, bool STAMP = false, int NW = 8>
 __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_kernel(const AttnFwdArgs a) {
+  static_assert(NW == 8, "NW stays a parameter only because bench.py, tools/ and profiles/ key on the symbol attn_fwd_kernel<*, *, 8>");
   constexpr int WQ = 32 * NW;   // query rows per workgroup
   constexpr int NP = 16 / NW;   // 1-KiB staging pieces per wave, tile and operand
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_kernel(const AttnFwdArgs 
   const int my_qb = min((qb * WQ + wave * 32) / BQ, nqb - 1);
   const uint8_t* fl = GENERAL ? a.flags + ((int64_t)b * nqb + my_qb) * nkt : nullptr;
   const uint8_t* fl0 = GENERAL ? a.flags + ((int64_t)b * nqb + min(qb * WQ / BQ, nqb - 1)) * nkt : nullptr;
-  const uint8_t* fl1 = GENERAL ? a.flags + ((int64_t)b * nqb + min(qb * WQ / BQ + (NW > 4 ? 1 : 0), nqb - 1)) * nkt : nullptr;
+  const uint8_t* fl1 = GENERAL ? a.flags + ((int64_t)b * nqb + min(qb * WQ / BQ + 1, nqb - 1)) * nkt : nullptr;
   const int kt_end = GENERAL ? nkt : min(nkt, (qb * WQ + WQ + BKV - 1) / BKV);
   // GENERAL: the three flag bytes of a tile (this wave's block, the workgroup's two blocks) are fetched 64 tiles at a time into ONE
   // register - lane i holds tile 64*chunk + i - and read with v_readlane: as a byte load per tile and block they put two or three
@@ -390,16 +390,12 @@ extern "C" int llx_attn_fwd(const void* q, int64_t q_sb, int64_t q_ss, const voi
   LLX_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 == 0 && (uintptr_t)o % 8 == 0, "llx_attn_fwd: unaligned pointer");
   LLX_REQUIRE(!(doc_ids || prefix_len) || flags, "llx_attn_fwd: tile flags required with doc_ids/prefix_len");
   LLX_REQUIRE(S < (1 << 24), "llx_attn_fwd: S too large");
-  static int nw = 0;  // LLX_ATTN_FWD_NW=4: the 128-row workgroup (two per CU) this kernel had before, kept for A/B measurements
   {
     static std::once_flag once;  // forward may be entered from several host threads (activation checkpointing recomputes it in backward)
     static hipError_t err = hipSuccess;
     std::call_once(once, [] {
-      const char* e = getenv("LLX_ATTN_FWD_NW");
-      nw = (e && e[0] == '4') ? 4 : 8;
-      const void* fns[4] = {(const void*)attn_fwd_kernel<false, false, 4>, (const void*)attn_fwd_kernel<true, false, 4>,
-                            (const void*)attn_fwd_kernel<false, false, 8>, (const void*)attn_fwd_kernel<true, false, 8>};
-      for (int i = 0; i < 4 && err == hipSuccess; ++i) err = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, ATT_LDS_BYTES);
+      const void* fns[2] = {(const void*)attn_fwd_kernel<false, false, 8>, (const void*)attn_fwd_kernel<true, false, 8>};
+      for (int i = 0; i < 2 && err == hipSuccess; ++i) err = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, ATT_LDS_BYTES);
     });
     if (err != hipSuccess) { llx_set_error("llx_attn_fwd: %s", hipGetErrorString(err)); return LLX_ERR_LAUNCH; }
   }
@@ -410,14 +406,9 @@ extern "C" int llx_attn_fwd(const void* q, int64_t q_sb, int64_t q_ss, const voi
   a.B = (int)B; a.S = (int)S; a.H = (int)H; a.KVH = (int)KVH;
   a.scale_log2 = scale * 1.4426950408889634f;
   a.stamps = nullptr;
-  const dim3 grid((unsigned)H, (unsigned)cdiv64(S, 32 * nw), (unsigned)B), block(64 * nw);
-  if (nw == 8) {
-    if (a.flags) hipLaunchKernelGGL((attn_fwd_kernel<true, false, 8>), grid, block, ATT_LDS_BYTES, stream, a);
-    else hipLaunchKernelGGL((attn_fwd_kernel<false, false, 8>), grid, block, ATT_LDS_BYTES, stream, a);
-  } else {
-    if (a.flags) hipLaunchKernelGGL((attn_fwd_kernel<true, false, 4>), grid, block, ATT_LDS_BYTES, stream, a);
-    else hipLaunchKernelGGL((attn_fwd_kernel<false, false, 4>), grid, block, ATT_LDS_BYTES, stream, a);
-  }
+  const dim3 grid((unsigned)H, (unsigned)cdiv64(S, 256), (unsigned)B), block(512);
+  if (a.flags) hipLaunchKernelGGL((attn_fwd_kernel<true, false, 8>), grid, block, ATT_LDS_BYTES, stream, a);
+  else hipLaunchKernelGGL((attn_fwd_kernel<false, false, 8>), grid, block, ATT_LDS_BYTES, stream, a);
   LLX_LAUNCH_CHECK("llx_attn_fwd");
   return LLX_OK;
 }

@@ -352,7 +352,7 @@ extern "C" int llx_gemv_bf16(const void* w0, int64_t ldw0, int64_t n0, const voi
   const int rpw = rpw_knob == 4 ? 4 : 2;
   const int64_t groups = epilogue == GV_SWIGLU ? (N / 2 + rpw / 2 - 1) / (rpw / 2) : (N + rpw - 1) / rpw;
   // the wave count is trimmed so that every wave gets the same number of row groups where possible
-  static const int wave_cap = [] { const char* e = getenv("LLX_GEMV_WAVES"); return e && atoi(e) >= 256 ? atoi(e) : 2048; }();
+  constexpr int wave_cap = 2048;
   const int64_t per_wave = cdiv64(groups, wave_cap);
   const int grid = (int)cdiv64(cdiv64(groups, per_wave), 4);
   const int64_t kstep = 512 * (8 / rpw);

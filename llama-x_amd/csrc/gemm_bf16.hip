@@ -12,7 +12,6 @@
 // consecutive output columns; the epilogue stages the bf16 tile through LDS and stores whole 512-B rows.
 #include "common.h"
 #include <type_traits>
-#include <stdlib.h>
 #include <mutex>
 
 #define BM 256
@@ -54,7 +53,9 @@ __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + e
 template <int EPI, bool I8, int PIPE, int BNT = 256>
 __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(const GemmArgs g) {
   static_assert(BNT == 256 || BNT == 128, "tile width");
-  static_assert(BNT == 256 || (PIPE == 1 && EPI != EPI_SWIGLU_FWD), "the half tile exists for the four-phase loop only");
+  // PIPE named a second, older main loop; it stays in the signature because bench.py, tools/ and profiles/ key on gemm_nt_kernel<EPI, I8, 1>
+  static_assert(PIPE == 1, "the four-phase main loop is the only one");
+  static_assert(BNT == 256 || EPI != EPI_SWIGLU_FWD, "the SwiGLU-forward epilogue needs the full tile");
   constexpr int ESZ = I8 ? 1 : 2;         // bytes per element
   constexpr int TK = 128 / ESZ;           // elements per 128-byte tile row (64 bf16 | 128 int8)
   constexpr int WNG = BNT / 64;           // wave columns (64 output columns per wave): 4 | 2
@@ -120,25 +121,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(const GemmArgs g) {
     aoff[i] = (uint32_t)((int64_t)arow[i] * g.lda * ESZ + schunk * 16);
     boff[i] = (uint32_t)((int64_t)brow[i] * g.ldb * ESZ + schunk * 16);
   }
-  // half = 0: the A tile, half = 1: the B tile (4 x 16-B global_load_lds per thread each)
-  auto stage_half = [&](int buf, int kt, int half) {
-    char* sT = smem + buf * STAGE_BYTES + half * A_TILE_BYTES;
-    if (kt < nk1) {
-      const char* base = (const char*)(half ? g.B : g.A) + (int64_t)(kt + kofs) * 128;  // wave-uniform
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        __builtin_amdgcn_global_load_lds((gbl_void*)(base + (half ? boff[i] : aoff[i])), (lds_void*)(sT + (i * 512 + wave * 64) * 16), 16, 0, 0);
-    } else {  // K-extension tiles (LoRA operands): a different pointer / stride pair, at most a few tiles per launch
-      const char* base = (const char*)(half ? g.B2 : g.A2) + (int64_t)(kt - nk1) * 128;
-      const int64_t l = (half ? g.ldb2 : g.lda2) * 2;  // the K-extension operands are bf16 in the int8 kernel too
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const char* src = base + (int64_t)(half ? brow[i] : arow[i]) * l + schunk * 16;
-        __builtin_amdgcn_global_load_lds((gbl_void*)src, (lds_void*)(sT + (i * 512 + wave * 64) * 16), 16, 0, 0);
-      }
-    }
-  };
-  auto stage = [&](int buf, int kt) { stage_half(buf, kt, 0); stage_half(buf, kt, 1); };
 
   // ---- fragment read offsets (bytes inside a tile): row*128 + ((ks*4 + (lane>>4)) ^ ((lane>>1)&7))*16
   const int frow = lane & 15;
@@ -156,197 +138,160 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(const GemmArgs g) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = acc_t{0, 0, 0, 0};
 
-  if constexpr (PIPE == 0) {
-    stage(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-
-    for (int kt = 0; kt < nk; ++kt) {
-      const int cur = kt & 1;
-      const char* sA = smem + cur * STAGE_BYTES;
-      const char* sB = sA + A_TILE_BYTES;
-  #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        if (kt + 1 < nk) stage_half(cur ^ 1, kt + 1, ks);  // spread the next tile's loads over the two k-steps
-        const int slot = ks ? slot1 : slot0;
-        // 16-byte fragments: 8 bf16 (k = 8*(lane>>4)+j) or 16 int8 (k = 16*(lane>>4)+j) -- same bytes, same addresses
-        i32x4_t af[8], bfr[4];
-  #pragma unroll
-        for (int ni = 0; ni < 4; ++ni) bfr[ni] = *reinterpret_cast<const i32x4_t*>(sB + b_base + ni * 16 * 128 + slot);
-  #pragma unroll
-        for (int mi = 0; mi < 8; ++mi) af[mi] = *reinterpret_cast<const i32x4_t*>(sA + a_base + mi * 16 * 128 + slot);
-        __builtin_amdgcn_s_setprio(1);
-  #pragma unroll
-        for (int mi = 0; mi < 8; ++mi)
-  #pragma unroll
-          for (int ni = 0; ni < 4; ++ni) {
-            if constexpr (I8)
-              acc[mi][ni] = __builtin_amdgcn_mfma_i32_16x16x64_i8(bfr[ni], af[mi], acc[mi][ni], 0, 0, 0);
-            else
-              acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, bfr[ni]), __builtin_bit_cast(bf16x8_t, af[mi]),
-                                                                    acc[mi][ni], 0, 0, 0);
-          }
-        __builtin_amdgcn_s_setprio(0);
+  // ---- deep pipeline: 4 phases per K-tile (one 64x32 accumulator quadrant = 16 MFMAs each), one 16-KiB half-tile
+  // (A rows 0-127 | A rows 128-255 | B rows 0-127 | B rows 128-255) staged per phase, loads kept in flight ACROSS the
+  // barriers behind a counted vmcnt.  Half-tiles of K-tile T are issued:  B-lo, B-hi, A-lo in phases 1,2,3 of tile T-2
+  // and A-hi in phase 0 of tile T-1, i.e. 5-7 phases before their first read.  LDS reuse (same 2 x 64 KiB stages):
+  //   B(t) is read only in phase 0 (both 32-column halves stay in registers) -> free for B(t+2) after the phase-0 barrier
+  //   A(t) is read in phases 0 and 2 -> free for A(t+2) after the phase-2 barrier.
+  // pieces (8 KiB = 64 tile rows, one global_load_lds per thread) of a half-tile: A 2, B BSI / 2
+  auto stage_q = [&](int kt, int which) {  // which: 0 A-lo, 1 A-hi, 2 B-lo, 3 B-hi of K-tile kt into stage kt&1
+    if (kt >= nk) return;
+    const int half = which >> 1, hi = which & 1;
+    const int np = half ? BSI / 2 : 2;
+    char* sT = smem + (kt & 1) * STAGE_BYTES + half * A_TILE_BYTES + hi * np * 8192;
+    if (kt < nk1) {
+      const char* base = (const char*)(half ? g.B : g.A) + (int64_t)(kt + kofs) * 128;
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+        if (j < np)
+          __builtin_amdgcn_global_load_lds((gbl_void*)(base + (half ? boff[np * hi + j] : aoff[2 * hi + j])), (lds_void*)(sT + (j * 512 + wave * 64) * 16), 16, 0, 0);
+    } else {
+      const char* base = (const char*)(half ? g.B2 : g.A2) + (int64_t)(kt - nk1) * 128;
+      const int64_t l = (half ? g.ldb2 : g.lda2) * 2;  // the K-extension operands are bf16 in the int8 kernel too
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        if (j < np) {
+          const char* src = base + (int64_t)(half ? brow[np * hi + j] : arow[2 * hi + j]) * l + schunk * 16;
+          __builtin_amdgcn_global_load_lds((gbl_void*)src, (lds_void*)(sT + (j * 512 + wave * 64) * 16), 16, 0, 0);
+        }
       }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
     }
-  } else {
-    // ---- deep pipeline: 4 phases per K-tile (one 64x32 accumulator quadrant = 16 MFMAs each), one 16-KiB half-tile
-    // (A rows 0-127 | A rows 128-255 | B rows 0-127 | B rows 128-255) staged per phase, loads kept in flight ACROSS the
-    // barriers behind a counted vmcnt.  Half-tiles of K-tile T are issued:  B-lo, B-hi, A-lo in phases 1,2,3 of tile T-2
-    // and A-hi in phase 0 of tile T-1, i.e. 5-7 phases before their first read.  LDS reuse (same 2 x 64 KiB stages):
-    //   B(t) is read only in phase 0 (both 32-column halves stay in registers) -> free for B(t+2) after the phase-0 barrier
-    //   A(t) is read in phases 0 and 2 -> free for A(t+2) after the phase-2 barrier.
-    // pieces (8 KiB = 64 tile rows, one global_load_lds per thread) of a half-tile: A 2, B BSI / 2
-    auto stage_q = [&](int kt, int which) {  // which: 0 A-lo, 1 A-hi, 2 B-lo, 3 B-hi of K-tile kt into stage kt&1
-      if (kt >= nk) return;
-      const int half = which >> 1, hi = which & 1;
-      const int np = half ? BSI / 2 : 2;
-      char* sT = smem + (kt & 1) * STAGE_BYTES + half * A_TILE_BYTES + hi * np * 8192;
-      if (kt < nk1) {
-        const char* base = (const char*)(half ? g.B : g.A) + (int64_t)(kt + kofs) * 128;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          if (j < np)
-            __builtin_amdgcn_global_load_lds((gbl_void*)(base + (half ? boff[np * hi + j] : aoff[2 * hi + j])), (lds_void*)(sT + (j * 512 + wave * 64) * 16), 16, 0, 0);
-      } else {
-        const char* base = (const char*)(half ? g.B2 : g.A2) + (int64_t)(kt - nk1) * 128;
-        const int64_t l = (half ? g.ldb2 : g.lda2) * 2;  // the K-extension operands are bf16 in the int8 kernel too
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          if (j < np) {
-            const char* src = base + (int64_t)(half ? brow[np * hi + j] : arow[2 * hi + j]) * l + schunk * 16;
-            __builtin_amdgcn_global_load_lds((gbl_void*)src, (lds_void*)(sT + (j * 512 + wave * 64) * 16), 16, 0, 0);
-          }
-        }
-      }
-    };
-    // int8 kernel with a K-extension (LoRA on an int8 base, dynamic activations): after the last int8 K-tile the int32
-    // accumulators are dequantised IN PLACE (acc * a_scale[m] * b_scale[n], rounded to bf16 as the reference's int8_mm_dequant
-    // output is, kept as fp32 bits) and the bf16 extension tiles accumulate on top with the bf16 MFMA.
-    auto mfma_t = [&](auto ext_tag, const i32x4_t& b, const i32x4_t& a, acc_t& c) {
-      constexpr bool ext_phase = decltype(ext_tag)::value;
-      if constexpr (I8) {
-        if constexpr (ext_phase) {
-          f32x4_t cf = __builtin_bit_cast(f32x4_t, c);
-          cf = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, b), __builtin_bit_cast(bf16x8_t, a), cf, 0, 0, 0);
-          c = __builtin_bit_cast(acc_t, cf);
-        } else {
-          c = __builtin_amdgcn_mfma_i32_16x16x64_i8(b, a, c, 0, 0, 0);
-        }
-      } else {
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, b), __builtin_bit_cast(bf16x8_t, a), c, 0, 0, 0);
-      }
-    };
-    auto dequant_in_place = [&]() {
-      if constexpr (I8) {
-        // the 16 column scales and MI row scales of this lane are requested together, once (as written per accumulator element
-        // they were 128 two-byte loads per lane behind 40-odd s_waitcnt vmcnt(0))
-        float sbv[4][4], rsv[MI];
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) sbv[ni][e] = bf2f(g.sb[col_of(wn * 64 + ni * 16 + fq * 4 + e)]);
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi) rsv[mi] = bf2f(g.sa[min(m0 + wm * WR + mi * 16 + frow, g.M - 1)]);
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi) {
-          const float rs = rsv[mi];
-#pragma unroll
-          for (int ni = 0; ni < 4; ++ni) {
-            f32x4_t cf;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) cf[e] = bf2f(f2bf(((float)acc[mi][ni][e] * rs) * sbv[ni][e]));
-            acc[mi][ni] = __builtin_bit_cast(acc_t, cf);
-          }
-        }
-      }
-    };
-    // prologue: all of tile 0, then B-lo, B-hi, A-lo of tile 1
-    stage_q(0, 0); stage_q(0, 1); stage_q(0, 2); stage_q(0, 3);
-    stage_q(1, 2); stage_q(1, 3); stage_q(1, 0);
-    auto ktile = [&](int kt, auto ext_tag) __attribute__((always_inline)) {
-      auto mfma = [&](const i32x4_t& b, const i32x4_t& a, acc_t& c) { mfma_t(ext_tag, b, a, c); };
-      const char* sA = smem + (kt & 1) * STAGE_BYTES;
-      const char* sB = sA + A_TILE_BYTES;
-      // ---------------- phase 0: tile kt has landed once all but the youngest loads (3 half-tiles of kt+1: A-lo 2 pieces, B-lo and B-hi
-      // BSI / 2 each = 6 | 4 loads per thread) are done
-      if (kt + 1 < nk) {
-        if constexpr (BSI == 4) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      stage_q(kt + 1, 1);  // A-hi of the next tile (its stage's A-hi was last read in phase 2 of tile kt-1)
-      i32x4_t bfr[2][4], af[2 * MH];  // bfr[ks][nh*2 + n2], af[ks*MH + m4]
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) bfr[ks][ni] = *reinterpret_cast<const i32x4_t*>(sB + b_base + ni * 16 * 128 + (ks ? slot1 : slot0));
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int m4 = 0; m4 < MH; ++m4) af[ks * MH + m4] = *reinterpret_cast<const i32x4_t*>(sA + a_base + m4 * 16 * 128 + (ks ? slot1 : slot0));
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int m4 = 0; m4 < MH; ++m4)
-#pragma unroll
-          for (int n2 = 0; n2 < 2; ++n2) mfma(bfr[ks][n2], af[ks * MH + m4], acc[m4][n2]);
-      __builtin_amdgcn_s_setprio(0);
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_s_barrier();  // every wave has its B fragments: B(kt) may be overwritten
-      asm volatile("" ::: "memory");
-      // ---------------- phase 1: quadrant (first row half, cols 32-63)
-      stage_q(kt + 2, 2);
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int m4 = 0; m4 < MH; ++m4)
-#pragma unroll
-          for (int n2 = 0; n2 < 2; ++n2) mfma(bfr[ks][2 + n2], af[ks * MH + m4], acc[m4][2 + n2]);
-      __builtin_amdgcn_s_setprio(0);
-      // ---------------- phase 2: quadrant (second row half, cols 32-63)
-      stage_q(kt + 2, 3);
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int m4 = 0; m4 < MH; ++m4) af[ks * MH + m4] = *reinterpret_cast<const i32x4_t*>(sA + a_base + (MH + m4) * 16 * 128 + (ks ? slot1 : slot0));
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int m4 = 0; m4 < MH; ++m4)
-#pragma unroll
-          for (int n2 = 0; n2 < 2; ++n2) mfma(bfr[ks][2 + n2], af[ks * MH + m4], acc[MH + m4][2 + n2]);
-      __builtin_amdgcn_s_setprio(0);
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_s_barrier();  // every wave has its second A half: A(kt) may be overwritten
-      asm volatile("" ::: "memory");
-      // ---------------- phase 3: quadrant (second row half, cols 0-31)
-      stage_q(kt + 2, 0);
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int m4 = 0; m4 < MH; ++m4)
-#pragma unroll
-          for (int n2 = 0; n2 < 2; ++n2) mfma(bfr[ks][n2], af[ks * MH + m4], acc[MH + m4][n2]);
-      __builtin_amdgcn_s_setprio(0);
-    };
-    const int nk_main = I8 ? nk1 : nk;  // bf16: the K-extension tiles use the same MFMA and simply continue the loop
-    for (int kt = 0; kt < nk_main; ++kt) ktile(kt, std::false_type{});
+  };
+  // int8 kernel with a K-extension (LoRA on an int8 base, dynamic activations): after the last int8 K-tile the int32
+  // accumulators are dequantised IN PLACE (acc * a_scale[m] * b_scale[n], rounded to bf16 as the reference's int8_mm_dequant
+  // output is, kept as fp32 bits) and the bf16 extension tiles accumulate on top with the bf16 MFMA.
+  auto mfma_t = [&](auto ext_tag, const i32x4_t& b, const i32x4_t& a, acc_t& c) {
+    constexpr bool ext_phase = decltype(ext_tag)::value;
     if constexpr (I8) {
-      if (nk > nk1) {
-        dequant_in_place();
-        for (int kt = nk1; kt < nk; ++kt) ktile(kt, std::true_type{});
+      if constexpr (ext_phase) {
+        f32x4_t cf = __builtin_bit_cast(f32x4_t, c);
+        cf = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, b), __builtin_bit_cast(bf16x8_t, a), cf, 0, 0, 0);
+        c = __builtin_bit_cast(acc_t, cf);
+      } else {
+        c = __builtin_amdgcn_mfma_i32_16x16x64_i8(b, a, c, 0, 0, 0);
+      }
+    } else {
+      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, b), __builtin_bit_cast(bf16x8_t, a), c, 0, 0, 0);
+    }
+  };
+  auto dequant_in_place = [&]() {
+    if constexpr (I8) {
+      // the 16 column scales and MI row scales of this lane are requested together, once (as written per accumulator element
+      // they were 128 two-byte loads per lane behind 40-odd s_waitcnt vmcnt(0))
+      float sbv[4][4], rsv[MI];
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) sbv[ni][e] = bf2f(g.sb[col_of(wn * 64 + ni * 16 + fq * 4 + e)]);
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi) rsv[mi] = bf2f(g.sa[min(m0 + wm * WR + mi * 16 + frow, g.M - 1)]);
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi) {
+        const float rs = rsv[mi];
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni) {
+          f32x4_t cf;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) cf[e] = bf2f(f2bf(((float)acc[mi][ni][e] * rs) * sbv[ni][e]));
+          acc[mi][ni] = __builtin_bit_cast(acc_t, cf);
+        }
       }
     }
-    __syncthreads();  // all LDS reads done before the epilogue reuses the stages
+  };
+  // prologue: all of tile 0, then B-lo, B-hi, A-lo of tile 1
+  stage_q(0, 0); stage_q(0, 1); stage_q(0, 2); stage_q(0, 3);
+  stage_q(1, 2); stage_q(1, 3); stage_q(1, 0);
+  auto ktile = [&](int kt, auto ext_tag) __attribute__((always_inline)) {
+    auto mfma = [&](const i32x4_t& b, const i32x4_t& a, acc_t& c) { mfma_t(ext_tag, b, a, c); };
+    const char* sA = smem + (kt & 1) * STAGE_BYTES;
+    const char* sB = sA + A_TILE_BYTES;
+    // ---------------- phase 0: tile kt has landed once all but the youngest loads (3 half-tiles of kt+1: A-lo 2 pieces, B-lo and B-hi
+    // BSI / 2 each = 6 | 4 loads per thread) are done
+    if (kt + 1 < nk) {
+      if constexpr (BSI == 4) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    stage_q(kt + 1, 1);  // A-hi of the next tile (its stage's A-hi was last read in phase 2 of tile kt-1)
+    i32x4_t bfr[2][4], af[2 * MH];  // bfr[ks][nh*2 + n2], af[ks*MH + m4]
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni) bfr[ks][ni] = *reinterpret_cast<const i32x4_t*>(sB + b_base + ni * 16 * 128 + (ks ? slot1 : slot0));
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int m4 = 0; m4 < MH; ++m4) af[ks * MH + m4] = *reinterpret_cast<const i32x4_t*>(sA + a_base + m4 * 16 * 128 + (ks ? slot1 : slot0));
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int m4 = 0; m4 < MH; ++m4)
+#pragma unroll
+        for (int n2 = 0; n2 < 2; ++n2) mfma(bfr[ks][n2], af[ks * MH + m4], acc[m4][n2]);
+    __builtin_amdgcn_s_setprio(0);
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_barrier();  // every wave has its B fragments: B(kt) may be overwritten
+    asm volatile("" ::: "memory");
+    // ---------------- phase 1: quadrant (first row half, cols 32-63)
+    stage_q(kt + 2, 2);
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int m4 = 0; m4 < MH; ++m4)
+#pragma unroll
+        for (int n2 = 0; n2 < 2; ++n2) mfma(bfr[ks][2 + n2], af[ks * MH + m4], acc[m4][2 + n2]);
+    __builtin_amdgcn_s_setprio(0);
+    // ---------------- phase 2: quadrant (second row half, cols 32-63)
+    stage_q(kt + 2, 3);
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int m4 = 0; m4 < MH; ++m4) af[ks * MH + m4] = *reinterpret_cast<const i32x4_t*>(sA + a_base + (MH + m4) * 16 * 128 + (ks ? slot1 : slot0));
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int m4 = 0; m4 < MH; ++m4)
+#pragma unroll
+        for (int n2 = 0; n2 < 2; ++n2) mfma(bfr[ks][2 + n2], af[ks * MH + m4], acc[MH + m4][2 + n2]);
+    __builtin_amdgcn_s_setprio(0);
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_barrier();  // every wave has its second A half: A(kt) may be overwritten
+    asm volatile("" ::: "memory");
+    // ---------------- phase 3: quadrant (second row half, cols 0-31)
+    stage_q(kt + 2, 0);
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int m4 = 0; m4 < MH; ++m4)
+#pragma unroll
+        for (int n2 = 0; n2 < 2; ++n2) mfma(bfr[ks][n2], af[ks * MH + m4], acc[MH + m4][n2]);
+    __builtin_amdgcn_s_setprio(0);
+  };
+  const int nk_main = I8 ? nk1 : nk;  // bf16: the K-extension tiles use the same MFMA and simply continue the loop
+  for (int kt = 0; kt < nk_main; ++kt) ktile(kt, std::false_type{});
+  if constexpr (I8) {
+    if (nk > nk1) {
+      dequant_in_place();
+      for (int kt = nk1; kt < nk; ++kt) ktile(kt, std::true_type{});
+    }
   }
+  __syncthreads();  // all LDS reads done before the epilogue reuses the stages
 
   if constexpr (EPI == EPI_SPLITK) {
     // fp32 partial product of this K range, straight from the accumulators (16 B per lane: 4 consecutive columns of one row)
@@ -536,22 +481,9 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(const GemmArgs g) {
   }
 }
 
-#ifndef LLX_GEMM_PIPE_DEFAULT
-#define LLX_GEMM_PIPE_DEFAULT 1
-#endif
-
-static int gemm_pipe_mode() {
-  static int mode = -1;
-  if (mode < 0) {
-    const char* e = getenv("LLX_GEMM_PIPE");
-    mode = e ? (e[0] == '0' ? 0 : 1) : LLX_GEMM_PIPE_DEFAULT;
-  }
-  return mode;
-}
-
-template <int EPI, bool I8, int PIPE, int BNT = 256>
+template <int EPI, bool I8, int BNT = 256>
 static int launch_gemm_p(const GemmArgs& a, hipStream_t stream) {
-  auto kern = gemm_nt_kernel<EPI, I8, PIPE, BNT>;
+  auto kern = gemm_nt_kernel<EPI, I8, 1, BNT>;
   // forward and autograd's backward thread may both be the first caller: the attribute is set exactly once, race-free
   static std::once_flag attr_once;
   static hipError_t attr_err = hipSuccess;
@@ -565,37 +497,47 @@ static int launch_gemm_p(const GemmArgs& a, hipStream_t stream) {
   return LLX_OK;
 }
 
-static int gemm_tail_mode() {  // LLX_GEMM_TAIL=0: never split off the half-tile launch (A/B knob)
-  static int mode = -1;
-  if (mode < 0) {
-    const char* e = getenv("LLX_GEMM_TAIL");
-    mode = (e && e[0] == '0') ? 0 : 1;
-  }
-  return mode;
-}
-
 // A grid of 256 x 256 tiles whose last round of 256 CUs would be at most half full (q|k|v forward: 384 tiles = 1.5 rounds; w2 data
 // gradient: 896 = 3.5) is cut in two launches: the columns that fill whole rounds with full tiles, and the remaining columns with
 // 256 x 128 half tiles (twice as many workgroups, each moving 3/4 of a full tile's operand bytes - the per-CU delivery rate, not
 // the MFMA pipe, sets a tile's time), so the last round is full and 1/4 shorter.  Results are bit-identical (same K order per output).
 template <int EPI, bool I8 = false>
 static int launch_gemm(const GemmArgs& a, hipStream_t stream) {
-  if (!gemm_pipe_mode()) return launch_gemm_p<EPI, I8, 0>(a, stream);
   if constexpr (EPI != EPI_SWIGLU_FWD) {
     const int tiles = a.grid_m * a.grid_n, tail = tiles % 256;
-    if (gemm_tail_mode() && a.col0 == 0 && a.col_end == a.N && a.N % 256 == 0 && tiles > 256 && tail > 0 && tail <= 128 && tail % a.grid_m == 0) {
+    if (a.col0 == 0 && a.col_end == a.N && a.N % 256 == 0 && tiles > 256 && tail > 0 && tail <= 128 && tail % a.grid_m == 0) {
       const int tail_cols = tail / a.grid_m * 256;
       GemmArgs full = a, half = a;
       full.col_end = a.N - tail_cols;
       full.grid_n = a.grid_n - tail / a.grid_m;
       half.col0 = a.N - tail_cols;
       half.grid_n = tail_cols / 128;
-      const int rc = launch_gemm_p<EPI, I8, 1, 256>(full, stream);
+      const int rc = launch_gemm_p<EPI, I8, 256>(full, stream);
       if (rc != LLX_OK) return rc;
-      return launch_gemm_p<EPI, I8, 1, 128>(half, stream);
+      return launch_gemm_p<EPI, I8, 128>(half, stream);
     }
   }
-  return launch_gemm_p<EPI, I8, 1>(a, stream);
+  return launch_gemm_p<EPI, I8>(a, stream);
+}
+
+// The fields every entry point sets the same way; the rest (K-extension, epilogue operand, scales, RoPE, row count, split-K) start
+// out null / 0 and each entry point fills in what it uses.
+static GemmArgs make_args(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t M, int64_t N, int64_t K) {
+  GemmArgs a = {};
+  a.A = (const bf16_t*)A; a.B = (const bf16_t*)B; a.C = (bf16_t*)C;
+  a.lda = lda; a.ldb = ldb; a.ldc = ldc;
+  a.M = (int)M; a.N = (int)N; a.K = (int)K;
+  a.grid_m = (int)cdiv64(M, BM); a.grid_n = (int)cdiv64(N, BN);
+  a.col_end = (int)N;
+  a.splits = 1;
+  return a;
+}
+
+// What the kernel's 32-bit tile arithmetic asks of every problem (esz = bytes per A / B element); `who` names the entry point.
+static int check_extent(const char* who, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int esz) {
+  LLX_REQUIRE(M < (1 << 30) && N < (1 << 30) && K < (1 << 30), "%s: dimension too large", who);
+  LLX_REQUIRE(M * lda * esz < (int64_t)4294967296 && N * ldb * esz < (int64_t)4294967296, "%s: operand larger than 4 GiB (32-bit tile offsets)", who);
+  return LLX_OK;
 }
 
 // C[M,N] = A[M,K].B[N,K]^T (+ A2[M,K2].B2[N,K2]^T), bf16 in/out, fp32 accumulate.
@@ -620,19 +562,12 @@ static int gemm_nt_bf16_impl(const void* A, int64_t lda, const void* B, int64_t 
               "llx_gemm_nt_bf16_rope: need an aligned fp32 table, rope_S > 0 and rope_cols a multiple of 128 within N");
   LLX_REQUIRE((epilogue != EPI_RESIDUAL && epilogue != EPI_SWIGLU_BWD) || lde % 8 == 0, "llx_gemm_nt_bf16: residual / gate|up stride must be a multiple of 8");
   LLX_REQUIRE(epilogue != EPI_SWIGLU_BWD || (lde >= 2 * N && ldc >= 2 * N), "llx_gemm_nt_bf16: the SwiGLU-backward epilogue reads E[M,2N] (gate|up) and writes C[M,2N] (dg|du)");
-  LLX_REQUIRE(M < (1 << 30) && N < (1 << 30) && K < (1 << 30), "llx_gemm_nt_bf16: dimension too large");
-  LLX_REQUIRE(M * lda * 2 < (int64_t)4294967296 && N * ldb * 2 < (int64_t)4294967296, "llx_gemm_nt_bf16: operand larger than 4 GiB (32-bit tile offsets)");
-  GemmArgs a;
-  a.A = (const bf16_t*)A; a.B = (const bf16_t*)B; a.C = (bf16_t*)C;
-  a.A2 = (const bf16_t*)A2; a.B2 = (const bf16_t*)B2; a.E = (const bf16_t*)E; a.E2 = nullptr;
-  a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.lde = lde; a.lda2 = lda2; a.ldb2 = ldb2;
-  a.M = (int)M; a.N = (int)N; a.K = (int)K; a.K2 = (int)K2;
-  a.grid_m = (int)cdiv64(M, BM); a.grid_n = (int)cdiv64(N, BN);
-  a.col0 = 0; a.col_end = (int)N;
+  if (const int rc = check_extent("llx_gemm_nt_bf16", M, N, K, lda, ldb, 2); rc != LLX_OK) return rc;
+  GemmArgs a = make_args(A, lda, B, ldb, C, ldc, M, N, K);
+  a.A2 = (const bf16_t*)A2; a.B2 = (const bf16_t*)B2; a.lda2 = lda2; a.ldb2 = ldb2; a.K2 = (int)K2;
+  a.E = (const bf16_t*)E; a.lde = lde;
   a.rope = rope; a.rope_S = (int)rope_S; a.rope_cols = (int)rope_cols;
-  a.sa = nullptr; a.sb = nullptr;
   a.m_valid = m_valid;
-  a.C32 = nullptr; a.splits = 1;
   switch (epilogue) {
     case EPI_NONE: return launch_gemm<EPI_NONE>(a, stream);
     case EPI_RESIDUAL: return launch_gemm<EPI_RESIDUAL>(a, stream);
@@ -679,21 +614,12 @@ extern "C" int llx_gemm_nt_bf16_splitk(const void* A, int64_t lda, const void* B
   LLX_REQUIRE(K % ((int64_t)BK * splits) == 0, "llx_gemm_nt_bf16_splitk: K=%lld must be a multiple of 64 * splits (%d)", (long long)K, splits);
   LLX_REQUIRE(N % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0, "llx_gemm_nt_bf16_splitk: N and the row strides must be multiples of 8");
   LLX_REQUIRE(((uintptr_t)A | (uintptr_t)B | (uintptr_t)partial) % 16 == 0, "llx_gemm_nt_bf16_splitk: pointers must be 16-byte aligned");
-  LLX_REQUIRE(M < (1 << 30) && N < (1 << 30) && K < (1 << 30), "llx_gemm_nt_bf16_splitk: dimension too large");
-  LLX_REQUIRE(M * lda * 2 < (int64_t)4294967296 && N * ldb * 2 < (int64_t)4294967296, "llx_gemm_nt_bf16_splitk: operand larger than 4 GiB (32-bit tile offsets)");
-  LLX_REQUIRE(gemm_pipe_mode() == 1, "llx_gemm_nt_bf16_splitk: needs the four-phase main loop (LLX_GEMM_PIPE unset or 1)");
+  if (const int rc = check_extent("llx_gemm_nt_bf16_splitk", M, N, K, lda, ldb, 2); rc != LLX_OK) return rc;
   LLX_REQUIRE(m_valid == nullptr || (uintptr_t)m_valid % 4 == 0, "llx_gemm_nt_bf16_splitk: m_valid must be a device int32 pointer");
-  GemmArgs a;
-  a.A = (const bf16_t*)A; a.B = (const bf16_t*)B; a.C = nullptr; a.A2 = nullptr; a.B2 = nullptr; a.E = nullptr; a.E2 = nullptr;
-  a.lda = lda; a.ldb = ldb; a.ldc = N; a.lde = 0; a.lda2 = 0; a.ldb2 = 0;
-  a.M = (int)M; a.N = (int)N; a.K = (int)K; a.K2 = 0;
-  a.grid_m = (int)cdiv64(M, BM); a.grid_n = (int)cdiv64(N, BN);
-  a.col0 = 0; a.col_end = (int)N;
-  a.rope = nullptr; a.rope_S = 0; a.rope_cols = 0;
-  a.sa = nullptr; a.sb = nullptr;
+  GemmArgs a = make_args(A, lda, B, ldb, nullptr, N, M, N, K);
   a.m_valid = m_valid;
   a.C32 = partial; a.splits = splits;
-  return launch_gemm_p<EPI_SPLITK, false, 1>(a, stream);
+  return launch_gemm_p<EPI_SPLITK, false>(a, stream);
 }
 
 // out[i] = bf16(scale[0] * bf16(sum_s partial[s][row(i)][:]))  with row(i) = inv ? inv[i] : i; rows with inv[i] < 0 are zero.
@@ -752,18 +678,9 @@ extern "C" int llx_int8_mm_dequant(const void* A, int64_t lda, const void* B, in
   LLX_REQUIRE(N % 8 == 0 && ldc % 8 == 0, "llx_int8_mm_dequant: N and ldc must be multiples of 8");
   LLX_REQUIRE(lda % 16 == 0 && ldb % 16 == 0, "llx_int8_mm_dequant: int8 row strides must be multiples of 16");
   LLX_REQUIRE(((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) % 16 == 0, "llx_int8_mm_dequant: pointers must be 16-byte aligned");
-  LLX_REQUIRE(M < (1 << 30) && N < (1 << 30) && K < (1 << 30), "%s: dimension too large", "llx_int8_mm_dequant");
-  LLX_REQUIRE(M * lda < (int64_t)4294967296 && N * ldb < (int64_t)4294967296, "%s: operand larger than 4 GiB (32-bit tile offsets)", "llx_int8_mm_dequant");
-  GemmArgs a;
-  a.A = (const bf16_t*)A; a.B = (const bf16_t*)B; a.C = (bf16_t*)C; a.A2 = nullptr; a.B2 = nullptr;
-  a.E = nullptr; a.E2 = nullptr; a.sa = (const bf16_t*)a_scale; a.sb = (const bf16_t*)b_scale;
-  a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.lde = 0; a.lda2 = 0; a.ldb2 = 0;
-  a.M = (int)M; a.N = (int)N; a.K = (int)K; a.K2 = 0;
-  a.grid_m = (int)cdiv64(M, BM); a.grid_n = (int)cdiv64(N, BN);
-  a.col0 = 0; a.col_end = (int)N;
-  a.rope = nullptr; a.rope_S = 0; a.rope_cols = 0;
-  a.m_valid = nullptr;
-  a.C32 = nullptr; a.splits = 1;
+  if (const int rc = check_extent("llx_int8_mm_dequant", M, N, K, lda, ldb, 1); rc != LLX_OK) return rc;
+  GemmArgs a = make_args(A, lda, B, ldb, C, ldc, M, N, K);
+  a.sa = (const bf16_t*)a_scale; a.sb = (const bf16_t*)b_scale;
   return launch_gemm<EPI_ROWCOLSCALE, true>(a, stream);
 }
 
@@ -777,18 +694,9 @@ extern "C" int llx_int8_mm_dequant_f32(const void* A, int64_t lda, const void* B
   LLX_REQUIRE(N % 8 == 0 && ldc % 4 == 0, "llx_int8_mm_dequant_f32: N must be a multiple of 8 and ldc of 4");
   LLX_REQUIRE(lda % 16 == 0 && ldb % 16 == 0, "llx_int8_mm_dequant_f32: int8 row strides must be multiples of 16");
   LLX_REQUIRE(((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)b_scale) % 16 == 0 && (uintptr_t)a_scale % 4 == 0, "llx_int8_mm_dequant_f32: unaligned pointer");
-  LLX_REQUIRE(M < (1 << 30) && N < (1 << 30) && K < (1 << 30), "%s: dimension too large", "llx_int8_mm_dequant_f32");
-  LLX_REQUIRE(M * lda < (int64_t)4294967296 && N * ldb < (int64_t)4294967296, "%s: operand larger than 4 GiB (32-bit tile offsets)", "llx_int8_mm_dequant_f32");
-  GemmArgs a;
-  a.A = (const bf16_t*)A; a.B = (const bf16_t*)B; a.C = (bf16_t*)C; a.A2 = nullptr; a.B2 = nullptr;
-  a.E = nullptr; a.E2 = nullptr; a.sa = (const bf16_t*)a_scale; a.sb = (const bf16_t*)b_scale;
-  a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.lde = 0; a.lda2 = 0; a.ldb2 = 0;
-  a.M = (int)M; a.N = (int)N; a.K = (int)K; a.K2 = 0;
-  a.grid_m = (int)cdiv64(M, BM); a.grid_n = (int)cdiv64(N, BN);
-  a.col0 = 0; a.col_end = (int)N;
-  a.rope = nullptr; a.rope_S = 0; a.rope_cols = 0;
-  a.m_valid = nullptr;
-  a.C32 = nullptr; a.splits = 1;
+  if (const int rc = check_extent("llx_int8_mm_dequant_f32", M, N, K, lda, ldb, 1); rc != LLX_OK) return rc;
+  GemmArgs a = make_args(A, lda, B, ldb, C, ldc, M, N, K);
+  a.sa = (const bf16_t*)a_scale; a.sb = (const bf16_t*)b_scale;
   return launch_gemm<EPI_ROWCOLSCALE_F32, true>(a, stream);
 }
 
@@ -814,19 +722,12 @@ extern "C" int llx_int8_mm_dequant_ext(const void* A, int64_t lda, const void* B
   LLX_REQUIRE(epilogue != EPI_ROPE || (rope_table && (uintptr_t)rope_table % 16 == 0 && rope_S > 0 && rope_cols >= 0 && rope_cols <= N && rope_cols % 128 == 0),
               "llx_int8_mm_dequant_ext: bad RoPE arguments");
   LLX_REQUIRE(epilogue != EPI_SWIGLU_FWD || N % 256 == 0, "llx_int8_mm_dequant_ext: the SwiGLU epilogue needs N = 2I with I a multiple of 128");
-  LLX_REQUIRE(K2 == 0 || gemm_pipe_mode() == 1, "llx_int8_mm_dequant_ext: the K-extension needs the four-phase main loop (LLX_GEMM_PIPE unset or 1)");
-  LLX_REQUIRE(M < (1 << 30) && N < (1 << 30) && K < (1 << 30), "%s: dimension too large", "llx_int8_mm_dequant_ext");
-  LLX_REQUIRE(M * lda < (int64_t)4294967296 && N * ldb < (int64_t)4294967296, "%s: operand larger than 4 GiB (32-bit tile offsets)", "llx_int8_mm_dequant_ext");
-  GemmArgs a;
-  a.A = (const bf16_t*)A; a.B = (const bf16_t*)B; a.C = (bf16_t*)C; a.A2 = (const bf16_t*)A2; a.B2 = (const bf16_t*)B2;
-  a.E = (const bf16_t*)E; a.E2 = nullptr; a.sa = (const bf16_t*)a_scale; a.sb = (const bf16_t*)b_scale;
-  a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.lde = lde; a.lda2 = lda2; a.ldb2 = ldb2;
-  a.M = (int)M; a.N = (int)N; a.K = (int)K; a.K2 = (int)K2;
-  a.grid_m = (int)cdiv64(M, BM); a.grid_n = (int)cdiv64(N, BN);
-  a.col0 = 0; a.col_end = (int)N;
+  if (const int rc = check_extent("llx_int8_mm_dequant_ext", M, N, K, lda, ldb, 1); rc != LLX_OK) return rc;
+  GemmArgs a = make_args(A, lda, B, ldb, C, ldc, M, N, K);
+  a.sa = (const bf16_t*)a_scale; a.sb = (const bf16_t*)b_scale;
+  a.A2 = (const bf16_t*)A2; a.B2 = (const bf16_t*)B2; a.lda2 = lda2; a.ldb2 = ldb2; a.K2 = (int)K2;
+  a.E = (const bf16_t*)E; a.lde = lde;
   a.rope = rope_table; a.rope_S = (int)rope_S; a.rope_cols = (int)rope_cols;
-  a.m_valid = nullptr;
-  a.C32 = nullptr; a.splits = 1;
   switch (epilogue) {
     case EPI_RESIDUAL: return launch_gemm<EPI_RESIDUAL, true>(a, stream);
     case EPI_ROPE: return launch_gemm<EPI_ROPE, true>(a, stream);

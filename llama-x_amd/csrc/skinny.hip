@@ -3,7 +3,6 @@
 //   skinny_tn :  G[R, N]     = s * U[M, R]^T . Y[M, N]       (d lora_a = s * u^T x ; d lora_b^T = s * t^T dy)
 // Both are HBM-bound on the big operand (X or Y, read once); R <= 64 rides on 16x16x32 MFMA tiles.
 #include "common.h"
-#include <cstdlib>
 
 typedef __attribute__((address_space(3))) s16x4_t lds_s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8_t;
@@ -350,7 +349,7 @@ __global__ __launch_bounds__(256) void skinny_tn_many_kernel(const TnPartMany m)
 
 static int tn_splits(int64_t M, int64_t N) {
   const int64_t ntiles = cdiv64(N, TN_NT);
-  static const int target = getenv("LLX_TN_BLOCKS") ? atoi(getenv("LLX_TN_BLOCKS")) : 384;
+  constexpr int target = 384;
   int64_t want = cdiv64(target, ntiles);        // blocks per launch: 384 measured best over 128..1024 on the step's shapes (fewer, longer blocks and a smaller reduce)
   const int64_t max_split = cdiv64(M, 4 * TN_MS);  // at least 4 steps per block
   if (want > max_split) want = max_split;

@@ -7,6 +7,8 @@ from __future__ import annotations
 
 import ctypes
 import math
+import os
+from dataclasses import dataclass
 from typing import Optional, Sequence
 
 import torch
@@ -33,12 +35,9 @@ def _lib():
 def gemm_kernel_launches(M: int, N: int, epilogue: int) -> int:
     """Kernel launches behind one GEMM call: 2 when the launcher re-tiles the columns of a half-empty last round with 256 x 128 tiles
     (csrc/gemm_bf16.hip launch_gemm), else 1.  Accounting only (the GEMM trace of bench.py counts kernel launches, as rocprofv3 does)."""
-    import os
-
     gm, gn = -(-M // 256), -(-N // 256)
     tail = (gm * gn) % 256
-    split = (epilogue != EPI_SWIGLU_FWD and os.environ.get("LLX_GEMM_TAIL", "1") != "0" and os.environ.get("LLX_GEMM_PIPE", "1") != "0"
-             and N % 256 == 0 and gm * gn > 256 and 0 < tail <= 128 and tail % gm == 0)
+    split = epilogue != EPI_SWIGLU_FWD and N % 256 == 0 and gm * gn > 256 and 0 < tail <= 128 and tail % gm == 0
     return 2 if split else 1
 
 
@@ -244,8 +243,6 @@ def lora_pack(x: Tensor, out: Tensor, row_off: int, col_off: int, scale_: float 
 
 def lora_group_pack(lora_as: list, lora_bs: list, K_in: int, scale_: float):
     """(a_cat [R,K], b2 [N,64], bT [R,N], a2t [K,64]) for the members' LoRA factors, built by one launch."""
-    import ctypes
-
     nm = len(lora_as)
     Ns = [b.shape[0] for b in lora_bs]
     ranks = [a.shape[0] for a in lora_as]
@@ -274,8 +271,6 @@ def lora_group_pack(lora_as: list, lora_bs: list, K_in: int, scale_: float):
 def lora_groups_pack(groups: list) -> list:
     """[(lora_as, lora_bs, K_in, scale), ...] (<= 4 linear groups, e.g. the four of one transformer layer) -> [(a_cat, b2, bT, a2t), ...]
     as lora_group_pack builds them, from ONE launch and one buffer."""
-    import ctypes
-
     ng = len(groups)
     assert 1 <= ng <= 4
     sizes, metas = [], []
@@ -611,10 +606,8 @@ def _trace_end(trace, ev, *info):
         trace.append((ev[0], ev[1], *info))
 
 
-import os as _os
-
-_ATTN_BWD_DS = _os.environ.get("LLX_ATTN_BWD_DS", "0") == "1"
-_ATTN_BWD_DS_MAX = int(float(_os.environ.get("LLX_ATTN_BWD_DS_MAX_GB", "16")) * 2**30)
+_ATTN_BWD_DS = os.environ.get("LLX_ATTN_BWD_DS", "0") == "1"
+_ATTN_BWD_DS_MAX = int(float(os.environ.get("LLX_ATTN_BWD_DS_MAX_GB", "16")) * 2**30)
 
 
 def attn_bwd(q: Tensor, k: Tensor, v: Tensor, o: Tensor, do: Tensor, lse: Tensor, dq: Tensor, dk: Tensor, dv: Tensor,
@@ -748,9 +741,7 @@ def kv_scatter(k: Tensor, v: Tensor, k_cache: Tensor, v_cache: Tensor, input_pos
 
 
 _DECODE_WS: dict = {}
-
-
-_DECODE_WGS = int(_os.environ.get("LLX_DECODE_WGS", "512"))
+_DECODE_WGS = 512  # workgroups the decode attention aims for (nsplit * B * KVH)
 
 
 def attn_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, mask: Tensor, extent: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
@@ -876,18 +867,33 @@ def skinny_nt(x: Tensor, w: Tensor, kranges: Optional[Sequence[int]] = None, col
     return out
 
 
+@dataclass
+class TnQueued:
+    """One product queued by skinny_tn(..., pending=...): its first stage has run, skinny_tn_flush runs the second."""
+    ws: Tensor                      # fp32 split partials the first stage wrote
+    out: Tensor
+    out_ld: int
+    M: int
+    N: int
+    R: int
+    scale: float
+    transpose_out: int
+    accumulate: int
+    segs: Optional[ctypes.Array]    # int32 (n_lo, n_hi, r_lo, r_hi) per member, or None
+    n_segs: int
+    upart: Optional[Tensor] = None  # column-tile partials of u = y @ u_from^T (skinny_u_reduce sums them)
+
+
 def skinny_tn(u: Tensor, y: Tensor, R: int, scale_: float, out: Tensor, transpose_out: bool, accumulate: bool = False,
-              segs: Optional[Sequence[tuple[int, int, int, int]]] = None, pending: Optional[list] = None, defer: bool = False,
+              segs: Optional[Sequence[tuple[int, int, int, int]]] = None, pending: Optional[list] = None,
               u_from: Optional[Tensor] = None, scaled: Optional[tuple[Tensor, Tensor]] = None) -> Tensor:
     """out ([R,N], or [N,R] when transpose_out) (+)= scale * u[:, :R]^T @ y, u [M,64], y [M,N].
     segs: members (n_lo, n_hi, r_lo, r_hi) of a fused group (block-diagonal product): out is then a flat buffer that receives the
     members' [n, r] blocks one after another, each contiguous.
     pending: a list - only the first stage (fp32 split partials) is launched and the second stage is appended to it; ``out`` is valid
     once skinny_tn_flush(pending) has run (one launch for up to 4 products: the adapter gradients of a transformer block).
-    defer (with pending): the first stage waits too, until skinny_tn_partials(pending) / the flush launches it together with the other
-    queued products (u and y must stay untouched until then).
-    u_from (with pending, not deferred): the batched B^T image [R, N] of the group - the first stage then also emits the column-tile
-    partials of y @ u_from^T from the y tiles it stages (y is read once for both products); skinny_u_reduce(pending[-1]) finishes it.
+    u_from (with pending): the batched B^T image [R, N] of the group - the first stage then also emits the column-tile partials of
+    y @ u_from^T from the y tiles it stages (y is read once for both products); skinny_u_reduce(pending[-1]) finishes it.
     scaled = (colscale [N] bf16, g [M, N] bf16 output; with u_from): the first stage also writes g = bf16(y * colscale) - the scaled
     gradient an int8 linear's data gradient multiplies (subclasses/int8.py:127)."""
     _chk_bf16(u, y, out)
@@ -907,79 +913,52 @@ def skinny_tn(u: Tensor, y: Tensor, R: int, scale_: float, out: Tensor, transpos
         L.check(_lib().llx_skinny_tn(L.ptr(u), L.ptr(y), y.stride(0), L.ptr(out), out_ld, M, N, R, scale_, int(transpose_out), int(accumulate),
                                      L.ptr(ws), sp, ns, L.stream()), "llx_skinny_tn")
         return out
-    # queued: [ws, out, out_ld, M, N, R, scale, transpose_out, accumulate, segs, n_segs, first stage not launched yet?, u, y, Bt, upart]
-    upart = None
-    if u_from is not None:
-        assert not defer and u_from.dtype is BF16 and u_from.dim() == 2 and u_from.shape == (R, N) and u_from.stride(1) == 1
-        upart = torch.empty(_lib().llx_skinny_u_workspace_bytes(M, N) // 4, device=y.device, dtype=torch.float32)
-    if scaled is not None:
-        assert u_from is not None and scaled[0].dtype is BF16 and scaled[0].numel() == N and scaled[1].shape == (M, N) and scaled[1].stride(1) == 1
-    pending.append([ws, out, out_ld, M, N, R, scale_, int(transpose_out), int(accumulate), sp, ns, True, u, y, u_from, upart, scaled])
-    if not defer:
-        skinny_tn_partials(pending)
+    q = TnQueued(ws, out, out_ld, M, N, R, scale_, int(transpose_out), int(accumulate), sp, ns)
+    if u_from is None:
+        assert scaled is None
+        L.check(_lib().llx_skinny_tn_partial(L.ptr(u), L.ptr(y), y.stride(0), M, N, R, L.ptr(ws), sp, ns, L.stream()), "llx_skinny_tn_partial")
+    else:
+        assert u_from.dtype is BF16 and u_from.dim() == 2 and u_from.shape == (R, N) and u_from.stride(1) == 1
+        q.upart = torch.empty(_lib().llx_skinny_u_workspace_bytes(M, N) // 4, device=y.device, dtype=torch.float32)
+        cs = g = None
+        if scaled is not None:
+            cs, g = scaled
+            assert cs.dtype is BF16 and cs.numel() == N and g.shape == (M, N) and g.stride(1) == 1
+        one = lambda ctype, v: (ctype * 1)(v)  # the entry point takes arrays: up to 4 products per launch
+        ptr = lambda t: one(ctypes.c_void_p, t.data_ptr() if t is not None else None)
+        L.check(_lib().llx_skinny_tn_partial_many_us(1, ptr(u), ptr(y), one(ctypes.c_int64, y.stride(0)), one(ctypes.c_int64, M), one(ctypes.c_int64, N),
+                                                     one(ctypes.c_int64, R), ptr(ws), one(ctypes.c_void_p, ctypes.cast(sp, ctypes.c_void_p).value if sp is not None else None),
+                                                     one(ctypes.c_int, ns), ptr(u_from), one(ctypes.c_int64, u_from.stride(0)), ptr(q.upart), ptr(cs), ptr(g),
+                                                     one(ctypes.c_int64, g.stride(0) if g is not None else 0), L.stream()), "llx_skinny_tn_partial_many")
+    pending.append(q)
     if len(pending) == 4:
         skinny_tn_flush(pending)
     return out
 
 
-def skinny_tn_partials(pending: list) -> None:
-    """First stage (fp32 split partials) of every queued product that has not had it yet, in ONE launch (up to 4 products): the dB and
-    dA products of a linear group are queued with defer=True and launched together."""
-    todo = [c for c in pending if c[11]]
-    while todo:
-        chunk, todo = todo[:4], todo[4:]
-        n = len(chunk)
-        if n == 1 and chunk[0][15] is None:
-            c = chunk[0]
-            L.check(_lib().llx_skinny_tn_partial(L.ptr(c[12]), L.ptr(c[13]), c[13].stride(0), c[3], c[4], c[5], L.ptr(c[0]), c[9], c[10], L.stream()),
-                    "llx_skinny_tn_partial")
-        else:
-            UU = (ctypes.c_void_p * n)(*[c[12].data_ptr() for c in chunk])
-            YY = (ctypes.c_void_p * n)(*[c[13].data_ptr() for c in chunk])
-            LY = (ctypes.c_int64 * n)(*[c[13].stride(0) for c in chunk])
-            MM = (ctypes.c_int64 * n)(*[c[3] for c in chunk])
-            NN = (ctypes.c_int64 * n)(*[c[4] for c in chunk])
-            RR = (ctypes.c_int64 * n)(*[c[5] for c in chunk])
-            WS = (ctypes.c_void_p * n)(*[c[0].data_ptr() for c in chunk])
-            SG = (ctypes.c_void_p * n)(*[ctypes.cast(c[9], ctypes.c_void_p).value if c[9] is not None else None for c in chunk])
-            NS = (ctypes.c_int * n)(*[c[10] for c in chunk])
-            BT = (ctypes.c_void_p * n)(*[(c[14].data_ptr() if c[15] is not None else None) for c in chunk])
-            LB = (ctypes.c_int64 * n)(*[(c[14].stride(0) if c[15] is not None else 0) for c in chunk])
-            UP = (ctypes.c_void_p * n)(*[(c[15].data_ptr() if c[15] is not None else None) for c in chunk])
-            CS = (ctypes.c_void_p * n)(*[(c[16][0].data_ptr() if c[16] is not None else None) for c in chunk])
-            GG = (ctypes.c_void_p * n)(*[(c[16][1].data_ptr() if c[16] is not None else None) for c in chunk])
-            LG = (ctypes.c_int64 * n)(*[(c[16][1].stride(0) if c[16] is not None else 0) for c in chunk])
-            L.check(_lib().llx_skinny_tn_partial_many_us(n, UU, YY, LY, MM, NN, RR, WS, SG, NS, BT, LB, UP, CS, GG, LG, L.stream()), "llx_skinny_tn_partial_many")
-        for c in chunk:
-            c[11] = False
-            c[12] = c[13] = None  # the operands are not needed past the first stage
-
-
-def skinny_u_reduce(entry: list) -> Tensor:
-    """u [M, 64] bf16 (= y @ Bt^T, columns >= R zero) from the column-tile partials the first stage of `entry` (a pending item queued with
+def skinny_u_reduce(q: TnQueued) -> Tensor:
+    """u [M, 64] bf16 (= y @ Bt^T, columns >= R zero) from the column-tile partials the first stage of `q` (a pending item queued with
     u_from) has written; call it right after that skinny_tn (the partial workspace is reused by the next product of the same parity)."""
-    assert entry[15] is not None and not entry[11], "the product's first stage must have run with u_from"
-    M, N, R = entry[3], entry[4], entry[5]
-    out = torch.empty(M, SK_PAD, device=entry[15].device, dtype=BF16)
-    L.check(_lib().llx_skinny_u_reduce(L.ptr(entry[15]), L.ptr(out), M, N, R, entry[9], entry[10], L.stream()), "llx_skinny_u_reduce")
+    assert q.upart is not None, "the product must have been queued with u_from"
+    out = torch.empty(q.M, SK_PAD, device=q.upart.device, dtype=BF16)
+    L.check(_lib().llx_skinny_u_reduce(L.ptr(q.upart), L.ptr(out), q.M, q.N, q.R, q.segs, q.n_segs, L.stream()), "llx_skinny_u_reduce")
     return out
 
 
 def skinny_tn_flush(pending: list) -> None:
     """Second stage of every product queued by skinny_tn(..., pending=...) in one launch (at most 4 per launch)."""
-    skinny_tn_partials(pending)
     while pending:
         chunk, pending[:] = pending[:4], pending[4:]
         n = len(chunk)
-        WS = (ctypes.c_void_p * n)(*[c[0].data_ptr() for c in chunk])
-        OUT = (ctypes.c_void_p * n)(*[c[1].data_ptr() for c in chunk])
-        LD = (ctypes.c_int64 * n)(*[c[2] for c in chunk])
-        MM = (ctypes.c_int64 * n)(*[c[3] for c in chunk])
-        NN = (ctypes.c_int64 * n)(*[c[4] for c in chunk])
-        RR = (ctypes.c_int64 * n)(*[c[5] for c in chunk])
-        SC = (ctypes.c_float * n)(*[c[6] for c in chunk])
-        TR = (ctypes.c_int * n)(*[c[7] for c in chunk])
-        AC = (ctypes.c_int * n)(*[c[8] for c in chunk])
-        SG = (ctypes.c_void_p * n)(*[ctypes.cast(c[9], ctypes.c_void_p).value if c[9] is not None else None for c in chunk])
-        NS = (ctypes.c_int * n)(*[c[10] for c in chunk])
+        WS = (ctypes.c_void_p * n)(*[q.ws.data_ptr() for q in chunk])
+        OUT = (ctypes.c_void_p * n)(*[q.out.data_ptr() for q in chunk])
+        LD = (ctypes.c_int64 * n)(*[q.out_ld for q in chunk])
+        MM = (ctypes.c_int64 * n)(*[q.M for q in chunk])
+        NN = (ctypes.c_int64 * n)(*[q.N for q in chunk])
+        RR = (ctypes.c_int64 * n)(*[q.R for q in chunk])
+        SC = (ctypes.c_float * n)(*[q.scale for q in chunk])
+        TR = (ctypes.c_int * n)(*[q.transpose_out for q in chunk])
+        AC = (ctypes.c_int * n)(*[q.accumulate for q in chunk])
+        SG = (ctypes.c_void_p * n)(*[ctypes.cast(q.segs, ctypes.c_void_p).value if q.segs is not None else None for q in chunk])
+        NS = (ctypes.c_int * n)(*[q.n_segs for q in chunk])
         L.check(_lib().llx_skinny_tn_reduce_many(n, WS, OUT, LD, MM, NN, RR, SC, TR, AC, SG, NS, L.stream()), "llx_skinny_tn_reduce_many")

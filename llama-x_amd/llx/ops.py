@@ -27,16 +27,21 @@ BF16 = torch.bfloat16
 # =================================================================================================
 # cached derived images of (mostly frozen) weights
 # =================================================================================================
-def _cached(t: Tensor, tag: str, build):
-    """Cache ``build()`` on the tensor object, keyed by its version counter (in-place updates invalidate)."""
-    store = t.__dict__.setdefault("_llx_cache", {})
-    ver = t._version
+def _cached_multi(tensors: Sequence[Tensor], tag: str, build):
+    """Cache ``build()`` (any value) on the first tensor, keyed by the version counters and devices of all of them: an in-place update
+    or a move of any source invalidates."""
+    store = tensors[0].__dict__.setdefault("_llx_cache", {})
+    key = tuple((t._version, str(t.device)) for t in tensors)
     hit = store.get(tag)
-    if hit is not None and hit[0] == ver and hit[1].device == t.device:
+    if hit is not None and hit[0] == key:
         return hit[1]
     val = build()
-    store[tag] = (ver, val)
+    store[tag] = (key, val)
     return val
+
+
+def _cached(t: Tensor, tag: str, build):
+    return _cached_multi([t], tag, build)
 
 
 def weight_t(w: Tensor) -> Tensor:
@@ -205,18 +210,6 @@ def dora_colscale(members: Sequence[LinearPlan], w_cat: Tensor, a_cat: Tensor, b
     return c, inv
 
 
-def _cached_multi(tensors: Sequence[Tensor], tag: str, build):
-    """Cache on the first tensor, keyed by the version counters (and devices) of all of them."""
-    store = tensors[0].__dict__.setdefault("_llx_cache", {})
-    key = tuple((t._version, str(t.device)) for t in tensors)
-    hit = store.get(tag)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    val = build()
-    store[tag] = (key, val)
-    return val
-
-
 class GroupPlan:
     """Linears that read the SAME input (wq|wk|wv, w1|w3), executed as one GEMM over concatenated weight images.
 
@@ -284,7 +277,7 @@ class GroupPlan:
 
     def norm_can_make_t(self, dim: int) -> bool:
         """The preceding RMSNorm can emit t = xn @ A_cat^T itself: the operand images exist already (prepack) and the width fits."""
-        return self.fused and self.R > 0 and self.packed is not None and K.rmsnorm_skinny_ok(dim) and _FUSE_NORM_SKINNY
+        return self.fused and self.R > 0 and self.packed is not None and K.rmsnorm_skinny_ok(dim)
 
     def wants_quantized_input(self) -> bool:
         """The fused group runs torchao::int8_mm_dequant on row-wise quantised activations (subclasses/int8.py:110-113)."""
@@ -382,8 +375,9 @@ class GroupPlan:
                  swiglu: Optional[tuple[Tensor, Tensor]] = None, pending: Optional[list] = None):
         """swiglu = (gate|up activations [M, 2K], dg|du output [M, 2K]): the data gradient of this linear is the gradient of
         silu(g)*u, and the dgrad GEMM applies the SwiGLU backward in its epilogue (returns the dg|du tensor instead of dx).
-        pending: the second stage of the adapter-gradient products is queued there instead of launched (K.skinny_tn_flush: the block's
-        backward runs the second stages of its two groups - four products - in one launch before it returns the gradients)."""
+        pending (a list; a fused group needs it): the second stage of the adapter-gradient products is queued there instead of launched
+        (K.skinny_tn_flush: the block's backward runs the second stages of its two groups - four products - in one launch before it
+        returns the gradients)."""
         if not self.fused:
             grads, dx, first = [], None, True
             ni = 0
@@ -410,7 +404,6 @@ class GroupPlan:
         else:
             t, bT, a2t = saved if saved is not None else (None, None, None)
         u = gA = gBt = g_scaled = None
-        fused_u_here = False
         gB_views: Optional[list[Optional[Tensor]]] = None
         need_a, need_b = self.R > 0 and any(nd[ia] for nd in need), self.R > 0 and any(nd[ia + 1] for nd in need)
         # (issuing the dB chain, the dA chain or both on a side stream - parallel branches of the replayed hipGraph - was measured three
@@ -424,19 +417,14 @@ class GroupPlan:
                 flat = _grad_dst([m.lora_b for m in self.members if m.rank > 0])  # the arena keeps a group's B factors back to back
                 if flat is None:
                     flat = torch.empty(sum((b - a) * (d - c_) for a, b, c_, d in segs), device=dy.device, dtype=BF16)
-                fuse_u = _FUSE_U and pending is not None and tuple(bT.shape) == (self.R, self.N)
-                if fuse_u:
-                    # dB's first stage also emits u = dy @ B from the dy tiles it stages (dy read once instead of twice) - and, for an
-                    # int8 base, (dy * scale), the operand of its data gradient (subclasses/int8.py:127)
-                    sc = None
-                    if self.int8 and need_dx and _FUSE_DY_SCALE:
-                        g_scaled = torch.empty_like(dy)
-                        sc = (self.scale_cat(), g_scaled)
-                    K.skinny_tn(t, dy, self.R, self.scale, flat, transpose_out=True, segs=segs, pending=pending, u_from=bT, scaled=sc)
-                    u = K.skinny_u_reduce(pending[-1])
-                    fused_u_here = True
-                else:
-                    K.skinny_tn(t, dy, self.R, self.scale, flat, transpose_out=True, segs=segs, pending=pending, defer=need_a and _BATCH_TN_PARTIAL)
+                # dB's first stage also emits u = dy @ B from the dy tiles it stages (dy read once instead of twice) - and, for an
+                # int8 base, (dy * scale), the operand of its data gradient (subclasses/int8.py:127)
+                sc = None
+                if self.int8 and need_dx:
+                    g_scaled = torch.empty_like(dy)
+                    sc = (self.scale_cat(), g_scaled)
+                K.skinny_tn(t, dy, self.R, self.scale, flat, transpose_out=True, segs=segs, pending=pending, u_from=bT, scaled=sc)
+                u = K.skinny_u_reduce(pending[-1])
                 gB_views, off = [], 0
                 for m_, (a, b, c_, d) in zip([m for m in self.members if m.rank > 0], segs):
                     gB_views.append(flat[off : off + (b - a) * (d - c_)].view(b - a, d - c_))
@@ -444,10 +432,10 @@ class GroupPlan:
             else:
                 gBt = torch.empty(self.N, self.R, device=dy.device, dtype=BF16)
                 K.skinny_tn(t, dy, self.R, self.scale, gBt, transpose_out=True)  # (sliced below: needs the finished product)
-        if self.R > 0:  # u = dy.B, then dA = s u^T.x
+        if self.R > 0:  # u = dy.B (unless it came out of the dB pass above), then dA = s u^T.x
             if u is not None:
-                pass  # came out of the dB pass above
-            elif self.int8 and need_dx and _FUSE_DY_SCALE:
+                pass
+            elif self.int8 and need_dx:
                 # ... and (dy * scale), the int8 base's data-gradient operand (subclasses/int8.py:127), from the same read of dy
                 u, g_scaled = K.skinny_nt(dy, bT, self._kranges(), colscale=self.scale_cat())
             else:
@@ -456,9 +444,9 @@ class GroupPlan:
                 gA = _grad_dst([m.lora_a for m in self.members if m.rank > 0], (self.R, self.K))  # ... and its A factors
                 if gA is None:
                     gA = torch.empty(self.R, self.K, device=dy.device, dtype=BF16)
-                # (with the fused u the dB stage has run already and dA's first stage launches on its own: batched with the NEXT group's
-                # dB + u stage it made one long launch of unequal blocks - 105 us where the two take 25 + 39)
-                K.skinny_tn(u, x, self.R, self.scale, gA, transpose_out=False, pending=pending)  # otherwise: launches the deferred dB stage with its own
+                # (dA's first stage launches on its own: batched with the NEXT group's dB + u stage it made one long launch of unequal
+                # blocks - 105 us where the two take 25 + 39)
+                K.skinny_tn(u, x, self.R, self.scale, gA, transpose_out=False, pending=pending)
         dx = None
         if need_dx:
             if self.int8:
@@ -560,6 +548,33 @@ def prepack(plans: Sequence[GroupPlan]) -> None:
             p.packed = im
 
 
+def _norm_prologue(meta, plan: GroupPlan, x2: Tensor, norm_w: Optional[Tensor]):
+    """xn = [rmsnorm(x2)] for the linear group that reads it -> (xn, rstd, xq, t_pre).  The norm kernel also emits what the group would
+    otherwise make from xn in a pass of its own: xq = quantize_int8_rowwise(xn) for dynamically quantised int8 members, or t_pre = the
+    adapters' xn @ A_cat^T."""
+    if not meta.fuse_norm:
+        return x2, None, None, None
+    if plan.wants_quantized_input():
+        xn, rstd, *xq = K.rmsnorm_fwd(x2, norm_w.detach(), meta.eps, quant=True)
+        return xn, rstd, xq, None
+    if plan.norm_can_make_t(x2.shape[1]):
+        xn, rstd, t_pre = K.rmsnorm_skinny_nt(x2, norm_w.detach(), meta.eps, plan.packed[0])
+        return xn, rstd, None, t_pre
+    xn, rstd = K.rmsnorm_fwd(x2, norm_w.detach(), meta.eps)
+    return xn, rstd, None, None
+
+
+def _norm_epilogue(dxn: Optional[Tensor], x2: Tensor, norm_w: Optional[Tensor], rstd: Optional[Tensor], need_dnw: bool,
+                   dres: Optional[Tensor] = None, fuse_norm: bool = True):
+    """Backward of xn = [rmsnorm(x)] -> (dx, d norm_w): d(xn) goes through the norm's backward, which joins dres - the gradient that came
+    around the residual connection - in the same pass (without a fused norm: one add).  (None, None) when nothing wanted d(xn)."""
+    if dxn is None:
+        return None, None
+    if fuse_norm:
+        return K.rmsnorm_bwd(dxn, x2, norm_w.detach(), rstd, need_dnw, dres, dw_out=_grad_dst([norm_w]))
+    return (K.add(dxn, dres) if dres is not None else dxn), None
+
+
 def _plans_tensors(plans: Sequence[LinearPlan]) -> tuple[list[Tensor], list[int]]:
     ts, counts = [], []
     for p in plans:
@@ -637,18 +652,10 @@ class AttnBlockFn(Function):
         B, S, D = x.shape
         H, KVH, hd = meta.H, meta.KVH, meta.hd
         x2 = K._rows2d(x.contiguous())
-        xq = t_pre = None
-        if meta.fuse_norm and meta.qkv.wants_quantized_input() and _FUSE_NORM_QUANT:
-            xn, rstd, *xq = K.rmsnorm_fwd(x2, norm_w.detach(), meta.eps, quant=True)  # the norm also emits quantize_int8_rowwise(xn)
-        elif meta.fuse_norm and meta.qkv.norm_can_make_t(D):
-            xn, rstd, t_pre = K.rmsnorm_skinny_nt(x2, norm_w.detach(), meta.eps, meta.qkv.packed[0])  # ... or the adapters' xn @ A_cat^T
-        elif meta.fuse_norm:
-            xn, rstd = K.rmsnorm_fwd(x2, norm_w.detach(), meta.eps)
-        else:
-            xn, rstd = x2, None
+        xn, rstd, xq, t_pre = _norm_prologue(meta, meta.qkv, x2, norm_w)
         W = (H + 2 * KVH) * hd
         qkv = torch.empty(B * S, W, device=x.device, dtype=BF16)
-        fuse_rope = meta.qkv.rope_fusable() and _FUSE_ROPE
+        fuse_rope = meta.qkv.rope_fusable()
         _, tqkv = meta.qkv.forward(xn, qkv, rope=(rope, S, (H + KVH) * hd) if fuse_rope else None, xq=xq, t_pre=t_pre)
         qkv3 = qkv.view(B, S, W)
         if not fuse_rope:
@@ -676,7 +683,7 @@ class AttnBlockFn(Function):
         needs = list(ctx.needs_input_grad[4:])
         n_qkv = len(meta.qkv.tensors())
         nqkv, no = needs[:n_qkv], needs[n_qkv:]
-        pend = [] if _BATCH_TN_REDUCE else None  # second stages of the four adapter-gradient products of this block: one launch at the end
+        pend = []  # second stages of the four adapter-gradient products of this block: one launch at the end
         # wo
         do2, g_o = meta.wo.backward(dy2, o.view(B * S, H * hd), to, no, True, pending=pend)
         # attention
@@ -688,39 +695,21 @@ class AttnBlockFn(Function):
         dq = dqkv[..., : H * hd].unflatten(-1, (H, hd))
         dk = dqkv[..., H * hd : (H + KVH) * hd].unflatten(-1, (KVH, hd))
         dv = dqkv[..., (H + KVH) * hd :].unflatten(-1, (KVH, hd))
-        if _FUSE_ROPE:  # apply_rope's transpose rides in the dQ epilogue and the dK/dV reduce
-            K.attn_bwd(q, k, v, o, do2.view(B, S, H, hd), lse, dq, dk, dv, meta.mask, rope=rope)
-        else:
-            K.attn_bwd(q, k, v, o, do2.view(B, S, H, hd), lse, dq, dk, dv, meta.mask)
-            K.rope_(dqkv, rope, H + KVH, backward=True)
+        # apply_rope's transpose rides in the dQ epilogue and the dK/dV reduce
+        K.attn_bwd(q, k, v, o, do2.view(B, S, H, hd), lse, dq, dk, dv, meta.mask, rope=rope)
         d2 = dqkv.view(B * S, W)
         need_dx = ctx.needs_input_grad[0]
         need_dxn = need_dx or (meta.fuse_norm and ctx.needs_input_grad[2])  # the norm weight gradient needs d(xn) too
         dxn = torch.empty(B * S, D, device=x.device, dtype=BF16) if need_dxn else None
         _, g_qkv = meta.qkv.backward(d2, xn, tqkv, nqkv, need_dxn, dxn, pending=pend)
-        if pend:
-            K.skinny_tn_flush(pend)
-        dx = dnw = None
-        if meta.fuse_norm:
-            if need_dxn:
-                dx, dnw = K.rmsnorm_bwd(dxn, x2, norm_w.detach(), rstd, ctx.needs_input_grad[2], dy2 if (need_dx and meta.fuse_residual) else None,
-                                            dw_out=_grad_dst([norm_w]))
-        else:
-            dx = dxn
-            if need_dx and meta.fuse_residual:
-                dx = K.add(dx, dy2)
+        K.skinny_tn_flush(pend)
+        dx, dnw = _norm_epilogue(dxn, x2, norm_w, rstd, ctx.needs_input_grad[2], dy2 if (need_dx and meta.fuse_residual) else None, meta.fuse_norm)
         return (dx.view(B, S, D) if (dx is not None and need_dx) else None, None, dnw, None, *g_qkv, *g_o)
 
 
 # =================================================================================================
 # MLP residual branch:  [x +] w2( silu(w1 xn) * w3 xn ),  xn = [rmsnorm(x)]
 # =================================================================================================
-_FUSE_SWIGLU_FWD = os.environ.get("LLX_FUSE_SWIGLU_FWD", "1") != "0"  # A/B knob: 0 = stand-alone swiglu_fwd kernel
-_BATCH_TN_REDUCE = os.environ.get("LLX_BATCH_TN_REDUCE", "1") != "0"  # A/B knob: 0 = every adapter-gradient product reduces its partials at once
-_FUSE_NORM_SKINNY = os.environ.get("LLX_FUSE_NORM_SKINNY", "1") != "0"  # A/B knob: 0 = RMSNorm, then the stand-alone skinny product
-_FUSE_DY_SCALE = os.environ.get("LLX_FUSE_DY_SCALE", "1") != "0"  # A/B knob: 0 = stand-alone dy * scale pass for an int8 base's data gradient
-_FUSE_U = os.environ.get("LLX_FUSE_U", "1") != "0"  # A/B knob: 0 = u = dy @ B as its own pass over dy (skinny_nt) instead of riding in dB's first stage
-_BATCH_TN_PARTIAL = os.environ.get("LLX_BATCH_TN_PARTIAL", "1") != "0"  # A/B knob: 0 = dB's first stage launched on its own, before u
 _HEAD_COMPACT = os.environ.get("LLX_HEAD_COMPACT", "1") != "0"  # LM head + loss over the labelled rows only (HeadLossFn)
 # K ranges of the head's d-hidden GEMM (1 = unsplit).  The row count is only known on the device, so the split is static: with 4 ranges
 # a round of 256 tiles lasts a quarter of the unsplit tile time, i.e. the time follows the labelled-row count in steps of 1/4 round
@@ -728,8 +717,6 @@ _HEAD_COMPACT = os.environ.get("LLX_HEAD_COMPACT", "1") != "0"  # LM head + loss
 _HEAD_SPLITK = max(1, int(os.environ.get("LLX_HEAD_SPLITK", "4")))
 _HEAD_CHUNK_FORCED = "LLX_HEAD_CHUNK_ROWS" in os.environ
 _HEAD_CHUNK_ROWS = max(256, int(os.environ.get("LLX_HEAD_CHUNK_ROWS", "8192")) // 256 * 256)  # rows per logits buffer of the chunked head
-_FUSE_NORM_QUANT = os.environ.get("LLX_FUSE_NORM_QUANT", "1") != "0"  # A/B knob: 0 = stand-alone activation quantiser after the RMSNorm
-_FUSE_ROPE = os.environ.get("LLX_FUSE_ROPE", "1") != "0"  # A/B knob: 0 = stand-alone rope kernel after the projection / before its dgrad
 
 
 class MLPBlockMeta:
@@ -744,18 +731,10 @@ class MLPBlockFn(Function):
         K.L.require_cuda(x)
         shape = x.shape
         x2 = K._rows2d(x.contiguous())
-        xq = t_pre = None
-        if meta.fuse_norm and meta.w13.wants_quantized_input() and _FUSE_NORM_QUANT:
-            xn, rstd, *xq = K.rmsnorm_fwd(x2, norm_w.detach(), meta.eps, quant=True)  # the norm also emits quantize_int8_rowwise(xn)
-        elif meta.fuse_norm and meta.w13.norm_can_make_t(x2.shape[1]):
-            xn, rstd, t_pre = K.rmsnorm_skinny_nt(x2, norm_w.detach(), meta.eps, meta.w13.packed[0])  # ... or the adapters' xn @ A_cat^T
-        elif meta.fuse_norm:
-            xn, rstd = K.rmsnorm_fwd(x2, norm_w.detach(), meta.eps)
-        else:
-            xn, rstd = x2, None
+        xn, rstd, xq, t_pre = _norm_prologue(meta, meta.w13, x2, norm_w)
         T, I = x2.shape[0], meta.w13.Ns[0]
         gu = torch.empty(T, 2 * I, device=x.device, dtype=BF16)
-        if meta.w13.swiglu_fusable() and _FUSE_SWIGLU_FWD:
+        if meta.w13.swiglu_fusable():
             h = torch.empty(T, I, device=x.device, dtype=BF16)
             _, t13 = meta.w13.forward(xn, gu, swiglu_h=h, xq=xq, t_pre=t_pre)  # SwiGLU in the epilogue of the gate|up GEMM
         else:
@@ -778,7 +757,7 @@ class MLPBlockFn(Function):
         n_13 = len(meta.w13.tensors())
         n13, n2 = needs[:n_13], needs[n_13:]
         dgu = torch.empty(T, 2 * I, device=x.device, dtype=BF16)
-        pend = [] if _BATCH_TN_REDUCE else None  # second stages of the four adapter-gradient products of this block: one launch at the end
+        pend = []  # second stages of the four adapter-gradient products of this block: one launch at the end
         if meta.w2.fused:  # dh = dy.W2 (+LoRA) never reaches HBM: the dgrad GEMM's epilogue turns it into dg | du
             _, g_2 = meta.w2.backward(dy2, h, t2, n2, True, swiglu=(gu, dgu), pending=pend)
         else:
@@ -788,17 +767,8 @@ class MLPBlockFn(Function):
         need_dxn = need_dx or (meta.fuse_norm and ctx.needs_input_grad[1])
         dxn = torch.empty_like(x2) if need_dxn else None
         _, g_13 = meta.w13.backward(dgu, xn, t13, n13, need_dxn, dxn, pending=pend)
-        if pend:
-            K.skinny_tn_flush(pend)
-        dx = dnw = None
-        if meta.fuse_norm:
-            if need_dxn:
-                dx, dnw = K.rmsnorm_bwd(dxn, x2, norm_w.detach(), rstd, ctx.needs_input_grad[1], dy2 if (need_dx and meta.fuse_residual) else None,
-                                            dw_out=_grad_dst([norm_w]))
-        else:
-            dx = dxn
-            if need_dx and meta.fuse_residual:
-                dx = K.add(dx, dy2)
+        K.skinny_tn_flush(pend)
+        dx, dnw = _norm_epilogue(dxn, x2, norm_w, rstd, ctx.needs_input_grad[1], dy2 if (need_dx and meta.fuse_residual) else None, meta.fuse_norm)
         return (dx.view(x.shape) if (dx is not None and need_dx) else None, dnw, None, *g_13, *g_2)
 
 
@@ -895,7 +865,7 @@ class HeadLossFn(Function):
                         part = K.gemm_nt_splitk(dl, wt, _HEAD_SPLITK, m_valid=cnt_c) if split else K.gemm_nt(dl, wt, m_valid=cnt_c)
                         dxc[r0 : r0 + dl.shape[0]].copy_(part)
                     dxn = K.scatter_rows(dxc, inv, g32) if inv is not None else K.scale(dxc, dev_scalar=g32)
-                    dx, dnw = K.rmsnorm_bwd(dxn, x2, norm_w.detach(), rstd, ctx.needs_input_grad[1], dw_out=_grad_dst([norm_w]))
+                    dx, dnw = _norm_epilogue(dxn, x2, norm_w, rstd, ctx.needs_input_grad[1])
                 return (dx.view(x.shape) if dx is not None else None, dnw, None, None, None, *([None] * len(needs)))
             inv, cnt = t if ctx.compact else (None, None)
             dx = dnw = None
@@ -907,15 +877,14 @@ class HeadLossFn(Function):
                     dxn = K.scatter_rows(K.gemm_nt(dlogits, wt, m_valid=cnt, m_expect=ctx.m_expect), inv, g32)
                 else:
                     dxn = K.scale(K.gemm_nt(dlogits, wt), dev_scalar=g32)
-                dx, dnw = K.rmsnorm_bwd(dxn, x2, norm_w.detach(), rstd, ctx.needs_input_grad[1], dw_out=_grad_dst([norm_w]))
+                dx, dnw = _norm_epilogue(dxn, x2, norm_w, rstd, ctx.needs_input_grad[1])
             gw = None
             if ctx.plain_trainable:  # dW over the labelled rows (xn holds their gathered, normed activations), scaled by the incoming gradient
                 gw = K.scale(K.gemm_tn(dlogits, xn, m_valid=cnt, m_expect=ctx.m_expect), dev_scalar=g32)
             return (dx.view(x.shape) if dx is not None else None, dnw, None, None, None, *([gw] + [None] * (len(needs) - 1) if needs else []))
         dxn, grads = plan.backward(dlogits, xn, t, needs, need_dx=ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
         grads = [None if g is None else K.scale(g, dev_scalar=g32) for g in grads]
-        dx = dnw = None
         if dxn is not None:
             K.scale(dxn, dev_scalar=g32, out=dxn)
-            dx, dnw = K.rmsnorm_bwd(dxn, x2, norm_w.detach(), rstd, ctx.needs_input_grad[1], dw_out=_grad_dst([norm_w]))
+        dx, dnw = _norm_epilogue(dxn, x2, norm_w, rstd, ctx.needs_input_grad[1])
         return (dx.view(x.shape) if dx is not None else None, dnw, None, None, None, *grads)

@@ -401,3 +401,33 @@ def test_group_plan_block_diagonal_descriptors():
     assert g._kranges() is None and g._tn_segs() == [(0, 4096, 0, 16)]
     g = group((200, 312), 16)  # boundary not a multiple of 64: dense
     assert g._kranges() is None and g._tn_segs() is None
+
+
+def test_cached_is_keyed_by_version_and_device_of_every_source():
+    """llx.ops._cached / _cached_multi: miss, hit (build not called again), rebuild after an in-place update of a source tensor, and a
+    value without a ``.device`` (the tuple modelling/llama.py caches for a dense mask) surviving a second look-up."""
+    from llx.ops import _cached, _cached_multi
+
+    calls = []
+
+    def build(v):
+        def f():
+            calls.append(v)
+            return v
+        return f
+
+    a, b = torch.zeros(4), torch.zeros(4)
+    assert _cached(a, "x", build("first")) == "first" and calls == ["first"]            # miss
+    assert _cached(a, "x", build("second")) == "first" and calls == ["first"]           # hit: build not called
+    assert _cached(a, "y", build("other tag")) == "other tag" and len(calls) == 2       # tags do not share an entry
+    a.add_(1)
+    assert _cached(a, "x", build("third")) == "third" and calls[-1] == "third"          # in-place update: rebuilt
+    assert _cached(a, "x", build("fourth")) == "third"
+    spec = (None,)                                                                       # a non-tensor value, hit twice
+    assert _cached(b, "maskspec", lambda: spec) is spec
+    assert _cached(b, "maskspec", build("never")) is spec and _cached(b, "maskspec", build("never")) is spec and "never" not in calls
+    # several sources: an update of ANY of them invalidates; the entry lives on the first
+    n = len(calls)
+    assert _cached_multi([a, b], "cat", build("ab")) == "ab" and _cached_multi([a, b], "cat", build("ab2")) == "ab" and len(calls) == n + 1
+    b.mul_(2)
+    assert _cached_multi([a, b], "cat", build("ab3")) == "ab3" and _cached_multi([a, b], "cat", build("ab4")) == "ab3"

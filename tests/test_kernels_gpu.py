@@ -1058,8 +1058,9 @@ def test_gemm_splitk(K, cuda, M, N, Kd, splits, rows):
 
 
 def test_skinny_tn_batched_stages(K, cuda):
-    """Products queued with pending / defer: the first stages of several products run as ONE launch (llx_skinny_tn_partial_many, products
-    with 1, 2, 3 row blocks and a segmented one side by side), the second stages as one more - bit-identical to the stand-alone calls."""
+    """Products queued with pending: every product launches its first stage at once, the second stages of up to four products (with 1, 2,
+    3 row blocks and a segmented one side by side) run as ONE launch - bit-identical to the stand-alone calls.  (The deferred first
+    stages this test also covered went with the `defer` parameter: nothing in llx/ops.py could reach them any more.)"""
     M = 1000
     specs = [(768, 16, False, None), (1280, 32, True, None), (512, 48, False, None), (1024, 24, True, [(0, 512, 0, 8), (512, 1024, 8, 24)])]
     args, want = [], []
@@ -1072,25 +1073,22 @@ def test_skinny_tn_batched_stages(K, cuda):
         K.skinny_tn(u.to(cuda), y.to(cuda), R, 0.25, ref, tr, segs=segs)
         args.append((u.to(cuda), y.to(cuda), R, tr, segs, shape))
         want.append(ref)
-    for defer in (True, False):
-        pend, outs = [], []
-        for u, y, R, tr, segs, shape in args:
-            out = torch.full(shape, float("nan"), device=cuda, dtype=torch.bfloat16)
-            K.skinny_tn(u, y, R, 0.25, out, tr, segs=segs, pending=pend, defer=defer)
-            outs.append(out)
-        assert not pend  # the fourth product triggers the flush (first stages together when deferred, then the second stages)
-        for o, w in zip(outs, want):
-            assert torch.equal(o, w)
-    # two deferred products, launched explicitly, flushed later
+    pend, outs = [], []
+    for u, y, R, tr, segs, shape in args:
+        out = torch.full(shape, float("nan"), device=cuda, dtype=torch.bfloat16)
+        K.skinny_tn(u, y, R, 0.25, out, tr, segs=segs, pending=pend)
+        outs.append(out)
+    assert not pend  # the fourth product triggers the flush (the second stages)
+    for o, w in zip(outs, want):
+        assert torch.equal(o, w)
+    # two products, flushed later
     pend = []
     outs = [torch.empty(s[5], device=cuda, dtype=torch.bfloat16) for s in args[:2]]
     for (u, y, R, tr, segs, _), out in zip(args[:2], outs):
-        K.skinny_tn(u, y, R, 0.25, out, tr, segs=segs, pending=pend, defer=True)
-    assert all(c[11] for c in pend)
-    K.skinny_tn_partials(pend)
-    assert not any(c[11] for c in pend) and len(pend) == 2
+        K.skinny_tn(u, y, R, 0.25, out, tr, segs=segs, pending=pend)
+    assert len(pend) == 2
     K.skinny_tn_flush(pend)
-    assert torch.equal(outs[0], want[0]) and torch.equal(outs[1], want[1])
+    assert not pend and torch.equal(outs[0], want[0]) and torch.equal(outs[1], want[1])
 
 
 @pytest.mark.parametrize("M,Kd,R,ranged", [(1000, 4096 + 2048, 16, False), (515, 2048 + 96, 48, False), (777, 4096, 32, True)])
