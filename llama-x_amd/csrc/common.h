@@ -182,3 +182,17 @@ __device__ __forceinline__ bf16x8_t frag_of(const s16x4_t& lo, const s16x4_t& hi
   const llx_s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   return __builtin_bit_cast(bf16x8_t, v);
 }
+
+// ---- LDS-DMA (16 B per lane) through a buffer descriptor.  hipcc never selects the scalar-base form of global_load_lds: even
+// `uniform base + zext(32-bit lane offset)` becomes a 64-bit vector add (v_lshl_add_u64) in front of every piece and the lane
+// offsets live as 64-bit pairs.  The buffer form takes the address in three parts - descriptor (4 SGPRs, wave-uniform base and
+// byte extent), a 32-bit per-lane offset, a scalar offset - so a loop that only advances the scalar part has no vector address
+// arithmetic at all.  `bytes` = the operand's real extent: lanes at or beyond it read zeros and cannot fault.  The instruction's own
+// immediate offset (12 bits) stays 0: a larger constant is dropped without a diagnostic.
+typedef __attribute__((address_space(3))) void llx_lds_void;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t lds_dma_rsrc(const void* base, uint32_t bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);  // raw buffer, 32-bit data format
+}
+__device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t rsrc, llx_lds_void* dst, uint32_t lane_off, uint32_t wave_off) {
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, dst, 16, (int)lane_off, (int)wave_off, 0, 0);
+}

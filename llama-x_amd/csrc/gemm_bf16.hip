@@ -6,7 +6,7 @@
 // kernel serves every dense contraction of the layer.
 //
 // Tile 256x256x64, 8 waves (2 along M x 4 along N), v_mfma_f32_16x16x32_bf16, fp32 accumulate.
-// HBM -> LDS by global_load_lds (16 B/lane) into two 64-KiB stages; the LDS image is lane-linear, so the
+// HBM -> LDS by LDS-DMA (16 B/lane, buffer form: common.h lds_dma16) into two 64-KiB stages; the LDS image is lane-linear, so the
 // bank swizzle (16-B slot ^= (row>>1)&7 inside each 128-B row) is applied to the per-lane SOURCE address and
 // to the ds_read_b128 address.  The accumulators hold C^T fragments (mfma(B,A)), so each lane owns 4
 // consecutive output columns; the epilogue stages the bf16 tile through LDS and stores whole 512-B rows.
@@ -113,14 +113,18 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(const GemmArgs g) {
   const int nk = nk1 + g.K2 / 64;  // K-extension tiles are bf16: 64 elements per 128-byte row
   const int kofs = split * nk1;    // first K tile of this tile's range (EPI_SPLITK)
 
-  // Per-lane source offsets are loop invariant (row * stride + swizzled chunk, 32-bit bytes); per K-tile only the
-  // wave-uniform base pointer advances, so the loads need no vector address arithmetic inside the loop.
+  // Per-lane source offsets are loop invariant (row * stride + swizzled chunk, 32-bit bytes); per K-tile only a scalar offset
+  // advances.  The loads go through one buffer descriptor per operand (common.h: lds_dma16), which takes exactly these parts, so there
+  // is no vector address arithmetic inside the loop (through global_load_lds every piece paid a 64-bit vector add).
   uint32_t aoff[4], boff[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     aoff[i] = (uint32_t)((int64_t)arow[i] * g.lda * ESZ + schunk * 16);
     boff[i] = (uint32_t)((int64_t)brow[i] * g.ldb * ESZ + schunk * 16);
   }
+  // byte extent of A[M, K] / B[N, K] with their row strides (check_extent keeps both below 4 GiB)
+  const __amdgpu_buffer_rsrc_t rsA = lds_dma_rsrc(g.A, (uint32_t)(((int64_t)(g.M - 1) * g.lda + g.K) * ESZ));
+  const __amdgpu_buffer_rsrc_t rsB = lds_dma_rsrc(g.B, (uint32_t)(((int64_t)(g.N - 1) * g.ldb + g.K) * ESZ));
 
   // ---- fragment read offsets (bytes inside a tile): row*128 + ((ks*4 + (lane>>4)) ^ ((lane>>1)&7))*16
   const int frow = lane & 15;
@@ -144,19 +148,26 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(const GemmArgs g) {
   // and A-hi in phase 0 of tile T-1, i.e. 5-7 phases before their first read.  LDS reuse (same 2 x 64 KiB stages):
   //   B(t) is read only in phase 0 (both 32-column halves stay in registers) -> free for B(t+2) after the phase-0 barrier
   //   A(t) is read in phases 0 and 2 -> free for A(t+2) after the phase-2 barrier.
-  // pieces (8 KiB = 64 tile rows, one global_load_lds per thread) of a half-tile: A 2, B BSI / 2
-  auto stage_q = [&](int kt, int which) {  // which: 0 A-lo, 1 A-hi, 2 B-lo, 3 B-hi of K-tile kt into stage kt&1
-    if (kt >= nk) return;
+  // pieces (8 KiB = 64 tile rows, one LDS-DMA load per thread) of a half-tile: A 2, B BSI / 2
+  // steady_tag: the caller guarantees kt < nk1 (a tile of the main operands), so the piece is issued without a guard
+  auto stage_q = [&](auto steady_tag, int kt, int which) {  // which: 0 A-lo, 1 A-hi, 2 B-lo, 3 B-hi of K-tile kt into stage kt&1
+    constexpr bool steady = decltype(steady_tag)::value;
+    if constexpr (!steady) {
+      if (kt >= nk) return;
+    }
     const int half = which >> 1, hi = which & 1;
     const int np = half ? BSI / 2 : 2;
     char* sT = smem + (kt & 1) * STAGE_BYTES + half * A_TILE_BYTES + hi * np * 8192;
-    if (kt < nk1) {
-      const char* base = (const char*)(half ? g.B : g.A) + (int64_t)(kt + kofs) * 128;
+    if (steady || kt < nk1) {
+      const uint32_t koff = (uint32_t)(kt + kofs) * 128;  // wave-uniform: the scalar offset of the load
 #pragma unroll
-      for (int j = 0; j < 2; ++j)
-        if (j < np)
-          __builtin_amdgcn_global_load_lds((gbl_void*)(base + (half ? boff[np * hi + j] : aoff[2 * hi + j])), (lds_void*)(sT + (j * 512 + wave * 64) * 16), 16, 0, 0);
-    } else {
+      for (int j = 0; j < 2; ++j) {
+        if (j < np) {
+          if (half) lds_dma16(rsB, (llx_lds_void*)(sT + (j * 512 + wave * 64) * 16), boff[np * hi + j], koff);
+          else lds_dma16(rsA, (llx_lds_void*)(sT + (j * 512 + wave * 64) * 16), aoff[2 * hi + j], koff);
+        }
+      }
+    } else {  // K-extension tiles (the tail only): own leading dimensions, the flat form
       const char* base = (const char*)(half ? g.B2 : g.A2) + (int64_t)(kt - nk1) * 128;
       const int64_t l = (half ? g.ldb2 : g.lda2) * 2;  // the K-extension operands are bf16 in the int8 kernel too
 #pragma unroll
@@ -210,21 +221,28 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(const GemmArgs g) {
     }
   };
   // prologue: all of tile 0, then B-lo, B-hi, A-lo of tile 1
-  stage_q(0, 0); stage_q(0, 1); stage_q(0, 2); stage_q(0, 3);
-  stage_q(1, 2); stage_q(1, 3); stage_q(1, 0);
-  auto ktile = [&](int kt, auto ext_tag) __attribute__((always_inline)) {
+  {
+    const std::false_type guarded{};
+    stage_q(guarded, 0, 0); stage_q(guarded, 0, 1); stage_q(guarded, 0, 2); stage_q(guarded, 0, 3);
+    stage_q(guarded, 1, 2); stage_q(guarded, 1, 3); stage_q(guarded, 1, 0);
+  }
+  // steady_tag: kt + 2 < nk1, i.e. every tile this K-tile stages (kt + 1, kt + 2) is a tile of the main operands and tile kt + 1
+  // exists: no guard around a piece and a fixed vmcnt.  The tail (the last two main tiles and the K-extension) runs the same body
+  // with the guards.
+  auto ktile = [&](int kt, auto ext_tag, auto steady_tag) __attribute__((always_inline)) {
+    constexpr bool steady = decltype(steady_tag)::value;
     auto mfma = [&](const i32x4_t& b, const i32x4_t& a, acc_t& c) { mfma_t(ext_tag, b, a, c); };
     const char* sA = smem + (kt & 1) * STAGE_BYTES;
     const char* sB = sA + A_TILE_BYTES;
     // ---------------- phase 0: tile kt has landed once all but the youngest loads (3 half-tiles of kt+1: A-lo 2 pieces, B-lo and B-hi
     // BSI / 2 each = 6 | 4 loads per thread) are done
-    if (kt + 1 < nk) {
+    if (steady || kt + 1 < nk) {
       if constexpr (BSI == 4) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    stage_q(kt + 1, 1);  // A-hi of the next tile (its stage's A-hi was last read in phase 2 of tile kt-1)
+    stage_q(steady_tag, kt + 1, 1);  // A-hi of the next tile (its stage's A-hi was last read in phase 2 of tile kt-1)
     i32x4_t bfr[2][4], af[2 * MH];  // bfr[ks][nh*2 + n2], af[ks*MH + m4]
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
@@ -246,7 +264,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(const GemmArgs g) {
     __builtin_amdgcn_s_barrier();  // every wave has its B fragments: B(kt) may be overwritten
     asm volatile("" ::: "memory");
     // ---------------- phase 1: quadrant (first row half, cols 32-63)
-    stage_q(kt + 2, 2);
+    stage_q(steady_tag, kt + 2, 2);
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
@@ -256,7 +274,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(const GemmArgs g) {
         for (int n2 = 0; n2 < 2; ++n2) mfma(bfr[ks][2 + n2], af[ks * MH + m4], acc[m4][2 + n2]);
     __builtin_amdgcn_s_setprio(0);
     // ---------------- phase 2: quadrant (second row half, cols 32-63)
-    stage_q(kt + 2, 3);
+    stage_q(steady_tag, kt + 2, 3);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -273,7 +291,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(const GemmArgs g) {
     __builtin_amdgcn_s_barrier();  // every wave has its second A half: A(kt) may be overwritten
     asm volatile("" ::: "memory");
     // ---------------- phase 3: quadrant (second row half, cols 0-31)
-    stage_q(kt + 2, 0);
+    stage_q(steady_tag, kt + 2, 0);
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
@@ -284,11 +302,15 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(const GemmArgs g) {
     __builtin_amdgcn_s_setprio(0);
   };
   const int nk_main = I8 ? nk1 : nk;  // bf16: the K-extension tiles use the same MFMA and simply continue the loop
-  for (int kt = 0; kt < nk_main; ++kt) ktile(kt, std::false_type{});
+  int kt = 0;
+#pragma unroll 1
+  for (; kt + 2 < nk1; ++kt) ktile(kt, std::false_type{}, std::true_type{});
+#pragma unroll 1
+  for (; kt < nk_main; ++kt) ktile(kt, std::false_type{}, std::false_type{});
   if constexpr (I8) {
     if (nk > nk1) {
       dequant_in_place();
-      for (int kt = nk1; kt < nk; ++kt) ktile(kt, std::true_type{});
+      for (kt = nk1; kt < nk; ++kt) ktile(kt, std::true_type{}, std::false_type{});
     }
   }
   __syncthreads();  // all LDS reads done before the epilogue reuses the stages
