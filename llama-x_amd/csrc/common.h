@@ -178,6 +178,35 @@ __device__ __forceinline__ void lds_tr_wait8(s16x4_t (&c)[4], s16x4_t (&d)[4]) {
   asm volatile("s_waitcnt lgkmcnt(%8)" : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(d[0]), "+v"(d[1]), "+v"(d[2]), "+v"(d[3]) : "n"(N));
   __builtin_amdgcn_sched_barrier(0);
 }
+// ---- ds_read_b128 as inline asm, for a main loop that counts its fragment waits by hand.  Through plain loads hipcc puts
+// `s_waitcnt lgkmcnt(0)` in front of the first MFMA that uses any fragment of a group, whatever order the reads are written in.  The
+// ordering rules are those of lds_tr_read: the reads are volatile asm (kept in source order among themselves, the barriers and the
+// LDS-DMA issues), and a wait names every register it covers "+v" - fragments it releases, and any accumulator whose MFMAs must stay
+// above it - so that no consumer can be scheduled across it.  The wait itself and the "+v" marks are separate volatile asm statements
+// (an operand list cannot be a parameter pack); the marks emit nothing.
+__device__ __forceinline__ void lds_read16_rt(i32x4_t& dst, uint32_t addr, int off) {
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off));
+}
+template <typename T>
+__device__ __forceinline__ void lds_pin1(T& x) { asm volatile("" : "+v"(x)); }
+template <typename T, int N>
+__device__ __forceinline__ void lds_pin1(T (&x)[N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) asm volatile("" : "+v"(x[i]));
+}
+// no instruction: the named registers (or arrays of registers) are read and redefined here, in program order with the asm reads
+template <typename... T>
+__device__ __forceinline__ void lds_pin(T&... x) {
+  (lds_pin1(x), ...);
+  __builtin_amdgcn_sched_barrier(0);
+}
+// at most N LDS reads still outstanding (they return in order) before anything that uses the named registers
+template <int N, typename... T>
+__device__ __forceinline__ void lds_wait(T&... x) {
+  asm volatile("s_waitcnt lgkmcnt(%0)" : : "n"(N));
+  (lds_pin1(x), ...);
+  __builtin_amdgcn_sched_barrier(0);
+}
 __device__ __forceinline__ bf16x8_t frag_of(const s16x4_t& lo, const s16x4_t& hi) {
   const llx_s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   return __builtin_bit_cast(bf16x8_t, v);

@@ -134,6 +134,14 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(const GemmArgs g) {
   const int b_base = (wn * 64 + frow) * 128;
   const int slot0 = ((0 * 4 + fq) ^ fsw) * 16;
   const int slot1 = ((1 * 4 + fq) ^ fsw) * 16;
+  // The reads are inline asm (common.h: lds_read16_rt) on 32-bit LDS addresses: four lane addresses per K-tile (A | B of stage kt & 1,
+  // k-step 0 | 1); the 16-row fragment index is the instruction's immediate offset (m4 * 2048 < 64 KiB)
+  const uint32_t sbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+  const uint32_t fa0 = sbase + a_base + slot0, fa1 = sbase + a_base + slot1;
+  const uint32_t fb0 = sbase + A_TILE_BYTES + b_base + slot0, fb1 = sbase + A_TILE_BYTES + b_base + slot1;
+  // bf16: the k-step-0 fragments of the second A half are requested under phase 1's MFMAs, into MH registers of their own (the int8
+  // instances hold 246-248 registers without them)
+  constexpr bool EARLY_AHI = !I8;
 
   using acc_t = typename std::conditional<I8, i32x4_t, f32x4_t>::type;
   acc_t acc[MI][4];
@@ -147,7 +155,8 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(const GemmArgs g) {
   // barriers behind a counted vmcnt.  Half-tiles of K-tile T are issued:  B-lo, B-hi, A-lo in phases 1,2,3 of tile T-2
   // and A-hi in phase 0 of tile T-1, i.e. 5-7 phases before their first read.  LDS reuse (same 2 x 64 KiB stages):
   //   B(t) is read only in phase 0 (both 32-column halves stay in registers) -> free for B(t+2) after the phase-0 barrier
-  //   A(t) is read in phases 0 and 2 -> free for A(t+2) after the phase-2 barrier.
+  //   A(t) is read in phases 0 and 2 (bf16: half of phase 2's reads are issued in phase 1) -> free for A(t+2) after the phase-2 barrier.
+  // Every fragment read is waited for (counted lgkmcnt) before the barrier that releases its tile.
   // pieces (8 KiB = 64 tile rows, one LDS-DMA load per thread) of a half-tile: A 2, B BSI / 2
   // steady_tag: the caller guarantees kt < nk1 (a tile of the main operands), so the piece is issued without a guard
   auto stage_q = [&](auto steady_tag, int kt, int which) {  // which: 0 A-lo, 1 A-hi, 2 B-lo, 3 B-hi of K-tile kt into stage kt&1
@@ -232,8 +241,15 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(const GemmArgs g) {
   auto ktile = [&](int kt, auto ext_tag, auto steady_tag) __attribute__((always_inline)) {
     constexpr bool steady = decltype(steady_tag)::value;
     auto mfma = [&](const i32x4_t& b, const i32x4_t& a, acc_t& c) { mfma_t(ext_tag, b, a, c); };
-    const char* sA = smem + (kt & 1) * STAGE_BYTES;
-    const char* sB = sA + A_TILE_BYTES;
+    // the MFMAs issued so far on one quadrant's accumulators stay above this point (see lds_wait)
+    auto pin_acc = [&](int m_lo, int n_lo) {
+#pragma unroll
+      for (int m4 = 0; m4 < MH; ++m4)
+#pragma unroll
+        for (int n2 = 0; n2 < 2; ++n2) lds_pin1(acc[m_lo + m4][n_lo + n2]);
+    };
+    const uint32_t so = (uint32_t)(kt & 1) * STAGE_BYTES;
+    const uint32_t pa0 = so + fa0, pa1 = so + fa1, pb0 = so + fb0, pb1 = so + fb1;
     // ---------------- phase 0: tile kt has landed once all but the youngest loads (3 half-tiles of kt+1: A-lo 2 pieces, B-lo and B-hi
     // BSI / 2 each = 6 | 4 loads per thread) are done
     if (steady || kt + 1 < nk) {
@@ -243,49 +259,78 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(const GemmArgs g) {
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     stage_q(steady_tag, kt + 1, 1);  // A-hi of the next tile (its stage's A-hi was last read in phase 2 of tile kt-1)
-    i32x4_t bfr[2][4], af[2 * MH];  // bfr[ks][nh*2 + n2], af[ks*MH + m4]
+    // Fragment reads in the order of use, the waits counted per k-step (LDS returns in order): k-step 0 (B n0 n1, A-lo m0..MH-1),
+    // k-step 1 (the same), then phase 1's four B fragments - 8 + 2 MH reads, so MH + 6 are still out when k-step 0 may start and 4
+    // when k-step 1 may.
+    i32x4_t bfr[2][4], af[2][MH], ah0[MH];  // bfr[ks][nh*2 + n2], af[ks][m4]; ah0: A-hi k-step 0 (EARLY_AHI)
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+      for (int n2 = 0; n2 < 2; ++n2) lds_read16_rt(bfr[ks][n2], ks ? pb1 : pb0, n2 * 16 * 128);
+#pragma unroll
+      for (int m4 = 0; m4 < MH; ++m4) lds_read16_rt(af[ks][m4], ks ? pa1 : pa0, m4 * 16 * 128);
+    }
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-      for (int ni = 0; ni < 4; ++ni) bfr[ks][ni] = *reinterpret_cast<const i32x4_t*>(sB + b_base + ni * 16 * 128 + (ks ? slot1 : slot0));
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int m4 = 0; m4 < MH; ++m4) af[ks * MH + m4] = *reinterpret_cast<const i32x4_t*>(sA + a_base + m4 * 16 * 128 + (ks ? slot1 : slot0));
+      for (int n2 = 0; n2 < 2; ++n2) lds_read16_rt(bfr[ks][2 + n2], ks ? pb1 : pb0, (2 + n2) * 16 * 128);
     __builtin_amdgcn_s_setprio(1);
+    lds_wait<MH + 6>(bfr[0][0], bfr[0][1], af[0]);
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
+    for (int m4 = 0; m4 < MH; ++m4)
 #pragma unroll
-      for (int m4 = 0; m4 < MH; ++m4)
+      for (int n2 = 0; n2 < 2; ++n2) mfma(bfr[0][n2], af[0][m4], acc[m4][n2]);
+    // k-step 0's accumulators are named too: with the fragments alone hipcc sinks k-step 0's MFMAs below this wait
+    pin_acc(0, 0);
+    lds_wait<4>(bfr[1][0], bfr[1][1], af[1]);
 #pragma unroll
-        for (int n2 = 0; n2 < 2; ++n2) mfma(bfr[ks][n2], af[ks * MH + m4], acc[m4][n2]);
+    for (int m4 = 0; m4 < MH; ++m4)
+#pragma unroll
+      for (int n2 = 0; n2 < 2; ++n2) mfma(bfr[1][n2], af[1][m4], acc[m4][n2]);
     __builtin_amdgcn_s_setprio(0);
+    // phase 1's B fragments must be IN before the barrier that releases B(kt) (requested 16 MFMAs ago: nothing to wait for)
+    lds_wait<0>(bfr[0][2], bfr[0][3], bfr[1][2], bfr[1][3]);
     asm volatile("" ::: "memory");
     __builtin_amdgcn_s_barrier();  // every wave has its B fragments: B(kt) may be overwritten
     asm volatile("" ::: "memory");
     // ---------------- phase 1: quadrant (first row half, cols 32-63)
     stage_q(steady_tag, kt + 2, 2);
+    if constexpr (EARLY_AHI) {  // A(kt) stays valid until the phase-2 barrier
+#pragma unroll
+      for (int m4 = 0; m4 < MH; ++m4) lds_read16_rt(ah0[m4], pa0, (MH + m4) * 16 * 128);
+      __builtin_amdgcn_sched_barrier(0);
+    }
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
       for (int m4 = 0; m4 < MH; ++m4)
 #pragma unroll
-        for (int n2 = 0; n2 < 2; ++n2) mfma(bfr[ks][2 + n2], af[ks * MH + m4], acc[m4][2 + n2]);
+        for (int n2 = 0; n2 < 2; ++n2) mfma(bfr[ks][2 + n2], af[ks][m4], acc[m4][2 + n2]);
     __builtin_amdgcn_s_setprio(0);
     // ---------------- phase 2: quadrant (second row half, cols 32-63)
     stage_q(steady_tag, kt + 2, 3);
+    pin_acc(0, 2);
+    lds_pin(af[0], af[1]);  // phase 1 is through with af: the second A half goes into the same registers
+    i32x4_t (&ah)[MH] = EARLY_AHI ? ah0 : af[0];  // k-step 0 of the second A half
+    if constexpr (!EARLY_AHI) {
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
+      for (int m4 = 0; m4 < MH; ++m4) lds_read16_rt(af[0][m4], pa0, (MH + m4) * 16 * 128);
+    }
 #pragma unroll
-      for (int m4 = 0; m4 < MH; ++m4) af[ks * MH + m4] = *reinterpret_cast<const i32x4_t*>(sA + a_base + (MH + m4) * 16 * 128 + (ks ? slot1 : slot0));
+    for (int m4 = 0; m4 < MH; ++m4) lds_read16_rt(af[1][m4], pa1, (MH + m4) * 16 * 128);
     __builtin_amdgcn_s_setprio(1);
+    lds_wait<MH>(ah);
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
+    for (int m4 = 0; m4 < MH; ++m4)
 #pragma unroll
-      for (int m4 = 0; m4 < MH; ++m4)
+      for (int n2 = 0; n2 < 2; ++n2) mfma(bfr[0][2 + n2], ah[m4], acc[MH + m4][2 + n2]);
+    pin_acc(MH, 2);
+    lds_wait<0>(af[1]);  // in before the barrier that releases A(kt), too
 #pragma unroll
-        for (int n2 = 0; n2 < 2; ++n2) mfma(bfr[ks][2 + n2], af[ks * MH + m4], acc[MH + m4][2 + n2]);
+    for (int m4 = 0; m4 < MH; ++m4)
+#pragma unroll
+      for (int n2 = 0; n2 < 2; ++n2) mfma(bfr[1][2 + n2], af[1][m4], acc[MH + m4][2 + n2]);
     __builtin_amdgcn_s_setprio(0);
     asm volatile("" ::: "memory");
     __builtin_amdgcn_s_barrier();  // every wave has its second A half: A(kt) may be overwritten
@@ -298,7 +343,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(const GemmArgs g) {
 #pragma unroll
       for (int m4 = 0; m4 < MH; ++m4)
 #pragma unroll
-        for (int n2 = 0; n2 < 2; ++n2) mfma(bfr[ks][n2], af[ks * MH + m4], acc[MH + m4][n2]);
+        for (int n2 = 0; n2 < 2; ++n2) mfma(bfr[ks][n2], ks ? af[1][m4] : ah[m4], acc[MH + m4][n2]);
     __builtin_amdgcn_s_setprio(0);
   };
   const int nk_main = I8 ? nk1 : nk;  // bf16: the K-extension tiles use the same MFMA and simply continue the loop

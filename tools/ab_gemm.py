@@ -42,6 +42,12 @@ if what in ("bf16", "all"):
     bench("plain 4096x6144x4096", lambda: K.gemm_nt(x, wqkv), 2.0 * M * 6144 * D)
     w13 = rn(2 * I, D); hh = torch.empty(M, I, device=dev, dtype=torch.bfloat16)
     bench("gate|up + SwiGLU forward (EPI 7) 4096x28672x4096", lambda: K.gemm_nt(x, w13, epilogue=K.EPI_SWIGLU_FWD, e=hh), 2.0 * M * 2 * I * D)
+    S = 2048; pos = torch.arange(S, device=dev, dtype=torch.float32)[:, None] * (500000.0 ** (-torch.arange(64, device=dev, dtype=torch.float32) / 64))[None, :]
+    table = torch.stack([pos.cos(), pos.sin()], -1).contiguous()
+    a2 = rn(M, 64); b2q = rn(6144, 64); oq = torch.empty(M, 6144, device=dev, dtype=torch.bfloat16)
+    bench("q|k|v + LoRA ext + RoPE (EPI 8) 4096x6144x4096", lambda: K.gemm_nt(x, wqkv, out=oq, a2=a2, b2=b2q, rope=(table, S, 5120)), 2.0 * M * 6144 * D)
+    dgu2 = rn(M, 2 * I); w13t = rn(D, 2 * I); b2d = rn(D, 64)
+    bench("gate|up dgrad + LoRA ext 4096x4096x28672", lambda: K.gemm_nt(dgu2, w13t, a2=a2, b2=b2d), 2.0 * M * D * 2 * I)
 if what in ("i8", "all"):
     from subclasses.int8_mm import _launch as i8_gemm
     ri = lambda *s: torch.randint(-127, 128, s, device=dev, generator=g, dtype=torch.int8)
