@@ -13,10 +13,10 @@ from oracle import ref as O  # noqa: E402
 from tests.util import bf16_params, build_model  # noqa: E402
 
 
-def _setup(cuda, n_layers=3, kv_heads=1, quantize=None):
+def _setup(cuda, n_layers=3, kv_heads=1, quantize=None, rank=8):
     cfg = O.TINY._replace(num_layers=n_layers, num_kv_heads=kv_heads)
     p = O.init_params(cfg)
-    p.update(O.init_lora(cfg, 8))
+    p.update(O.init_lora(cfg, rank))
     pb, _ = bf16_params(p)
     batches = []
     for s in range(3):
@@ -24,7 +24,7 @@ def _setup(cuda, n_layers=3, kv_heads=1, quantize=None):
         batches.append((t, torch.roll(t, -1, 1)))
 
     def make():
-        model = build_model(cfg, pb, cuda, lora_rank=8, quantize=quantize, quantize_kwargs=dict(dynamic_int8_act=True) if quantize else None)
+        model = build_model(cfg, pb, cuda, lora_rank=rank, quantize=quantize, quantize_kwargs=dict(dynamic_int8_act=True) if quantize else None)
         for n, q in model.named_parameters():
             q.requires_grad_("lora_" in n or n.endswith("norm.weight"))
         return model
@@ -37,11 +37,28 @@ def _adamw(params, capturable=False):
 
 
 def test_backward_writes_gradients_in_place(cuda):
+    _backward_writes_gradients_in_place(cuda, 8)
+
+
+def test_backward_writes_gradients_in_place_rank32(cuda):
+    """Rank 32: q|k|v (96 ranks) runs member by member - every member's LinearPlan.backward claims its own arena slots for dA and dB -
+    while gate|up sits at R = 64 exactly on the fused route."""
+    from llx.ops import GroupPlan
+
+    _backward_writes_gradients_in_place(cuda, 32)
+    cfg, make, _ = _setup(cuda, n_layers=1, kv_heads=2, rank=32)
+    lay = make().layers[0]
+    qkv = GroupPlan([lay.attention.wq, lay.attention.wk, lay.attention.wv])
+    w13 = GroupPlan([lay.feed_forward.w1, lay.feed_forward.w3])
+    assert not qkv.fused and w13.fused and w13.R == 64
+
+
+def _backward_writes_gradients_in_place(cuda, rank):
     from llx.arena import TrainableArena
 
     # two kv heads: the q|k|v boundaries (512, 768, 1024) are multiples of 256 as at 8B dimensions, so the B factors take the segmented
     # in-place route too (with TINY's single kv head they fall back to slicing copies, which settle() gathers: the other tests)
-    _, make, batches = _setup(cuda, kv_heads=2)
+    _, make, batches = _setup(cuda, kv_heads=2, rank=rank)
     ref = make()
     ref(batches[0][0], labels=batches[0][1]).backward()
     model = make()

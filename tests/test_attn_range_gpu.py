@@ -228,8 +228,7 @@ def test_layer_with_diagonal_dominant_heads_at_8b_dimensions(cuda, kind):
     delta from the bf16 O (test_attn_bwd_dynamic_range_both_routes)."""
     from modelling import apply_linear_adapter_
     from modelling.llama import LlamaConfig, MaskSpec, TransformerLayer, build_rope
-    from tests.test_model_gpu import _close, _rows_close
-    from tests.util import bf16_params
+    from tests.util import _close, _rows_close, bf16_params
 
     S = 4096
     cfg = O.LLAMA31_8B._replace(num_layers=1, max_seq_len=S)

@@ -7,7 +7,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import ref as O  # noqa: E402
-from tests.util import bf16_params, build_model  # noqa: E402
+from tests.util import _close, _rows_close, bf16_params, build_model, layer_parity  # noqa: E402
 
 CFG = O.TINY
 
@@ -18,26 +18,6 @@ def _data(B, S, seed=0):
     labels[:, : S // 4] = -100
     labels[:, -1] = -100
     return tokens, labels
-
-
-def _close(a, b, rel, name):
-    scale = b.abs().max().item()
-    err = (a - b).abs().max().item()
-    assert err <= rel * scale + 1e-6, f"{name}: max err {err:.4e} vs scale {scale:.4e} (allowed {rel * scale:.4e})"
-
-
-def _rows_close(a, b, name, min_cos=0.999, floor=1e-3):
-    """Per-row check next to the max-norm one: every row (last dim) of `a` must point the same way as the reference row and have
-    the same length - an error confined to small-magnitude rows (a dropped LoRA row block, a mis-rotated head) passes `_close` but
-    not this.  Rows whose reference norm is below `floor` x the largest row norm carry rounding noise only and are skipped."""
-    a2, b2 = a.reshape(-1, a.shape[-1]).double(), b.reshape(-1, b.shape[-1]).double()
-    nb = b2.norm(dim=1)
-    keep = nb > floor * nb.max()
-    cos = (a2 * b2).sum(1) / (a2.norm(dim=1) * nb).clamp_min(1e-30)
-    worst = cos[keep].min().item()
-    assert worst >= min_cos, f"{name}: worst per-row cosine {worst:.5f} < {min_cos} (row {int(cos.masked_fill(~keep, 2).argmin())})"
-    ratio = (a2.norm(dim=1) / nb.clamp_min(1e-30))[keep]
-    assert (ratio - 1).abs().max().item() < 0.05, f"{name}: per-row norm ratio off by {(ratio - 1).abs().max().item():.4f}"
 
 
 def test_logits_causal(cuda):
@@ -68,17 +48,22 @@ def test_loss_and_full_grads(cuda, S):
         _close(prm.grad.float().cpu(), pr[name].grad, 0.04, name)
 
 
-@pytest.mark.parametrize("rank", [8, 16])
+@pytest.mark.parametrize("rank", [8, 16, 32, 64])
 def test_lora_loss_and_grads(cuda, rank):
+    """Ranks 32 and 64 leave the fused group plans (q|k|v from rank 22, gate|up from 33: tests/lora_cases.py); they run at alpha = 2 rank
+    with B drawn wide (lora_cases.b_std), so the loss bar sees the adapters' forward contribution and their scale."""
+    from tests.lora_cases import b_std
+
+    scale = 2.0 if rank > 16 else 1.0
     p = O.init_params(CFG)
-    p.update(O.init_lora(CFG, rank))
+    p.update(O.init_lora(CFG, rank, b_std=b_std(rank)) if rank > 16 else O.init_lora(CFG, rank))
     pb, pf = bf16_params(p)
     tokens, labels = _data(2, 256)
     train = [k for k in pf if "lora_" in k or k.endswith("_norm.weight")]
     pr = {k: (v.clone().requires_grad_() if k in train else v) for k, v in pf.items()}
-    ref = O.llama_forward(tokens, pr, CFG, labels=labels, lora_scale=1.0)
+    ref = O.llama_forward(tokens, pr, CFG, labels=labels, lora_scale=scale)
     ref.backward()
-    model = build_model(CFG, pb, cuda, lora_rank=rank)
+    model = build_model(CFG, pb, cuda, lora_rank=rank, lora_alpha=scale * rank)
     for n, prm in model.named_parameters():
         if n.startswith(("tok_embeddings", "output", "norm")):
             prm.requires_grad_(False)
@@ -391,24 +376,6 @@ def test_kv_cache_prefill_and_decode(cuda):
         layer(hid.to(cuda).requires_grad_(), model.rope[:384], mask=scattered.to(cuda))
 
 
-def _mask_for(kind, S):
-    """(dense bool oracle mask | None, MaskSpec | None) for the layer-parity cases."""
-    from modelling.llama import MaskSpec
-
-    if kind == "causal":
-        return None, None
-    if kind == "doc":  # packed documents of uneven length + the packer's id-0 tail (train_metamathqa.py:51-83)
-        doc = torch.zeros(S, dtype=torch.int64)
-        for c in (S // 16 + 5, S // 3 + 77, S // 2 - 130, (7 * S) // 8 + 9):
-            doc[c:] += 1
-        doc[S - 100 :] = 0
-        return O.document_mask(doc), MaskSpec(doc_ids=doc)
-    if kind == "prefix":  # prefix-LM: bidirectional over the first P positions (P not a multiple of the 64/128 tiles)
-        P = S // 2 - 56
-        return O.prefix_lm_mask(S, [P])[0, 0], MaskSpec(prefix_len=torch.tensor([P]))
-    raise ValueError(kind)
-
-
 @pytest.mark.parametrize("S,kind,base", [(512, "causal", "bf16"), (2048, "causal", "bf16"), (4096, "causal", "bf16"), (4096, "doc", "bf16"),
                                          (4096, "prefix", "bf16"), (8192, "causal", "bf16"), (8192, "prefix", "bf16"), (8192, "mixed-prefix-b2", "bf16"),
                                          (4096, "causal", "int8-dynamic"), (4096, "causal", "int8-weight-only")])
@@ -421,83 +388,8 @@ def test_full_dimension_layer_parity(cuda, S, kind, base):
     (quantize_linear_ then the adapter, train_metamathqa.py:178-179) - dynamic: fused norm-quantiser, llx_int8_mm_dequant_ext with
     RoPE / SwiGLU / residual epilogues and the scaled adapter gradient pass; weight-only: the bf16 GEMM on the widened int8 image
     with the column-scale epilogue - against O.int8_linear per member linear."""
-    from modelling import apply_linear_adapter_
-    from modelling.llama import LlamaConfig, MaskSpec, TransformerLayer, build_rope
-    from subclasses import quantize_linear_
-
     cfg = O.LLAMA31_8B._replace(num_layers=1, max_seq_len=S)
-    p = {k: v for k, v in O.init_params(cfg._replace(vocab_size=8)).items() if k.startswith("layers.0.")}
-    p.update(O.init_lora(cfg, 16))
-    pb, pf = bf16_params(p)
-    B = 2 if kind == "mixed-prefix-b2" else 1
-    x = O.randn("x_full", (B, S, cfg.embed_dim), 0.5).bfloat16()
-    dy = O.randn("dy_full", (B, S, cfg.embed_dim), 0.1).bfloat16()
-    if base != "bf16":  # oracle side: quantise the bf16 weights exactly as Int8LinearWeight.from_float does (scales in bf16)
-        for suf in O.LINEAR_SUFFIXES:
-            key = f"layers.0.{suf}"
-            q, sc = O.quantize_int8_rowwise(pb[key + ".weight"])
-            pf.pop(key + ".weight")
-            pf[key + ".int_data"], pf[key + ".scale"], pf[key + ".dynamic"] = q, sc.float(), base == "int8-dynamic"
-    train = [k for k in pf if "lora_" in k or k.endswith("_norm.weight")]
-    pr = {k: (v.clone().requires_grad_() if k in train else v) for k, v in pf.items()}
-    xr = x.float().requires_grad_()
-    if kind == "mixed-prefix-b2":  # configs[4]: per-sample prefix lengths {2048, 4096} in one batch
-        P = torch.tensor([2048, 4096])
-        spec = MaskSpec(prefix_len=P)
-        outs = []
-        for b in range(B):  # the oracle sample by sample (its [H, S, S] fp32 scores are 8.6 GB each); parameter gradients add up
-            ob = O.layer(xr[b : b + 1], pr, 0, cfg, O.rope_table(cfg)[:S], O.prefix_lm_mask(S, P[b : b + 1])[0, 0], 1.0)
-            ob.backward(dy[b : b + 1].float())
-            outs.append(ob.detach())
-        ref = torch.cat(outs)
-    else:
-        dense, spec = _mask_for(kind, S)
-        ref = O.layer(xr, pr, 0, cfg, O.rope_table(cfg)[:S], dense, 1.0)
-        ref.backward(dy.float())
-        ref = ref.detach()
-
-    layer = TransformerLayer(LlamaConfig(**{f: getattr(cfg, f) for f in LlamaConfig._fields})).bfloat16()
-    layer.load_state_dict({k[len("layers.0."):]: v for k, v in pb.items() if "lora_" not in k})
-    if base != "bf16":
-        quantize_linear_(layer, "int8", dynamic_int8_act=base == "int8-dynamic")
-    apply_linear_adapter_(layer, "lora", rank=16, alpha=16.0)
-    with torch.no_grad():
-        for name, mod in layer.named_modules():
-            if f"layers.0.{name}.lora_a" in pb:
-                mod.lora_a.copy_(pb[f"layers.0.{name}.lora_a"])
-                mod.lora_b.copy_(pb[f"layers.0.{name}.lora_b"])
-    layer = layer.to(cuda)
-    for n, q in layer.named_parameters():
-        q.requires_grad_("lora_" in n or n.endswith("_norm.weight"))
-    rope = build_rope(LlamaConfig(**{f: getattr(cfg, f) for f in LlamaConfig._fields})).to(cuda)
-    xg = x.to(cuda).requires_grad_()
-    out = layer(xg, rope[:S], block_mask=spec)
-    out.backward(dy.to(cuda))
-    # Dynamic int8 activations: the oracle runs in fp32, the product rounds every activation to bf16 before the row-wise quantiser, so
-    # a few per cent of the int8 codes differ by one step between the two - a difference of the size of the quantisation noise itself
-    # (the heavy-tailed silu(g)*u rows carry ~3 % of it).  The max-norm bars widen accordingly; the per-row cosine bars stay tight
-    # enough to catch any structural error (a wrong scale, a dropped row block, a mis-rotated head).
-    dyn = base == "int8-dynamic"
-    t_out, t_dx, t_g = (0.06, 0.08, 0.08) if dyn else (0.02, 0.04, 0.05)
-    c_out, c_dx, c_g = (0.998, 0.995, 0.99) if dyn else (0.999, 0.998, 0.995)
-    o_cpu, dx_cpu = out.float().cpu(), xg.grad.float().cpu()
-    print(f"[{S}-{kind}-{base}] out err {(o_cpu - ref).abs().max() / ref.abs().max():.4f}, dx err {(dx_cpu - xr.grad).abs().max() / xr.grad.abs().max():.4f}")
-    _close(o_cpu, ref, t_out, "layer output at 8B dims")
-    _rows_close(o_cpu, ref, "layer output rows", min_cos=c_out)
-    _close(dx_cpu, xr.grad, t_dx, "dx at 8B dims")
-    _rows_close(dx_cpu, xr.grad, "dx rows", min_cos=c_dx)
-    for name, q in layer.named_parameters():
-        if q.requires_grad:
-            _close(q.grad.float().cpu(), pr["layers.0." + name].grad, t_g, name)
-            if q.grad.dim() == 2:
-                _rows_close(q.grad.float().cpu(), pr["layers.0." + name].grad, name, min_cos=c_g)
-    # determinism at full size: a second run is bit-identical (no atomics anywhere on the path)
-    xg2 = x.to(cuda).requires_grad_()
-    for q in layer.parameters():
-        q.grad = None
-    out2 = layer(xg2, rope[:S], block_mask=spec)
-    out2.backward(dy.to(cuda))
-    assert torch.equal(out2, out) and torch.equal(xg2.grad, xg.grad)
+    layer_parity(cuda, cfg, S, kind, base, ("lora", O.init_lora(cfg, 16), 1.0))
 
 
 def test_packed_iterator_with_prefetch_trains(cuda):
