@@ -151,6 +151,18 @@ int llx_gemv_bf16(const void* w0, int64_t ldw0, int64_t n0, const void* w1, int6
                   const void* res, int64_t ldr, const float* rope, int64_t n_q, int64_t n_k, void* k_cache, void* v_cache, int64_t c_sh,
                   int64_t c_ss, const int64_t* input_pos, const void* bext0, const void* bext1, const void* bext2, int64_t rank0, int64_t rank1,
                   int64_t rank2, const void* t, int64_t ldt, float lora_scale, llx_stream_t s);
+/* llx_gemv_bf16 on int8 weight rows: F.linear on an Int8LinearWeight (subclasses/int8.py:106-121) at the same call sites of a model
+ * after quantize_linear_(model.layers, "int8", ...).  W_s [n_s, K] int8 row-major (ldw_s in bytes, % 16), scale_s [n_s] bf16 per-row
+ * scales, K % 16 == 0, all members of a call of one kind.  dynamic = 0 (weight-only, :118): out = bf16(bf16(x . W^T) * scale[row]).
+ * dynamic = 1 (:112-113, int8_mm.py:93-118): each (normalised) row of x is quantised as llx_quantize_int8_rowwise does, int32 dot
+ * products, out = bf16(((float)acc * x_scale[m]) * scale[row]) - bit-exact with the reference when no norm is fused.  Norm, epilogues
+ * and LoRA operands as llx_gemv_bf16 (t = x . A^T from llx_gemv_bf16 on the un-quantised x): out = bf16(out + lora_scale * t_s . bext_s[row]). */
+int llx_gemv_i8(const void* w0, int64_t ldw0, int64_t n0, const void* w1, int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2, int64_t n2,
+                const void* x, int64_t ldx, int64_t M, int64_t K, const void* norm_w, float eps, int epilogue, void* out, int64_t ldo,
+                const void* res, int64_t ldr, const float* rope, int64_t n_q, int64_t n_k, void* k_cache, void* v_cache, int64_t c_sh,
+                int64_t c_ss, const int64_t* input_pos, const void* bext0, const void* bext1, const void* bext2, int64_t rank0, int64_t rank1,
+                int64_t rank2, const void* t, int64_t ldt, float lora_scale, const void* scale0, const void* scale1, const void* scale2,
+                int dynamic, llx_stream_t s);
 /* *extent (device int) = 1 + the largest key index any of the `rows` bool mask rows (row stride in bytes) allows; 0 if none: the
  * mask of the cached path is data (rows of a tril matrix gathered at input_pos, :194,:205), its extent sizes the decode key ranges. */
 int llx_mask_extent(const void* mask, int64_t row_stride, int64_t rows, int64_t Skv, int* extent, llx_stream_t s);

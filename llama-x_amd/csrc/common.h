@@ -90,6 +90,26 @@ __device__ __forceinline__ float block_max(float v, float* red) {
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// ---- row-wise int8 quantiser pieces (subclasses/int8.py:10-16) on 8 packed bf16 elements, shared by int8_quant.hip and the int8
+// GEMV prologue of decode.hip: scale = absmax / 127 in fp32, the divisor is max(scale, 1e-12), the quotient (true IEEE division) is
+// rounded half-to-even; the scale that dequantises is the fp32 scale rounded to the row's dtype.
+__device__ __forceinline__ float q8_absmax8(const u32x4_t& v, float amax) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) amax = fmaxf(amax, fmaxf(fabsf(bflo(v[e])), fabsf(bfhi(v[e]))));
+  return amax;
+}
+__device__ __forceinline__ float q8_scale(float amax) { return amax / 127.0f; }
+__device__ __forceinline__ float q8_divisor(float scale) { return fmaxf(scale, 1e-12f); }
+__device__ __forceinline__ u32x2_t q8_quant8(const u32x4_t& v, float div) {
+  u32x2_t o = {0u, 0u};
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int a = (int)rintf(bflo(v[e]) / div), b = (int)rintf(bfhi(v[e]) / div);
+    o[e >> 1] |= ((uint32_t)(a & 0xff) | ((uint32_t)(b & 0xff) << 8)) << ((e & 1) * 16);
+  }
+  return o;
+}
+
 // ---- SwiGLU pieces shared by the element-wise kernels and the GEMM epilogue (h = silu(g) * u, modelling/llama.py:150)
 // v_rcp_f32 (1 ulp) instead of the IEEE divide sequence: the result is rounded to bf16 right after
 __device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }

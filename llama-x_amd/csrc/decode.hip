@@ -13,13 +13,19 @@
 //   * mask_extent_kernel: the number of leading keys any query row may attend to (the mask is a bool tensor - the reference gathers
 //     rows of its tril matrix, :194,:205 - so the extent is data; it stays on the device and sizes the key ranges of the workgroups);
 //   * kv_scatter_kernel: KVCache.update (:83-90) for calls that do not go through the fused projection.
+// int8 weights (subclasses/int8.py:106-121) stream through the same kernel at one byte per element: weight-only (bf16 activations,
+// bytes sign-extended to fp32, EPI_COLSCALE's rounding points) and dynamic (the prologue quantises the activation rows as
+// int8_quant.hip does, v_dot4c_i32_i8 into int32, EPI_ROWCOLSCALE's dequantisation).
 // HBM-bound: the step moves (weights + live K/V) bytes once; bench.py --config decode reports that against the 8 TB/s peak.
 #include "common.h"
+#include <type_traits>
 
 #define HD 128
 
 // ------------------------------------------------------------------------------------------------- weight-streaming GEMV
 enum { GV_NONE = 0, GV_RESIDUAL = 1, GV_QKV = 2, GV_SWIGLU = 3 };
+// weight kind: bf16 | int8 rows x bf16 activations (weight-only) | int8 rows x int8 activations quantised in the prologue (dynamic)
+enum { WK_BF16 = 0, WK_I8W = 1, WK_I8D = 2 };
 
 struct GemvArgs {
   const bf16_t* W[3]; int64_t ldw[3]; int seg_end[3];  // output rows [seg_end[s-1], seg_end[s]) come from W[s] (row-major [rows, K])
@@ -34,7 +40,18 @@ struct GemvArgs {
   // LoRA (modelling/lora.py:43): out += scale * (t . Bext[row]) with t = x . A^T computed by a previous launch of this kernel
   const bf16_t* bext[3]; int64_t ldb[3]; int t_off[3]; int rank[3];
   const bf16_t* t; int64_t ldt; float lora_scale;
+  const bf16_t* wscale[3];                              // int8 kinds: per-row scales of W[s] (W[s] then points at int8 rows, ldw in bytes)
 };
+
+// 16 int8 weights (sign-extended to fp32: one v_cvt_f32_i32 with a byte selector each) against 16 fp32 activations, chained onto s
+__device__ __forceinline__ float dot16_i8(const u32x4_t& w, const float (&xf)[16], float s) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+#pragma unroll
+    for (int b = 0; b < 4; ++b) s = __builtin_fmaf((float)(signed char)(w[e] >> (8 * b)), xf[4 * e + b], s);
+  }
+  return s;
+}
 
 __device__ __forceinline__ float dot8(const u32x4_t& w, const float (&xf)[8]) {
   float s = bflo(w[0]) * xf[0];
@@ -65,45 +82,75 @@ __device__ __forceinline__ float wave_sum_valu(float v) {
   const auto s32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
   return __uint_as_float(s32[0]) + __uint_as_float(s32[1]);
 }
+// the same butterfly on int32 (the dynamic int8 kind: integer sums are exact in any order)
+template <int CTRL>
+__device__ __forceinline__ int dpp_i32(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
+__device__ __forceinline__ int wave_sum_valu_i(int v) {
+  v += dpp_i32<0xB1>(v);
+  v += dpp_i32<0x4E>(v);
+  v += dpp_i32<0x141>(v);
+  v += dpp_i32<0x140>(v);
+  const auto s16 = __builtin_amdgcn_permlane16_swap((uint32_t)v, (uint32_t)v, false, false);
+  v = (int)(s16[0] + s16[1]);
+  const auto s32 = __builtin_amdgcn_permlane32_swap((uint32_t)v, (uint32_t)v, false, false);
+  return (int)(s32[0] + s32[1]);
+}
 
 // RPW output rows per wave at a time (4, or 2 for the narrow projections: twice the waves, each with the same 8 loads in flight, so
 // that 4096 output rows still put 2 workgroups on every CU); a step is 8 / RPW pieces of 512 elements (64 lanes x 8) of those rows.
-template <int MT, int EPI, bool NORM, int RPW = 4>
+// int8 kinds: a lane's 16 bytes are 16 elements, a piece is 1024 elements.  WK_I8W keeps x in LDS as bf16, each piece stored as its
+// lanes' first eight elements (1 KiB) followed by their second eight, so that both 16-byte reads of a lane are conflict-free;
+// WK_I8D keeps x as int8 (after the optional norm each row is quantised here, the row scales stay in registers).
+template <int MT, int EPI, bool NORM, int RPW = 4, int WK = WK_BF16>
 __global__ __launch_bounds__(256, 2) void gemv_kernel(const GemvArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int K = a.K;
   static_assert(RPW == 4 || RPW == 2, "rows per wave");
-  constexpr int PIECES = 8 / RPW, STEP = 512 * PIECES;
+  using WT = std::conditional_t<WK == WK_BF16, bf16_t, int8_t>;  // a stored weight element
+  constexpr int EPL = 16 / (int)sizeof(WT), PIECE = 64 * EPL;      // elements per lane and load; per wave-instruction
+  constexpr int PIECES = 8 / RPW, STEP = PIECE * PIECES;
   const int nsteps = (K + STEP - 1) / STEP;  // a step = PIECES 512-element pieces of RPW weight rows: 8 x 16-byte loads per lane
-  const int Kp = nsteps * STEP;              // the LDS copy of x is zero-padded to whole steps: weight lanes past K multiply zeros
+  // the LDS copy of x is zero-padded to whole steps: weight lanes past K multiply zeros (int8 kinds, whose steps are 4096 elements:
+  // padded to whole pieces plus ONE piece of zeros that every piece past the row end reads)
+  const int Kp = WK == WK_BF16 ? nsteps * STEP : ((K + PIECE - 1) / PIECE + 1) * PIECE;
   bf16_t* xs = reinterpret_cast<bf16_t*>(smem);  // [MT][Kp]
-  float* red = reinterpret_cast<float*>(smem + (size_t)MT * Kp * 2);
+  int8_t* xq = reinterpret_cast<int8_t*>(smem);  // [MT][Kp] (WK_I8D)
+  float* red = reinterpret_cast<float*>(smem + (size_t)MT * Kp * (WK == WK_I8D ? 1 : 2));
+  float xsc[MT];                                 // WK_I8D: the activation rows' scales, as the bf16 the reference keeps
 
   // ---- row groups: RPW output rows per wave at a time.  SWIGLU: the gate and up rows of RPW / 2 hidden units (W[0] rows UPG g .. and
   // W[1] rows UPG g ..; r = matrix * UPG + unit), so that the epilogue has g and u of one unit side by side.
   constexpr int UPG = RPW / 2;  // hidden units per SwiGLU group
-  struct Grp { const bf16_t* wr[RPW]; int row0, seg; };
+  struct Grp { const WT* wr[RPW]; int row0, seg; float sc[RPW]; };  // sc: the rows' weight scales (int8 kinds)
   auto setup = [&](int g, Grp& G) {
     if constexpr (EPI == GV_SWIGLU) {
       const int half = a.N / 2;
       G.row0 = UPG * g; G.seg = 0;
 #pragma unroll
-      for (int r = 0; r < RPW; ++r) G.wr[r] = a.W[r / UPG] + (int64_t)min(G.row0 + (r % UPG), half - 1) * a.ldw[r / UPG];
+      for (int r = 0; r < RPW; ++r) G.wr[r] = reinterpret_cast<const WT*>(a.W[r / UPG]) + (int64_t)min(G.row0 + (r % UPG), half - 1) * a.ldw[r / UPG];
+      if constexpr (WK != WK_BF16) {
+#pragma unroll
+        for (int r = 0; r < RPW; ++r) G.sc[r] = bf2f(a.wscale[r / UPG][min(G.row0 + (r % UPG), half - 1)]);
+      }
     } else {
       G.row0 = RPW * g;
       G.seg = G.row0 >= a.seg_end[0] ? (G.row0 >= a.seg_end[1] ? 2 : 1) : 0;  // wave-uniform (segment boundaries are multiples of 4)
       const int base = G.seg == 0 ? 0 : a.seg_end[G.seg - 1];
       const int last = a.seg_end[G.seg] - 1 - base;
 #pragma unroll
-      for (int r = 0; r < RPW; ++r) G.wr[r] = a.W[G.seg] + (int64_t)min(G.row0 - base + r, last) * a.ldw[G.seg];
+      for (int r = 0; r < RPW; ++r) G.wr[r] = reinterpret_cast<const WT*>(a.W[G.seg]) + (int64_t)min(G.row0 - base + r, last) * a.ldw[G.seg];
+      if constexpr (WK != WK_BF16) {
+#pragma unroll
+        for (int r = 0; r < RPW; ++r) G.sc[r] = bf2f(a.wscale[G.seg][min(G.row0 - base + r, last)]);
+      }
     }
   };
   auto load_step = [&](u32x4_t (&w)[8], const Grp& G, int s) {
 #pragma unroll
     for (int j = 0; j < PIECES; ++j) {
-      const int k = (PIECES * s + j) * 512 + lane * 8;
+      const int k = (PIECES * s + j) * PIECE + lane * EPL;
       const int kk = k < K ? k : 0;  // lanes past the row end re-read its start; their x is zero
 #pragma unroll
       for (int r = 0; r < RPW; ++r) w[RPW * j + r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(G.wr[r] + kk));
@@ -132,17 +179,52 @@ __global__ __launch_bounds__(256, 2) void gemv_kernel(const GemvArgs a) {
       ss = block_sum(ss, red);
       rstd = rsqrtf(ss / (float)K + a.eps);
     }
-    for (int i = tid * 8; i < Kp; i += 2048) {
-      u32x4_t v = {0u, 0u, 0u, 0u};
-      if (i < K) {
-        v = *reinterpret_cast<const u32x4_t*>(xr + i);
+    if constexpr (WK == WK_BF16) {
+      for (int i = tid * 8; i < Kp; i += 2048) {
+        u32x4_t v = {0u, 0u, 0u, 0u};
+        if (i < K) {
+          v = *reinterpret_cast<const u32x4_t*>(xr + i);
+          if constexpr (NORM) {
+            const u32x4_t w = *reinterpret_cast<const u32x4_t*>(a.norm_w + i);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = pack_bf2(bflo(v[e]) * rstd * bflo(w[e]), bfhi(v[e]) * rstd * bfhi(w[e]));
+          }
+        }
+        *reinterpret_cast<u32x4_t*>(xs + (size_t)m * Kp + i) = v;
+      }
+    } else {
+      // 8 elements of the (normalised, bf16-rounded) row: what the linear of the reference sees
+      auto xrow8 = [&](int i) -> u32x4_t {
+        u32x4_t v = *reinterpret_cast<const u32x4_t*>(xr + i);
         if constexpr (NORM) {
           const u32x4_t w = *reinterpret_cast<const u32x4_t*>(a.norm_w + i);
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = pack_bf2(bflo(v[e]) * rstd * bflo(w[e]), bfhi(v[e]) * rstd * bfhi(w[e]));
         }
+        return v;
+      };
+      if constexpr (WK == WK_I8W) {
+        for (int i = tid * 8; i < Kp; i += 2048) {
+          u32x4_t v = {0u, 0u, 0u, 0u};
+          if (i < K) v = xrow8(i);
+          // element (piece, lane l, half h, e) of the row -> piece * 1024 + h * 512 + l * 8 + e
+          const int at = (i & ~1023) + ((i >> 3) & 1) * 512 + ((i & 1023) >> 4) * 8;
+          *reinterpret_cast<u32x4_t*>(xs + (size_t)m * Kp + at) = v;
+        }
+      } else {
+        // quantize_int8_rowwise on the row (the pieces int8_quant.hip is made of); the second pass recomputes the same bf16 values
+        float amax = 0.f;
+        for (int i = tid * 8; i < K; i += 2048) amax = q8_absmax8(xrow8(i), amax);
+        amax = block_max(amax, red);
+        const float scale = q8_scale(amax);
+        const float div = q8_divisor(scale);
+        xsc[m] = bf2f(f2bf(scale));
+        for (int i = tid * 8; i < Kp; i += 2048) {
+          u32x2_t q = {0u, 0u};
+          if (i < K) q = q8_quant8(xrow8(i), div);
+          *reinterpret_cast<u32x2_t*>(xq + (size_t)m * Kp + i) = q;
+        }
       }
-      *reinterpret_cast<u32x4_t*>(xs + (size_t)m * Kp + i) = v;
     }
   }
   __syncthreads();
@@ -152,23 +234,51 @@ __global__ __launch_bounds__(256, 2) void gemv_kernel(const GemvArgs a) {
   for (int r = 0; r < RPW; ++r)
 #pragma unroll
     for (int m = 0; m < MT; ++m) acc[r][m] = 0.f;
+  int iacc[RPW][MT];  // WK_I8D: the integer dot products
+#pragma unroll
+  for (int r = 0; r < RPW; ++r)
+#pragma unroll
+    for (int m = 0; m < MT; ++m) iacc[r][m] = 0;
   auto compute_step = [&](const u32x4_t (&w)[8], int st) {
 #pragma unroll
     for (int j = 0; j < PIECES; ++j) {
-      const int k = (PIECES * st + j) * 512 + lane * 8;
+      const int k = (PIECES * st + j) * PIECE + lane * EPL;
 #pragma unroll
       for (int m = 0; m < MT; ++m) {
-        const u32x4_t xv = *reinterpret_cast<const u32x4_t*>(xs + (size_t)m * Kp + k);
-        float xf[8];
+        if constexpr (WK == WK_BF16) {
+          const u32x4_t xv = *reinterpret_cast<const u32x4_t*>(xs + (size_t)m * Kp + k);
+          float xf[8];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { xf[2 * e] = bflo(xv[e]); xf[2 * e + 1] = bfhi(xv[e]); }
+          for (int e = 0; e < 4; ++e) { xf[2 * e] = bflo(xv[e]); xf[2 * e + 1] = bfhi(xv[e]); }
 #pragma unroll
-        for (int r = 0; r < RPW; ++r) acc[r][m] += dot8(w[RPW * j + r], xf);
+          for (int r = 0; r < RPW; ++r) acc[r][m] += dot8(w[RPW * j + r], xf);
+        } else if constexpr (WK == WK_I8W) {
+          const bf16_t* xp = xs + (size_t)m * Kp + min((PIECES * st + j) * PIECE, Kp - PIECE) + lane * 8;
+          const u32x4_t x0 = *reinterpret_cast<const u32x4_t*>(xp), x1 = *reinterpret_cast<const u32x4_t*>(xp + 512);
+          float xf[16];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { xf[2 * e] = bflo(x0[e]); xf[2 * e + 1] = bfhi(x0[e]); xf[8 + 2 * e] = bflo(x1[e]); xf[9 + 2 * e] = bfhi(x1[e]); }
+#pragma unroll
+          for (int r = 0; r < RPW; ++r) acc[r][m] = dot16_i8(w[RPW * j + r], xf, acc[r][m]);
+        } else {
+          const u32x4_t xv = *reinterpret_cast<const u32x4_t*>(xq + (size_t)m * Kp + min((PIECES * st + j) * PIECE, Kp - PIECE) + lane * EPL);
+#pragma unroll
+          for (int r = 0; r < RPW; ++r)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) iacc[r][m] = __builtin_amdgcn_sdot4((int)w[RPW * j + r][e], (int)xv[e], iacc[r][m], false);
+        }
       }
     }
   };
   auto finish = [&](const Grp& G) {
     const int row0 = G.row0, seg = G.seg;
+    // int8 kinds: the adapter term is summed on its own and meets the base after the base's bf16 rounding (modelling/lora.py:41-43)
+    const bool any_lora = WK != WK_BF16 && (a.bext[0] != nullptr || a.bext[1] != nullptr || a.bext[2] != nullptr);
+    float lacc[RPW][MT];
+#pragma unroll
+    for (int r = 0; r < RPW; ++r)
+#pragma unroll
+      for (int m = 0; m < MT; ++m) lacc[r][m] = 0.f;
     // LoRA extension: lanes 0 .. rank/8-1 hold 8 elements of the row's B factor each
 #pragma unroll
     for (int r = 0; r < RPW; ++r) {
@@ -189,23 +299,54 @@ __global__ __launch_bounds__(256, 2) void gemv_kernel(const GemvArgs a) {
           float xf[8];
 #pragma unroll
           for (int e = 0; e < 4; ++e) { xf[2 * e] = bflo(tv[e]); xf[2 * e + 1] = bfhi(tv[e]); }
-          acc[r][m] += a.lora_scale * dot8(bv, xf);
+          if constexpr (WK == WK_BF16) acc[r][m] += a.lora_scale * dot8(bv, xf);
+          else lacc[r][m] += a.lora_scale * dot8(bv, xf);
         }
       }
     }
 #pragma unroll
     for (int r = 0; r < RPW; ++r)
 #pragma unroll
-      for (int m = 0; m < MT; ++m) acc[r][m] = wave_sum_valu(acc[r][m]);
+      for (int m = 0; m < MT; ++m) {
+        if constexpr (WK == WK_I8D) iacc[r][m] = wave_sum_valu_i(iacc[r][m]);
+        else acc[r][m] = wave_sum_valu(acc[r][m]);
+      }
+    if (any_lora) {
+#pragma unroll
+      for (int r = 0; r < RPW; ++r)
+#pragma unroll
+        for (int m = 0; m < MT; ++m) lacc[r][m] = wave_sum_valu(lacc[r][m]);
+    }
     // ---- epilogue: lane m writes token m (every lane holds every sum)
     if (lane < MT && lane < a.M) {
       float v[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int r = 0; r < RPW; ++r) {
-        float sm = acc[r][0];
+        if constexpr (WK == WK_BF16) {
+          float sm = acc[r][0];
 #pragma unroll
-        for (int m = 1; m < MT; ++m) sm = lane == m ? acc[r][m] : sm;
-        v[r] = bf2f(f2bf(sm));  // the linear's bf16 output
+          for (int m = 1; m < MT; ++m) sm = lane == m ? acc[r][m] : sm;
+          v[r] = bf2f(f2bf(sm));  // the linear's bf16 output
+        } else {
+          float ls = lacc[r][0];
+#pragma unroll
+          for (int m = 1; m < MT; ++m) ls = lane == m ? lacc[r][m] : ls;
+          if constexpr (WK == WK_I8W) {
+            // (x @ W_i8^T) rounded to bf16, times the row's scale, rounded (subclasses/int8.py:118; EPI_COLSCALE of gemm_bf16.hip)
+            float sm = acc[r][0];
+#pragma unroll
+            for (int m = 1; m < MT; ++m) sm = lane == m ? acc[r][m] : sm;
+            v[r] = bf2f(f2bf(bf2f(f2bf(sm)) * G.sc[r]));
+          } else {
+            // int32 sum x activation-row scale x weight-row scale in fp32, rounded (int8_mm.py:93-118; EPI_ROWCOLSCALE)
+            int sm = iacc[r][0];
+            float xm = xsc[0];
+#pragma unroll
+            for (int m = 1; m < MT; ++m) { sm = lane == m ? iacc[r][m] : sm; xm = lane == m ? xsc[m] : xm; }
+            v[r] = bf2f(f2bf(((float)sm * xm) * G.sc[r]));
+          }
+          if (any_lora) v[r] = bf2f(f2bf(v[r] + ls));
+        }
       }
       const int m = lane;
       if constexpr (EPI == GV_SWIGLU) {
@@ -249,7 +390,7 @@ __global__ __launch_bounds__(256, 2) void gemv_kernel(const GemvArgs a) {
 #pragma unroll
     for (int r = 0; r < RPW; ++r)
 #pragma unroll
-      for (int m = 0; m < MT; ++m) acc[r][m] = 0.f;
+      for (int m = 0; m < MT; ++m) { acc[r][m] = 0.f; iacc[r][m] = 0; }
   };
   // software pipeline over the flattened (row group, step) sequence of this wave: while one register set is consumed the next step's
   // 8 loads (of this group or of the wave's next group) are in flight
@@ -278,21 +419,34 @@ __global__ __launch_bounds__(256, 2) void gemv_kernel(const GemvArgs a) {
   }
 }
 
-template <int MT, int EPI, int RPW>
+template <int MT, int EPI, int RPW, int WK>
 static int launch_gemv_n(const GemvArgs& a, int grid, size_t lds, hipStream_t stream) {
-  if (a.norm_w) hipLaunchKernelGGL((gemv_kernel<MT, EPI, true, RPW>), dim3(grid), dim3(256), lds, stream, a);
-  else hipLaunchKernelGGL((gemv_kernel<MT, EPI, false, RPW>), dim3(grid), dim3(256), lds, stream, a);
-  LLX_LAUNCH_CHECK("llx_gemv_bf16");
+  if (a.norm_w) hipLaunchKernelGGL((gemv_kernel<MT, EPI, true, RPW, WK>), dim3(grid), dim3(256), lds, stream, a);
+  else hipLaunchKernelGGL((gemv_kernel<MT, EPI, false, RPW, WK>), dim3(grid), dim3(256), lds, stream, a);
+  LLX_LAUNCH_CHECK(WK == WK_BF16 ? "llx_gemv_bf16" : "llx_gemv_i8");
   return LLX_OK;
 }
 
-template <int MT, int RPW>
+template <int MT, int RPW, int WK>
 static int launch_gemv_m(const GemvArgs& a, int epi, int grid, size_t lds, hipStream_t stream) {
   switch (epi) {
-    case GV_NONE: return launch_gemv_n<MT, GV_NONE, RPW>(a, grid, lds, stream);
-    case GV_RESIDUAL: return launch_gemv_n<MT, GV_RESIDUAL, RPW>(a, grid, lds, stream);
-    case GV_QKV: return launch_gemv_n<MT, GV_QKV, RPW>(a, grid, lds, stream);
-    default: return launch_gemv_n<MT, GV_SWIGLU, RPW>(a, grid, lds, stream);
+    case GV_NONE: return launch_gemv_n<MT, GV_NONE, RPW, WK>(a, grid, lds, stream);
+    case GV_RESIDUAL: return launch_gemv_n<MT, GV_RESIDUAL, RPW, WK>(a, grid, lds, stream);
+    case GV_QKV: return launch_gemv_n<MT, GV_QKV, RPW, WK>(a, grid, lds, stream);
+    default: return launch_gemv_n<MT, GV_SWIGLU, RPW, WK>(a, grid, lds, stream);
+  }
+}
+
+template <int RPW, int WK>
+static int launch_gemv_mt(const GemvArgs& a, int MT, int epi, int grid, size_t lds, hipStream_t stream) {
+  switch (MT) {
+    case 1: return launch_gemv_m<1, RPW, WK>(a, epi, grid, lds, stream);
+    case 2: return launch_gemv_m<2, RPW, WK>(a, epi, grid, lds, stream);
+    default:
+      // (weight-only int8 has no 4-token build: 16 fp32 activations per lane and token next to the two weight register sets do not fit
+      // the 256 registers of two workgroups per CU without scratch; its callers run 3 and 4 tokens as two passes of the 2-token build)
+      if constexpr (WK == WK_I8W) { llx_set_error("llx_gemv_i8: no 4-token build of the weight-only kind"); return LLX_ERR_UNSUPPORTED; }
+      else return launch_gemv_m<4, RPW, WK>(a, epi, grid, lds, stream);
   }
 }
 
@@ -303,32 +457,36 @@ static int launch_gemv_m(const GemvArgs& a, int epi, int grid, size_t lds, hipSt
 // rest -> v cache, at input_pos[m] (device int64), caches through (head, position) strides | 3 (gate|up = W0|W1, N = 2 n_0):
 // out [M, N/2] = silu(gate) * up.  LoRA (nullable bext_s [n_s, rank_s], t [M, sum rank] bf16 = x . A^T, offsets t_off_s, scale):
 // out += scale * t_s . bext_s[row].
-extern "C" int llx_gemv_bf16(const void* w0, int64_t ldw0, int64_t n0, const void* w1, int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2,
+// the two entry points below: fn = the caller's name for messages, wk = weight kind, ws_s = per-row scales of W_s (int8 kinds)
+static int gemv_run(const char* fn, int wk, const void* ws0, const void* ws1, const void* ws2, const void* w0, int64_t ldw0, int64_t n0, const void* w1, int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2,
                              int64_t n2, const void* x, int64_t ldx, int64_t M, int64_t K, const void* norm_w, float eps, int epilogue,
                              void* out, int64_t ldo, const void* res, int64_t ldr, const float* rope, int64_t n_q, int64_t n_k, void* k_cache,
                              void* v_cache, int64_t c_sh, int64_t c_ss, const int64_t* input_pos, const void* bext0, const void* bext1,
                              const void* bext2, int64_t rank0, int64_t rank1, int64_t rank2, const void* t, int64_t ldt, float lora_scale,
-                             hipStream_t stream) {
-  LLX_REQUIRE(w0 && x && out, "llx_gemv_bf16: null pointer");
-  LLX_REQUIRE(M >= 1 && M <= 4, "llx_gemv_bf16: M=%lld outside 1..4 (larger row counts run the MFMA GEMM)", (long long)M);
-  LLX_REQUIRE(K > 0 && K % 8 == 0 && K <= 32768, "llx_gemv_bf16: K=%lld must be a multiple of 8 and at most 32768", (long long)K);
-  LLX_REQUIRE(n0 > 0 && n1 >= 0 && n2 >= 0 && (w1 || n1 == 0) && (w2 || n2 == 0), "llx_gemv_bf16: bad segment sizes");
-  LLX_REQUIRE((n1 == 0 || n0 % 4 == 0) && (n2 == 0 || n1 % 4 == 0), "llx_gemv_bf16: inner segment sizes must be multiples of 4");
-  LLX_REQUIRE(ldw0 % 8 == 0 && ldw1 % 8 == 0 && ldw2 % 8 == 0 && ldx % 8 == 0, "llx_gemv_bf16: row strides must be multiples of 8 elements");
-  LLX_REQUIRE(((uintptr_t)w0 | (uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)x | (uintptr_t)norm_w) % 16 == 0, "llx_gemv_bf16: pointers must be 16-byte aligned");
-  LLX_REQUIRE(epilogue >= GV_NONE && epilogue <= GV_SWIGLU, "llx_gemv_bf16: unknown epilogue %d", epilogue);
+                    hipStream_t stream) {
+  LLX_REQUIRE(w0 && x && out, "%s: null pointer", fn);
+  LLX_REQUIRE(M >= 1 && M <= 4, "%s: M=%lld outside 1..4 (larger row counts run the MFMA GEMM)", fn, (long long)M);
+  const int wa = wk == WK_BF16 ? 8 : 16;  // weight elements per 16-byte lane load: K and the weight row strides are multiples of it
+  LLX_REQUIRE(K > 0 && K % wa == 0 && K <= 32768, "%s: K=%lld must be a multiple of %d and at most 32768", fn, (long long)K, wa);
+  LLX_REQUIRE(n0 > 0 && n1 >= 0 && n2 >= 0 && (w1 || n1 == 0) && (w2 || n2 == 0), "%s: bad segment sizes", fn);
+  LLX_REQUIRE((n1 == 0 || n0 % 4 == 0) && (n2 == 0 || n1 % 4 == 0), "%s: inner segment sizes must be multiples of 4", fn);
+  LLX_REQUIRE(ldw0 % wa == 0 && ldw1 % wa == 0 && ldw2 % wa == 0 && ldx % 8 == 0, "%s: row strides must be multiples of 16 bytes", fn);
+  LLX_REQUIRE(wk == WK_BF16 || (ws0 && (ws1 || n1 == 0) && (ws2 || n2 == 0)), "%s: null scale (every int8 weight needs its per-row scales)", fn);
+  LLX_REQUIRE(((uintptr_t)ws0 | (uintptr_t)ws1 | (uintptr_t)ws2) % 2 == 0, "%s: scale pointers must be 2-byte aligned", fn);
+  LLX_REQUIRE(((uintptr_t)w0 | (uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)x | (uintptr_t)norm_w) % 16 == 0, "%s: pointers must be 16-byte aligned", fn);
+  LLX_REQUIRE(epilogue >= GV_NONE && epilogue <= GV_SWIGLU, "%s: unknown epilogue %d", fn, epilogue);
   const int64_t N = n0 + n1 + n2;
-  LLX_REQUIRE(N < (1 << 30), "llx_gemv_bf16: too many rows");
-  LLX_REQUIRE(epilogue != GV_RESIDUAL || res, "llx_gemv_bf16: residual missing");
-  LLX_REQUIRE(epilogue != GV_SWIGLU || (n0 == n1 && n2 == 0 && w1), "llx_gemv_bf16: the SwiGLU epilogue takes gate and up weights of equal size");
+  LLX_REQUIRE(N < (1 << 30), "%s: too many rows", fn);
+  LLX_REQUIRE(epilogue != GV_RESIDUAL || res, "%s: residual missing", fn);
+  LLX_REQUIRE(epilogue != GV_SWIGLU || (n0 == n1 && n2 == 0 && w1), "%s: the SwiGLU epilogue takes gate and up weights of equal size", fn);
   LLX_REQUIRE(epilogue != GV_QKV || (rope && k_cache && v_cache && input_pos && n_q % HD == 0 && n_k % HD == 0 && (N - n_q - n_k) % HD == 0 &&
                                      n_q + n_k <= N && (uintptr_t)rope % 8 == 0 && ((uintptr_t)out | (uintptr_t)k_cache | (uintptr_t)v_cache) % 8 == 0 &&
                                      ldo % 4 == 0 && c_sh % 4 == 0 && c_ss % 4 == 0),
-              "llx_gemv_bf16: bad q|k|v epilogue arguments");
+              "%s: bad q|k|v epilogue arguments", fn);
   const bool lora = bext0 || bext1 || bext2;
   LLX_REQUIRE(!lora || (t && ldt % 8 == 0 && (uintptr_t)t % 16 == 0 && rank0 % 8 == 0 && rank1 % 8 == 0 && rank2 % 8 == 0 && rank0 <= 512 && rank1 <= 512 &&
                         rank2 <= 512 && ((uintptr_t)bext0 | (uintptr_t)bext1 | (uintptr_t)bext2) % 16 == 0),
-              "llx_gemv_bf16: bad LoRA operands (ranks must be multiples of 8, at most 512)");
+              "%s: bad LoRA operands (ranks must be multiples of 8, at most 512)", fn);
   GemvArgs a;
   a.W[0] = (const bf16_t*)w0; a.W[1] = (const bf16_t*)(w1 ? w1 : w0); a.W[2] = (const bf16_t*)(w2 ? w2 : w0);
   a.ldw[0] = ldw0; a.ldw[1] = w1 ? ldw1 : ldw0; a.ldw[2] = w2 ? ldw2 : ldw0;
@@ -344,19 +502,25 @@ extern "C" int llx_gemv_bf16(const void* w0, int64_t ldw0, int64_t n0, const voi
   a.rank[0] = (int)rank0; a.rank[1] = (int)rank1; a.rank[2] = (int)rank2;
   a.t_off[0] = 0; a.t_off[1] = (int)rank0; a.t_off[2] = (int)(rank0 + rank1);
   a.t = (const bf16_t*)t; a.ldt = ldt; a.lora_scale = lora_scale;
+  a.wscale[0] = (const bf16_t*)ws0; a.wscale[1] = (const bf16_t*)(ws1 ? ws1 : ws0); a.wscale[2] = (const bf16_t*)(ws2 ? ws2 : ws0);
   if (n1 == 0 && lora) { a.bext[1] = a.bext[2] = a.bext[0]; a.ldb[1] = a.ldb[2] = a.ldb[0]; a.rank[1] = a.rank[2] = a.rank[0]; a.t_off[1] = a.t_off[2] = 0; }
   // rows per wave: 2 (steps of 2048 elements per row: half the dependent steps of the 4-row form on every product of the decode step and
   // twice the waves where N <= 4096 would fill only half of the 2048 slots: 3.51 -> 3.39 ms per token; one row per wave: 3.43);
   // LLX_GEMV_RPW=4: the 4-row form
   static const int rpw_knob = [] { const char* e = getenv("LLX_GEMV_RPW"); return e ? atoi(e) : 0; }();
-  const int rpw = rpw_knob == 4 ? 4 : 2;
+  // int8 rows: 2 as well (steps of 4 pieces = 4096 elements per row, so a K = 4096 row is one step and K = 14336 pads its last step
+  // by two pieces; the 4-row form with steps of 2048 elements, which tile both K exactly, was measured next to it on the 8B decode
+  // step: 2.64 / 2.81 ms per token (weight-only / dynamic, context 4096) against 2.54 / 2.71 with 2 rows - the wider grid of the
+  // N = 4096 and 6144 products decides, as for bf16).  Only the 2-row form is built.
+  const int rpw = wk == WK_BF16 ? (rpw_knob == 4 ? 4 : 2) : 2;
   const int64_t groups = epilogue == GV_SWIGLU ? (N / 2 + rpw / 2 - 1) / (rpw / 2) : (N + rpw - 1) / rpw;
   // the wave count is trimmed so that every wave gets the same number of row groups where possible
   constexpr int wave_cap = 2048;
   const int64_t per_wave = cdiv64(groups, wave_cap);
   const int grid = (int)cdiv64(cdiv64(groups, per_wave), 4);
-  const int64_t kstep = 512 * (8 / rpw);
-  const int64_t Kp = cdiv64(K, kstep) * kstep;
+  const int64_t kstep = 64 * wa * (8 / rpw);
+  const int64_t xb = wk == WK_I8D ? 1 : 2;  // bytes per staged activation element
+  const int64_t Kp = wk == WK_BF16 ? cdiv64(K, kstep) * kstep : (cdiv64(K, 64 * wa) + 1) * 64 * wa;  // the kernel's LDS row length
   // the build for m rows stages MT = 1 | 2 | 4 rows of x in LDS; above 64 KiB the rows go in pairs (two passes over the weights)
   auto run = [&](int m0, int mc) -> int {
     GemvArgs b = a;
@@ -368,26 +532,49 @@ extern "C" int llx_gemv_bf16(const void* w0, int64_t ldw0, int64_t n0, const voi
     if (a.pos) b.pos = a.pos + m0;
     if (a.t) b.t = a.t + (int64_t)m0 * a.ldt;
     const int MT = mc == 1 ? 1 : (mc == 2 ? 2 : 4);
-    const size_t lds = (size_t)MT * Kp * 2 + 64;
-    if (rpw == 2) {
-      switch (MT) {
-        case 1: return launch_gemv_m<1, 2>(b, epilogue, grid, lds, stream);
-        case 2: return launch_gemv_m<2, 2>(b, epilogue, grid, lds, stream);
-        default: return launch_gemv_m<4, 2>(b, epilogue, grid, lds, stream);
-      }
-    }
-    switch (MT) {
-      case 1: return launch_gemv_m<1, 4>(b, epilogue, grid, lds, stream);
-      case 2: return launch_gemv_m<2, 4>(b, epilogue, grid, lds, stream);
-      default: return launch_gemv_m<4, 4>(b, epilogue, grid, lds, stream);
-    }
+    const size_t lds = (size_t)MT * Kp * xb + 64;
+    if (wk == WK_I8W) return launch_gemv_mt<2, WK_I8W>(b, MT, epilogue, grid, lds, stream);
+    if (wk == WK_I8D) return launch_gemv_mt<2, WK_I8D>(b, MT, epilogue, grid, lds, stream);
+    return rpw == 2 ? launch_gemv_mt<2, WK_BF16>(b, MT, epilogue, grid, lds, stream) : launch_gemv_mt<4, WK_BF16>(b, MT, epilogue, grid, lds, stream);
   };
-  if (M > 2 && 4 * Kp * 2 + 64 > 64 * 1024) {
-    const int rc = run(0, 2);
-    return rc != LLX_OK ? rc : run(2, (int)M - 2);
+  // tokens per pass: all of them where their LDS stage fits, else pairs, else one (each pass streams the weights again); the
+  // weight-only int8 kind has no 4-token build
+  auto fits = [&](int64_t mt) { return mt * Kp * xb + 64 <= 64 * 1024; };
+  int per_pass = M > 2 ? 4 : (int)M;
+  if (per_pass == 4 && (wk == WK_I8W || !fits(4))) per_pass = 2;
+  if (per_pass == 2 && !fits(2)) per_pass = 1;
+  LLX_REQUIRE(fits(per_pass), "%s: K too large for the LDS stage", fn);
+  for (int m0 = 0; m0 < (int)M; m0 += per_pass) {
+    const int rc = run(m0, (int)M - m0 < per_pass ? (int)M - m0 : per_pass);
+    if (rc != LLX_OK) return rc;
   }
-  LLX_REQUIRE((M > 2 ? 4 : M) * Kp * 2 + 64 <= 64 * 1024, "llx_gemv_bf16: M * K too large for the LDS stage");
-  return run(0, (int)M);
+  return LLX_OK;
+}
+
+extern "C" int llx_gemv_bf16(const void* w0, int64_t ldw0, int64_t n0, const void* w1, int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2,
+                             int64_t n2, const void* x, int64_t ldx, int64_t M, int64_t K, const void* norm_w, float eps, int epilogue,
+                             void* out, int64_t ldo, const void* res, int64_t ldr, const float* rope, int64_t n_q, int64_t n_k, void* k_cache,
+                             void* v_cache, int64_t c_sh, int64_t c_ss, const int64_t* input_pos, const void* bext0, const void* bext1,
+                             const void* bext2, int64_t rank0, int64_t rank1, int64_t rank2, const void* t, int64_t ldt, float lora_scale,
+                             hipStream_t stream) {
+  return gemv_run("llx_gemv_bf16", WK_BF16, nullptr, nullptr, nullptr, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue, out, ldo, res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sh,
+                  c_ss, input_pos, bext0, bext1, bext2, rank0, rank1, rank2, t, ldt, lora_scale, stream);
+}
+
+// The same product on int8 weight rows (subclasses/int8.py:106-121): W_s [n_s, K] int8 row-major (ldw_s in bytes, multiples of 16),
+// scale_s [n_s] bf16 per-row scales, K % 16 == 0.  dynamic = 0 (weight-only, :118): out = bf16(bf16(x . W^T) * scale), fp32 FMA on
+// the sign-extended bytes.  dynamic = 1 (:112-113, int8_mm.py:93-118): every (normalised) row of x is quantised as
+// llx_quantize_int8_rowwise does, int32 dot products, out = bf16(((float)acc * x_scale[m]) * scale[row]) - bit-exact with the
+// reference when no norm is fused.  Epilogues, norm and the q|k|v / SwiGLU neighbours as llx_gemv_bf16; LoRA (t from llx_gemv_bf16 on
+// the un-quantised x): out = bf16(out + lora_scale * t_s . bext_s[row]).
+extern "C" int llx_gemv_i8(const void* w0, int64_t ldw0, int64_t n0, const void* w1, int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2,
+                           int64_t n2, const void* x, int64_t ldx, int64_t M, int64_t K, const void* norm_w, float eps, int epilogue,
+                           void* out, int64_t ldo, const void* res, int64_t ldr, const float* rope, int64_t n_q, int64_t n_k, void* k_cache,
+                           void* v_cache, int64_t c_sh, int64_t c_ss, const int64_t* input_pos, const void* bext0, const void* bext1,
+                           const void* bext2, int64_t rank0, int64_t rank1, int64_t rank2, const void* t, int64_t ldt, float lora_scale,
+                           const void* scale0, const void* scale1, const void* scale2, int dynamic, hipStream_t stream) {
+  return gemv_run("llx_gemv_i8", dynamic ? WK_I8D : WK_I8W, scale0, scale1, scale2, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue, out, ldo, res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sh,
+                  c_ss, input_pos, bext0, bext1, bext2, rank0, rank1, rank2, t, ldt, lora_scale, stream);
 }
 
 // ------------------------------------------------------------------------------------------------- mask extent / cache scatter

@@ -16,16 +16,14 @@ __global__ __launch_bounds__(256) void quant_rowwise_kernel(const T* __restrict_
   float amax = 0.f;
   if constexpr (sizeof(T) == 2) {
     for (int c = threadIdx.x * 8; c < cols; c += 256 * 8) {
-      const u32x4_t v = *reinterpret_cast<const u32x4_t*>(xr + c);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) amax = fmaxf(amax, fmaxf(fabsf(bflo(v[e])), fabsf(bfhi(v[e]))));
+      amax = q8_absmax8(*reinterpret_cast<const u32x4_t*>(xr + c), amax);
     }
   } else {
     for (int c = threadIdx.x; c < cols; c += 256) amax = fmaxf(amax, fabsf(ld_f<T>(xr + c)));
   }
   amax = block_max(amax, red);
-  const float scale = amax / 127.0f;
-  const float div = fmaxf(scale, 1e-12f);
+  const float scale = q8_scale(amax);
+  const float div = q8_divisor(scale);
   if (threadIdx.x == 0) {
     if constexpr (sizeof(T) == 2) scale_out[row] = f2bf(scale);
     else scale_out[row] = scale;
@@ -33,14 +31,7 @@ __global__ __launch_bounds__(256) void quant_rowwise_kernel(const T* __restrict_
   int8_t* qr = q + row * ldq;
   if constexpr (sizeof(T) == 2) {
     for (int c = threadIdx.x * 8; c < cols; c += 256 * 8) {
-      const u32x4_t v = *reinterpret_cast<const u32x4_t*>(xr + c);
-      u32x2_t o = {0u, 0u};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int a = (int)rintf(bflo(v[e]) / div), b = (int)rintf(bfhi(v[e]) / div);
-        o[e >> 1] |= ((uint32_t)(a & 0xff) | ((uint32_t)(b & 0xff) << 8)) << ((e & 1) * 16);
-      }
-      *reinterpret_cast<u32x2_t*>(qr + c) = o;
+      *reinterpret_cast<u32x2_t*>(qr + c) = q8_quant8(*reinterpret_cast<const u32x4_t*>(xr + c), div);
     }
   } else {
     for (int c = threadIdx.x; c < cols; c += 256) qr[c] = (int8_t)(int)rintf(ld_f<T>(xr + c) / div);

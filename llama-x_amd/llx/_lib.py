@@ -32,6 +32,8 @@ SIGNATURES: dict[str, tuple] = {
     "llx_attn_dense_fwd": (c_int, [_P, _L, _L, _L, _P, _L, _L, _L, _P, _L, _L, _L, _P, _L, _L, _L, _P, _L, _L, _L, _L, _L, _L, _L, _L, _L, _F, _P]),
     "llx_gemv_bf16": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _F, _I, _P, _L, _P, _L, _P, _L, _L, _P, _P, _L, _L, _P,
                               _P, _P, _P, _L, _L, _L, _P, _L, _F, _P]),
+    "llx_gemv_i8": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _F, _I, _P, _L, _P, _L, _P, _L, _L, _P, _P, _L, _L, _P,
+                            _P, _P, _P, _L, _L, _L, _P, _L, _F, _P, _P, _P, _I, _P]),
     "llx_mask_extent": (c_int, [_P, _L, _L, _L, _P, _P]),
     "llx_kv_scatter": (c_int, [_P, _P, _L, _L, _L, _P, _P, _L, _L, _L, _P, _L, _L, _L, _L, _L, _P]),
     "llx_attn_decode_workspace_bytes": (c_int64, [_L, _L, _L, _L]),

@@ -2,7 +2,9 @@
 
 Reference semantics: the cached branch of Attention.forward (modelling/llama.py:126-127,135-137) inside TransformerLayer.forward
 (:163-174) and the head of Llama.forward (:216) - same values as the generic inference path of modelling/llama.py::_run_dense, which
-stays for every call this path does not take (more than 4 tokens, more than 16 query rows per kv head, biases, int8 / DoRA linears).
+stays for every call this path does not take (more than 4 tokens, more than 16 query rows per kv head, biases, DoRA linears).
+Int8LinearWeight linears (weight-only or dynamic, subclasses/int8.py:106-121) stream their int8 rows (llx_gemv_i8): no bf16 image of
+the matrix is built or read.
 
 Per layer (M <= 4 tokens, batch 1 as KVCache is built, :189-192):
     q            = gemv([wq; wk; wv], rmsnorm(x))  + RoPE on q, k + k, v scattered into the caches        1 launch
@@ -26,14 +28,31 @@ BF16 = torch.bfloat16
 MAX_TOKENS = 4
 
 
-def _plain(m: nn.Linear) -> bool:
-    """A linear this path streams: bf16 weight, no bias, optionally a LoRA adapter (rank a multiple of 8)."""
+KIND_BF16, KIND_I8W, KIND_I8D = "bf16", "int8-weight-only", "int8-dynamic"
+
+
+def _plain(m: nn.Linear) -> Optional[str]:
+    """The kind of a linear this path streams, or None: bf16 weight or Int8LinearWeight (bf16 scale; weight-only or dynamic), no bias,
+    optionally a LoRA adapter (rank a multiple of 8)."""
     from subclasses.int8 import Int8LinearWeight
 
-    if m.bias is not None or isinstance(m.weight, Int8LinearWeight) or m.weight.dtype is not BF16 or getattr(m, "m", None) is not None:
-        return False
+    if m.bias is not None or m.weight.dtype is not BF16 or getattr(m, "m", None) is not None:
+        return None
     rank = int(getattr(m, "rank", 0) or 0)
-    return rank == 0 or (rank % 8 == 0 and m.lora_a.dtype is BF16)
+    if not (rank == 0 or (rank % 8 == 0 and m.lora_a.dtype is BF16)):
+        return None
+    if isinstance(m.weight, Int8LinearWeight):
+        if m.weight.scale.dtype is not BF16 or m.in_features % 16 != 0:
+            return None
+        return KIND_I8D if m.weight.dynamic_int8_act else KIND_I8W
+    return KIND_BF16
+
+
+def _w(mods) -> dict:
+    """The weight operands of one gemv call: (ws, wscale, dynamic) of a group of linears of one kind."""
+    if _plain(mods[0]) == KIND_BF16:
+        return dict(ws=[m.weight.detach() for m in mods])
+    return dict(ws=[m.weight.int_data for m in mods], wscale=[m.weight.scale for m in mods], dynamic=bool(mods[0].weight.dynamic_int8_act))
 
 
 def layer_ok(layer, x: Tensor, mask: Optional[Tensor]) -> bool:
@@ -47,11 +66,11 @@ def layer_ok(layer, x: Tensor, mask: Optional[Tensor]) -> bool:
         return False
     ff = layer.feed_forward
     lins = (att.wq, att.wk, att.wv, att.wo, ff.w1, ff.w3, ff.w2)
-    if not all(_plain(m) for m in lins):
+    if not all(_plain(m) is not None for m in lins):
         return False
-    for grp in ((att.wq, att.wk, att.wv), (ff.w1, ff.w3)):  # one t vector and one scale per fused group
+    for grp in ((att.wq, att.wk, att.wv), (ff.w1, ff.w3)):  # one t vector, one scale and one weight kind per fused group
         ranks = {int(getattr(m, "rank", 0) or 0) > 0 for m in grp}
-        if len(ranks) != 1 or len({float(getattr(m, "scale", 1.0)) for m in grp}) != 1:
+        if len(ranks) != 1 or len({float(getattr(m, "scale", 1.0)) for m in grp}) != 1 or len({_plain(m) for m in grp}) != 1:
             return False
     return att.wq.out_features % 4 == 0 and att.wk.out_features % 4 == 0 and ff.w1.out_features == ff.w3.out_features
 
@@ -78,19 +97,19 @@ def layer_forward(layer, x: Tensor, rope: Tensor, mask: Tensor, input_pos: Tenso
     qkv_mods = (att.wq, att.wk, att.wv)
     cache = att.kv_cache
     pos = input_pos.to(torch.int64).contiguous()
-    q = K.gemv([m.weight.detach() for m in qkv_mods], x2, norm=n1, epilogue=K.GV_QKV,
+    q = K.gemv(x=x2, norm=n1, epilogue=K.GV_QKV, **_w(qkv_mods),
                qkv=(rope, H * hd, KVH * hd, cache.k_cache, cache.v_cache, pos), lora=_lora(qkv_mods, x2, n1))
     o = K.attn_decode(q.view(1, M, H, hd).transpose(1, 2), cache.k_cache, cache.v_cache, mask, mask_extent(mask))  # [1, M, H*hd]
     o2 = o.view(M, H * hd)
-    x1 = K.gemv([att.wo.weight.detach()], o2, epilogue=K.GV_RESIDUAL, res=x2, lora=_lora((att.wo,), o2, None))
+    x1 = K.gemv(x=o2, epilogue=K.GV_RESIDUAL, res=x2, lora=_lora((att.wo,), o2, None), **_w((att.wo,)))
     n2 = (layer.ffn_norm.weight.detach(), layer.ffn_norm.eps)
-    h = K.gemv([ff.w1.weight.detach(), ff.w3.weight.detach()], x1, norm=n2, epilogue=K.GV_SWIGLU, lora=_lora((ff.w1, ff.w3), x1, n2))
-    x3 = K.gemv([ff.w2.weight.detach()], h, epilogue=K.GV_RESIDUAL, res=x1, lora=_lora((ff.w2,), h, None))
+    h = K.gemv(x=x1, norm=n2, epilogue=K.GV_SWIGLU, lora=_lora((ff.w1, ff.w3), x1, n2), **_w((ff.w1, ff.w3)))
+    x3 = K.gemv(x=h, epilogue=K.GV_RESIDUAL, res=x1, lora=_lora((ff.w2,), h, None), **_w((ff.w2,)))
     return x3.view(1, M, D)
 
 
 def head_ok(model, x: Tensor) -> bool:
-    return (x.dim() == 3 and x.shape[0] == 1 and x.shape[1] <= MAX_TOKENS and x.is_cuda and x.dtype is BF16 and _plain(model.output)
+    return (x.dim() == 3 and x.shape[0] == 1 and x.shape[1] <= MAX_TOKENS and x.is_cuda and x.dtype is BF16 and _plain(model.output) is not None
             and x.shape[2] % 8 == 0)
 
 
@@ -99,5 +118,5 @@ def head_forward(model, x: Tensor) -> Tensor:
     M, D = x.shape[1], x.shape[2]
     x2 = x.reshape(M, D)
     nw = (model.norm.weight.detach(), model.norm.eps)
-    logits = K.gemv([model.output.weight.detach()], x2, norm=nw, lora=_lora((model.output,), x2, nw))
+    logits = K.gemv(x=x2, norm=nw, lora=_lora((model.output,), x2, nw), **_w((model.output,)))
     return logits.view(1, M, -1)

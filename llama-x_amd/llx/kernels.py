@@ -674,11 +674,26 @@ GV_NONE, GV_RESIDUAL, GV_QKV, GV_SWIGLU = 0, 1, 2, 3
 
 
 def gemv(ws: Sequence[Tensor], x: Tensor, *, norm: Optional[tuple[Tensor, float]] = None, epilogue: int = GV_NONE, out: Optional[Tensor] = None,
-         res: Optional[Tensor] = None, qkv: Optional[tuple] = None, lora: Optional[tuple] = None) -> Tensor:
+         res: Optional[Tensor] = None, qkv: Optional[tuple] = None, lora: Optional[tuple] = None, wscale: Optional[Sequence[Tensor]] = None,
+         dynamic: bool = False) -> Tensor:
     """out = epilogue([rmsnorm(x) | x] @ cat(ws)^T) for M = x.shape[0] <= 4 rows: every CU streams weight rows (llx_gemv_bf16).
     ws: 1-3 weights [n_s, K]; norm = (weight, eps); res [M, N] for GV_RESIDUAL; qkv = (rope_table, n_q, n_k, k_cache, v_cache, input_pos)
-    for GV_QKV (caches [1, KVH, Smax, 128]; returns q [M, n_q]); GV_SWIGLU returns h [M, n_0]; lora = (b factors, t [M, sum r], scale)."""
-    _chk_bf16(x, *ws)
+    for GV_QKV (caches [1, KVH, Smax, 128]; returns q [M, n_q]); GV_SWIGLU returns h [M, n_0]; lora = (b factors, t [M, sum r], scale).
+    int8 ws (the int_data of Int8LinearWeights, all members of the call) with wscale = their bf16 per-row scales run llx_gemv_i8:
+    weight-only arithmetic, or with dynamic=True the rows of x quantised on chip and integer dot products (subclasses/int8.py:106-121)."""
+    i8 = [w.dtype is torch.int8 for w in ws]
+    if any(i8):
+        if not all(i8):
+            raise L.LlxError("gemv: bf16 and int8 weights in one call (all members of a fused group must be of one kind)")
+        if x.shape[1] % 16 != 0:
+            raise L.LlxError(f"gemv: K={x.shape[1]} must be a multiple of 16 for int8 weights")
+        assert wscale is not None and len(wscale) == len(ws), "int8 weights need their per-row scales"
+        assert all(sc.shape == (w.shape[0],) and sc.is_contiguous() for sc, w in zip(wscale, ws))
+        _chk_bf16(x, *wscale)
+        L.require_cuda(*ws)
+    else:
+        assert wscale is None and not dynamic, "wscale / dynamic belong to int8 weights"
+        _chk_bf16(x, *ws)
     M, Kd = x.shape
     assert 1 <= len(ws) <= 3 and all(w.dim() == 2 and w.shape[1] == Kd and w.stride(1) == 1 for w in ws) and x.stride(1) == 1
     ns = [w.shape[0] for w in ws] + [0] * (3 - len(ws))
@@ -709,6 +724,13 @@ def gemv(ws: Sequence[Tensor], x: Tensor, *, norm: Optional[tuple[Tensor, float]
             bs[i], ranks[i] = b, b.shape[1]
         assert t.shape[1] == sum(ranks)
         ldt = t.stride(0)
+    if any(i8):
+        sp = [L.ptr(sc) for sc in wscale] + [None] * (3 - len(ws))
+        L.check(_lib().llx_gemv_i8(wp[0], lw[0], ns[0], wp[1], lw[1], ns[1], wp[2], lw[2], ns[2], L.ptr(x), x.stride(0), M, Kd, L.ptr(nw), eps, epilogue,
+                                   L.ptr(out), out.stride(0), L.ptr(res), res.stride(0) if res is not None else 0, L.ptr(rope), n_q, n_k, L.ptr(kc), L.ptr(vc),
+                                   c_sh, c_ss, L.ptr(pos), L.ptr(bs[0]), L.ptr(bs[1]), L.ptr(bs[2]), ranks[0], ranks[1], ranks[2], L.ptr(t), ldt, float(lscale),
+                                   sp[0], sp[1], sp[2], int(bool(dynamic)), L.stream()), "llx_gemv_i8")
+        return out
     L.check(_lib().llx_gemv_bf16(wp[0], lw[0], ns[0], wp[1], lw[1], ns[1], wp[2], lw[2], ns[2], L.ptr(x), x.stride(0), M, Kd, L.ptr(nw), eps, epilogue,
                                  L.ptr(out), out.stride(0), L.ptr(res), res.stride(0) if res is not None else 0, L.ptr(rope), n_q, n_k, L.ptr(kc), L.ptr(vc),
                                  c_sh, c_ss, L.ptr(pos), L.ptr(bs[0]), L.ptr(bs[1]), L.ptr(bs[2]), ranks[0], ranks[1], ranks[2], L.ptr(t), ldt, float(lscale),
