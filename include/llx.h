@@ -136,6 +136,20 @@ int llx_attn_dense_fwd(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, 
                        const void* mask, int64_t m_sb, int64_t m_sh, int64_t m_sq, int64_t B, int64_t H, int64_t KVH, int64_t Sq, int64_t Skv,
                        int64_t head_dim, float scale, llx_stream_t s);
 
+/* ---- the same SDPA call (modelling/llama.py:126-127,135-137 with the mask of :194,:205) for a mask broadcast over heads, on the MFMA
+ *      tile loop of llx_attn_fwd: KV-cache prefill and explicit bool masks.  Sq query rows against Skv keys; the mask is the only rule.
+ *      q / o are ROWS [B, Sq, H*128] (batch / position strides, head h at h*128; o is what wo reads), k / v [B, KVH, Skv, 128] through
+ *      (batch, head, position) strides - the cache buffers or the views of a fused q|k|v row buffer.  mask bool / uint8 [B | 1, Sq, Skv],
+ *      last dim dense, m_sq / m_sb in bytes (m_sb = 0 broadcasts), Skv >= 4.  flags: llx_attn_mask_flags_bytes(B, Sq, Skv) bytes filled
+ *      by llx_attn_mask_tile_flags (128-row x 64-key tile classes: 0 skipped, 1 tested per byte, 2 unmasked).  lse nullable (fp32
+ *      [B,H,Sq], log2 units).  A row without any allowed key comes out NaN, as SDPA's.  Forward only. ----------------------------- */
+int64_t llx_attn_mask_flags_bytes(int64_t B, int64_t Sq, int64_t Skv);
+int llx_attn_mask_tile_flags(const void* mask, int64_t m_sb, int64_t m_sq, void* flags, int64_t B, int64_t Sq, int64_t Skv, llx_stream_t s);
+int llx_attn_mask_fwd(const void* q, int64_t q_sb, int64_t q_ss, const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, const void* v,
+                      int64_t v_sb, int64_t v_sh, int64_t v_ss, void* o, int64_t o_sb, int64_t o_ss, float* lse /* nullable */,
+                      const void* mask, int64_t m_sb, int64_t m_sq, const void* flags, int64_t B, int64_t Sq, int64_t Skv, int64_t H,
+                      int64_t KVH, int64_t head_dim, float scale, llx_stream_t s);
+
 /* ---- decode path: a few query tokens (M <= 4) against the KV cache - modelling/llama.py:76-90 (KVCache), :126-127,:135-137 (cached
  *      K/V through SDPA with the row-gathered causal mask), :189-194,:205-207 (Llama.forward with input_pos).  Every linear is a
  *      weight stream: all CUs read weight rows once (llx_gemv_bf16), the call sites' neighbours ride in its prologue / epilogue. ---- */

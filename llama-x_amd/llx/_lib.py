@@ -30,6 +30,9 @@ SIGNATURES: dict[str, tuple] = {
     "llx_attn_tile_flags": (c_int, [_P, _P, _P, _L, _L, _P]),
     "llx_attn_fwd": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _P, _P, _P, _L, _L, _L, _L, _L, _F, _P]),
     "llx_attn_dense_fwd": (c_int, [_P, _L, _L, _L, _P, _L, _L, _L, _P, _L, _L, _L, _P, _L, _L, _L, _P, _L, _L, _L, _L, _L, _L, _L, _L, _L, _F, _P]),
+    "llx_attn_mask_flags_bytes": (c_int64, [_L, _L, _L]),
+    "llx_attn_mask_tile_flags": (c_int, [_P, _L, _L, _P, _L, _L, _L, _P]),
+    "llx_attn_mask_fwd": (c_int, [_P, _L, _L, _P, _L, _L, _L, _P, _L, _L, _L, _P, _L, _L, _P, _P, _L, _L, _P, _L, _L, _L, _L, _L, _L, _F, _P]),
     "llx_gemv_bf16": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _F, _I, _P, _L, _P, _L, _P, _L, _L, _P, _P, _L, _L, _P,
                               _P, _P, _P, _L, _L, _L, _P, _L, _F, _P]),
     "llx_gemv_i8": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _F, _I, _P, _L, _P, _L, _P, _L, _L, _P, _P, _L, _L, _P,

@@ -669,6 +669,71 @@ def attn_dense_fwd(q: Tensor, k: Tensor, v: Tensor, mask: Tensor) -> Tensor:
     return o
 
 
+def _mask_4d(mask: Tensor, B: int, Sq: int, Skv: int) -> Optional[Tensor]:
+    """The mask as [B | 1, 1, Sq, Skv] if it is broadcast over heads, else None (per-head masks)."""
+    m = mask
+    while m.dim() < 4:
+        m = m.unsqueeze(0)
+    return m if m.dim() == 4 and m.shape[1] == 1 and m.shape[0] in (1, B) and m.shape[2:] == (Sq, Skv) else None
+
+
+def _mask_rows(mask: Tensor, B: int, Sq: int, Skv: int) -> Optional[Tensor]:
+    """The bool mask as [B | 1, Sq, Skv] with a dense last dim if it is broadcast over heads, else None."""
+    m = _mask_4d(mask, B, Sq, Skv)
+    if m is None:
+        return None
+    m = m[:, 0]
+    return m if m.stride(2) == 1 and m.stride(1) >= Skv else m.contiguous()
+
+
+def attn_mask_routable(mask: Tensor, B: int, Sq: int, Skv: int) -> bool:
+    """Whether attn_mask_fwd takes this mask: bool, broadcast over heads, at least 4 keys (its mask reads are 4 bytes wide)."""
+    return mask.dtype is torch.bool and Skv >= 4 and _mask_4d(mask, B, Sq, Skv) is not None
+
+
+def attn_mask_flags(mask: Tensor, B: int) -> Tensor:
+    """Tile classes (uint8 [B, ceil(Sq/128), ceil(Skv/64)]: 0 skip, 1 partly masked, 2 unmasked) of a bool mask broadcastable to
+    [B, 1, Sq, Skv]: one pass over the mask bytes."""
+    L.require_cuda(mask)
+    Sq, Skv = mask.shape[-2:]
+    m = _mask_rows(mask, B, Sq, Skv)
+    assert m is not None and mask.dtype is torch.bool, "mask must be bool and broadcast over heads"
+    fl = torch.empty(_lib().llx_attn_mask_flags_bytes(B, Sq, Skv), device=mask.device, dtype=torch.uint8)
+    L.check(_lib().llx_attn_mask_tile_flags(L.ptr(m), m.stride(0) if m.shape[0] != 1 else 0, m.stride(1), L.ptr(fl), B, Sq, Skv, L.stream()),
+            "llx_attn_mask_tile_flags")
+    return fl
+
+
+def attn_mask_fwd(q: Tensor, k: Tensor, v: Tensor, mask: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """Inference attention with an explicit bool mask broadcast over heads, on the MFMA tile loop of the training forward (KV-cache
+    prefill): q [B,H,Sq,128] as the transposed view of a row buffer (head stride 128), k/v [B,KVH,Skv,128] with any head / position
+    strides (the caches, or views of the q|k|v rows), mask broadcastable to [B,1,Sq,Skv] -> o [B,Sq,H*128], the rows `wo` reads.
+    The tile classes are computed once per mask tensor (cached on it: every layer of a call shares them).  No host synchronisation."""
+    from . import ops  # (ops imports this module)
+
+    _chk_bf16(q, k, v)
+    L.require_cuda(mask)
+    B, H, Sq, hd = q.shape
+    KVH, Skv = k.shape[1], k.shape[2]
+    assert mask.dtype is torch.bool and mask.shape[-2:] == (Sq, Skv) and v.shape == k.shape
+    for t in (q, k, v):
+        assert t.stride(3) == 1
+    if q.stride(1) != hd:  # heads must sit side by side in a row
+        q = q.transpose(1, 2).contiguous().transpose(1, 2)
+    m = _mask_rows(mask, B, Sq, Skv)
+    if m is None:
+        raise L.LlxError("attn_mask_fwd: the mask must be broadcast over heads ([B | 1, 1, Sq, Skv]); per-head masks run on attn_dense_fwd")
+    fl = ops._cached(mask, f"maskflags{B}", lambda: attn_mask_flags(mask, B))
+    if out is None:
+        out = torch.empty(B, Sq, H * hd, device=q.device, dtype=BF16)
+    assert out.shape == (B, Sq, H * hd) and out.dtype is BF16 and out.stride(2) == 1
+    L.check(_lib().llx_attn_mask_fwd(L.ptr(q), q.stride(0), q.stride(2), L.ptr(k), k.stride(0), k.stride(1), k.stride(2), L.ptr(v), v.stride(0),
+                                     v.stride(1), v.stride(2), L.ptr(out), out.stride(0), out.stride(1), None, L.ptr(m),
+                                     m.stride(0) if m.shape[0] != 1 else 0, m.stride(1), L.ptr(fl), B, Sq, Skv, H, KVH, hd, 1.0 / math.sqrt(hd),
+                                     L.stream()), "llx_attn_mask_fwd")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------- decode path (csrc/decode.hip)
 GV_NONE, GV_RESIDUAL, GV_QKV, GV_SWIGLU = 0, 1, 2, 3
 

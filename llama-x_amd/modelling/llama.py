@@ -206,7 +206,13 @@ class Attention(nn.Module):
             mask = torch.ones(L_, k.shape[2], dtype=torch.bool, device=x.device)
         if L_ * (H // KVH) <= 16 and k.stride() == v.stride():  # a few query tokens over a long cache: split-cache decode kernel
             o2 = K.attn_decode(q, k, v, mask, D.mask_extent(mask)).view(B * L_, H * hd)
-        else:
+        elif K.attn_mask_routable(mask, B, L_, k.shape[2]):
+            # prefill / explicit mask broadcast over heads: the MFMA tile loop driven by the mask bytes, o written as rows.  No range of small
+            # L stays on the per-row kernel: at the smallest shape past the decode branch (8 tokens at position 4096 of an 8192 cache,
+            # 8B heads) the attention call takes 0.12 ms here against 1.37 ms there, 0.18 against 25.2 ms at 4096 tokens
+            # (tools/prefill_bench.py, profiles/prefill_bench.json): no crossover was found.
+            o2 = K.attn_mask_fwd(q, k, v, mask).view(B * L_, H * hd)
+        else:  # per-head masks
             o2 = K.attn_dense_fwd(q, k, v, mask).transpose(1, 2).reshape(B * L_, H * hd)  # [B,H,L,hd] -> rows
         y, _ = ops.GroupPlan((self.wo,)).forward(o2, None, K._rows2d(x.contiguous()) if residual else None)
         return y.view(B, L_, -1)
