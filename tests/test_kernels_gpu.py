@@ -1,5 +1,6 @@
 """Kernel-level parity on the GPU: every C-ABI kernel vs the CPU oracle (oracle/ref.py) or a plain fp32 torch
-restatement of the same op, on seeded inputs.  Tolerances are stated per test (bf16 I/O, fp32 accumulate)."""
+restatement of the same op, on seeded inputs.  Tolerances are stated per test (bf16 I/O, fp32 accumulate).
+The norm, loss and glue kernels at every dispatch class and stride, against float64: tests/test_side_kernels_gpu.py."""
 import math
 
 import os
