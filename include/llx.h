@@ -142,13 +142,27 @@ int llx_attn_dense_fwd(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, 
  *      (batch, head, position) strides - the cache buffers or the views of a fused q|k|v row buffer.  mask bool / uint8 [B | 1, Sq, Skv],
  *      last dim dense, m_sq / m_sb in bytes (m_sb = 0 broadcasts), Skv >= 4.  flags: llx_attn_mask_flags_bytes(B, Sq, Skv) bytes filled
  *      by llx_attn_mask_tile_flags (128-row x 64-key tile classes: 0 skipped, 1 tested per byte, 2 unmasked).  lse nullable (fp32
- *      [B,H,Sq], log2 units).  A row without any allowed key comes out NaN, as SDPA's.  Forward only. ----------------------------- */
+ *      [B,H,Sq], log2 units).  A row without any allowed key comes out NaN, as SDPA's.  Backward: llx_attn_mask_bwd (Sq = Skv). --- */
 int64_t llx_attn_mask_flags_bytes(int64_t B, int64_t Sq, int64_t Skv);
 int llx_attn_mask_tile_flags(const void* mask, int64_t m_sb, int64_t m_sq, void* flags, int64_t B, int64_t Sq, int64_t Skv, llx_stream_t s);
 int llx_attn_mask_fwd(const void* q, int64_t q_sb, int64_t q_ss, const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, const void* v,
                       int64_t v_sb, int64_t v_sh, int64_t v_ss, void* o, int64_t o_sb, int64_t o_ss, float* lse /* nullable */,
                       const void* mask, int64_t m_sb, int64_t m_sq, const void* flags, int64_t B, int64_t Sq, int64_t Skv, int64_t H,
                       int64_t KVH, int64_t head_dim, float scale, llx_stream_t s);
+
+/* ---- training through any bool mask: the gradients autograd produces for the same SDPA call with an arbitrary dense mask, and for
+ *      flex_attention with a BlockMask of an arbitrary mask_mod (modelling/llama.py:129-137), with Sq = Skv = S.  Everything as
+ *      llx_attn_bwd (rows [B,S,H|KVH,128] with batch / sequence strides in elements, lse as llx_attn_mask_fwd wrote it, the workspace of
+ *      llx_attn_bwd_workspace_bytes(), nullable rope) except the rule: mask / m_sb / m_sq / flags as in llx_attn_mask_fwd with
+ *      flags = llx_attn_mask_tile_flags(mask, .., B, S, S); S >= 4.  Nothing causal is assumed: tiles above the diagonal can be live, and
+ *      a key that no row attends to gets exact zeros in dk / dv.  A row without any allowed key (NaN in the forward) has meaningless
+ *      gradients, as in the reference; the kernels stay memory-safe on it.  Deterministic (no atomics). ---------------------------- */
+int llx_attn_mask_bwd(const void* q, int64_t q_sb, int64_t q_ss, const void* k, int64_t k_sb, int64_t k_ss, const void* v, int64_t v_sb,
+                      int64_t v_ss, const void* o, int64_t o_sb, int64_t o_ss, const void* d_o, int64_t do_sb, int64_t do_ss,
+                      const float* lse, float* delta /* fp32 workspace, llx_attn_bwd_workspace_bytes() */, void* dq, int64_t dq_sb,
+                      int64_t dq_ss, void* dk, int64_t dk_sb, int64_t dk_ss, void* dv, int64_t dv_sb, int64_t dv_ss, const void* mask,
+                      int64_t m_sb, int64_t m_sq, const void* flags, const float* rope /* nullable, as in llx_attn_bwd */, int64_t B,
+                      int64_t S, int64_t H, int64_t KVH, int64_t head_dim, float scale, llx_stream_t s);
 
 /* ---- decode path: a few query tokens (M <= 4) against the KV cache - modelling/llama.py:76-90 (KVCache), :126-127,:135-137 (cached
  *      K/V through SDPA with the row-gathered causal mask), :189-194,:205-207 (Llama.forward with input_pos).  Every linear is a

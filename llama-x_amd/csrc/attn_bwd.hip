@@ -17,6 +17,11 @@
 //   1. attn_bwd_dq_kernel: one workgroup = 128 query rows of one head, sweeps key tiles      -> dQ, and delta[b,h,q] = sum_d dO.O
 //   2. attn_bwd_dkv3_kernel: as above without the dS^T store                                 -> fp32 partial dK, dV
 //   3. attn_dkv_reduce_kernel
+//   Route (b) also runs from a dense bool mask (llx_attn_mask_bwd, the BWD_MASK mode below): the same two kernels with their schedule
+//   from the mask's tile flags and the mask bytes as the predicate of partly masked tiles - the backward of the reference's SDPA call
+//   with an arbitrary mask and of flex_attention with an arbitrary mask_mod (modelling/llama.py:129-137).  Route (a) has no such mode.
+//   A fully masked row (no allowed key) is NaN in that forward, as SDPA's; its lse is -inf, which every route sanitises to 0, so the
+//   backward stays memory-safe on it - its gradients are as meaningless as the reference's NaNs.
 // MFMA orientation keeps the softmax row index where the row constants (lse, delta) are cheap:
 //   dq kernel : S^T = K.Q^T, dP^T = V.dO^T (query on the lane), dQ^T += K^T.dS^T with dS^T taken from the accumulator
 //               registers as the B operand and K^T read from the SAME LDS image by ds_read_b64_tr_b16.
@@ -90,14 +95,35 @@ struct AttnBwdArgs {
   const int* doc_ids; const int* prefix_len; const uint8_t* flags;
   int B, S, H, KVH;
   float scale, scale_log2;
+  // dense-mask mode only (llx_attn_mask_bwd): [B | 1, S, S] bool / uint8, last dim dense, nonzero = attend; strides in bytes
+  // (m_sb = 0: broadcast over the batch); flags are then those of llx_attn_mask_tile_flags with Sq = Skv = S
+  const uint8_t* mask; int64_t m_sb, m_sq;
 };
+
+// Where the tile schedule and the predicate of a partly masked (class-1) tile come from:
+//   BWD_CAUSAL  index arithmetic only (k <= q);
+//   BWD_RULE    tile flags + (k <= q || k < prefix_len[b]) && same document;
+//   BWD_MASK    tile flags + the bytes of a dense bool mask, and nothing else: no causal assumption is left in this mode (tiles above
+//               the diagonal can be live, a key block can have no live tile at all).  A row without any allowed key has lse = -inf
+//               (NaN output in the forward, as SDPA); the sanitised -lse keeps the backward memory-safe on it, its gradients mean nothing.
+enum { BWD_CAUSAL = 0, BWD_RULE = 1, BWD_MASK = 2 };
+
+// One mask dword (4 keys of one row) -> 4 bits, bit i = byte i is nonzero.  (x & 0x7f..) + 0x7f.. | x sets bit 7 of every nonzero byte;
+// the multiply gathers the four bits (at 0, 8, 16, 24 after the shift) into bits 24-27: no two partial products share a bit.
+__device__ __forceinline__ uint32_t mask_nibble(uint32_t w) {
+  const uint32_t nz = (((w & 0x7f7f7f7fu) + 0x7f7f7f7fu) | w) & 0x80808080u;
+  return ((nz >> 7) * 0x01020408u) >> 24;
+}
 
 // ------------------------------------------------------------------------------------------ dQ
 #define DQ_STAGE_BYTES (2 * TILE_BYTES)
 #define DQ_LDS_BYTES (2 * DQ_STAGE_BYTES)
 
-template <bool GENERAL>
+template <int MODE>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnBwdArgs a) {
+  constexpr bool GENERAL = MODE == BWD_RULE;   // doc_ids / prefix_len
+  constexpr bool FLAGS = MODE != BWD_CAUSAL;   // tile classes come from flags
+  constexpr bool MASK = MODE == BWD_MASK;
   extern __shared__ __attribute__((aligned(256))) char smem[];  // 256-aligned: the transposed-read addresses flip bits 5-7 by XOR
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -109,13 +135,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnBwdArgs a
   const int qi = qb * BQ + wave * 32 + r;
   const int qrow = min(qi, a.S - 1);
 
-  const uint8_t* fl = GENERAL ? a.flags + ((int64_t)b * nqb + qb) * nkt : nullptr;
-  const int kt_end = GENERAL ? nkt : min(nkt, (qb * BQ + BQ + BKV - 1) / BKV);
+  const uint8_t* fl = FLAGS ? a.flags + ((int64_t)b * nqb + qb) * nkt : nullptr;
+  const int kt_end = FLAGS ? nkt : min(nkt, (qb * BQ + BQ + BKV - 1) / BKV);
   // (general masks: the flags of 64 tiles at a time in one register, read by v_readlane - not a dependent byte load per tile)
   uint32_t fpack = 0;
   int fchunk = -1;
   auto tile_class = [&](int t) -> int {
-    if constexpr (GENERAL) {
+    if constexpr (FLAGS) {
       if ((t >> 6) != fchunk) {
         fchunk = t >> 6;
         fpack = fl[min(fchunk * 64 + lane, nkt - 1)];
@@ -182,8 +208,58 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnBwdArgs a
   const int* docrow = (GENERAL && a.doc_ids) ? a.doc_ids + (int64_t)b * a.S : nullptr;
   const int my_doc = docrow ? docrow[qrow] : 0;
   const int my_prefix = (GENERAL && a.prefix_len) ? a.prefix_len[b] : 0;
+  // BWD_MASK: the query sits on the lane, so the forward's scheme carries over: the lane's 32 keys of a tile are the byte groups
+  // 32 kb + 8 j + 4 hh .. +3 (kb < 2, j < 4) of its own mask row (clamped to row S - 1: rows past the end are computed and not stored) -
+  // 8 unaligned dwords, requested one tile ahead and only for class-1 tiles.  A group that would run past the row's end is read 4 bytes
+  // before the end and shifted down (S >= 4), so keys past S test as masked and no byte past a row is touched.  Unlike the forward this
+  // kernel has no 16 registers for two sets of words: when the tile starts, the 8 words that have landed are squeezed into ONE register
+  // (bit 16 kb + e = accumulator element e of key half kb) and the same 8 registers take the next request.
+  uint32_t mwn[MASK ? 8 : 1];
+  auto mask_request = [&](int t_) {
+    if constexpr (MASK) {
+      // (the row pointer is rebuilt per request from a fresh lane id: kept across the tile loop it is spilled, and its reload waits
+      // for the next tile's LDS-DMA as well)
+      uint32_t l0;
+      asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l0));
+      const int hh = (int)(l0 >> 5);
+      const uint8_t* mrow = a.mask + (int64_t)b * a.m_sb + (int64_t)min(qb * BQ + wave * 32 + (int)(l0 & 31), a.S - 1) * a.m_sq;
+      if (t_ * BKV + BKV <= a.S) {  // full tile (wave-uniform): one address, immediate offsets
+        const uint8_t* p = mrow + t_ * BKV + 4 * hh;
+#pragma unroll
+        for (int g = 0; g < 8; ++g) __builtin_memcpy(&mwn[g], p + (g >> 2) * 32 + 8 * (g & 3), 4);
+      } else {
+#pragma unroll
+        for (int g = 0; g < 8; ++g) {
+          const int g0 = t_ * BKV + (g >> 2) * 32 + 8 * (g & 3) + 4 * hh;
+          __builtin_memcpy(&mwn[g], mrow + min(g0, a.S - 4), 4);
+        }
+      }
+    }
+  };
+  auto mask_bits = [&](int t_) -> uint32_t {
+    uint32_t bits = 0;
+    if constexpr (MASK) {
+      const bool ragged = t_ * BKV + BKV > a.S;  // wave-uniform: undo the clamp of mask_request
+#pragma unroll
+      for (int g = 0; g < 8; ++g) {
+        uint32_t w = mwn[g];
+        if (ragged) {
+          const int g0 = t_ * BKV + (g >> 2) * 32 + 8 * (g & 3) + 4 * hh;
+          const int sh = g0 - min(g0, a.S - 4);
+          w = sh >= 4 ? 0u : w >> (8 * sh);
+        }
+        bits |= mask_nibble(w) << (4 * g);
+      }
+    }
+    return bits;
+  };
 
   int t = next_tile(0);
+  if constexpr (MASK) {
+#pragma unroll
+    for (int g = 0; g < 8; ++g) mwn[g] = 0;
+    if (t < kt_end && tile_class(t) == 1) mask_request(t);
+  }
   if (t < kt_end) stage(0, t);
   // (the rows' own operands are requested AFTER the first K/V tile: one memory round trip for both instead of two in a row)
   // q, dO, O and lse of the rows are requested in ONE batch (hipcc put a full wait between the q / dO loads and the lse / O loads)
@@ -226,12 +302,21 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnBwdArgs a
   // ds_bpermute, as in the forward kernel)
   int docv = (GENERAL && docrow && t < kt_end) ? docrow[min(t * BKV + lane, a.S - 1)] : 0, docv_next = 0;
   while (t < kt_end) {
+    int cls_m = 0;
+    uint32_t mbits = 0;
+    if constexpr (MASK) {  // (before the next tile's loads go out: the wait for these words then waits for nothing else)
+      cls_m = tile_class(t);
+      if (cls_m == 1) mbits = mask_bits(t);
+    }
     const int tn = next_tile(t + 1);
     if (tn < kt_end) stage(cur ^ 1, tn);
     if (GENERAL && docrow && tn < kt_end) docv_next = docrow[min(tn * BKV + lane, a.S - 1)];
+    if constexpr (MASK) {
+      if (tn < kt_end && tile_class(tn) == 1) mask_request(tn);
+    }
     const char* sK = smem + cur * DQ_STAGE_BYTES;
     const char* sV = sK + TILE_BYTES;
-    const int cls = tile_class(t);
+    const int cls = MASK ? cls_m : tile_class(t);
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
       f32x16_t st, dp;
@@ -246,6 +331,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnBwdArgs a
       if (cls != 2) {  // ONE wave-uniform branch per 32 keys: masked scores become -inf, exp2 turns them into 0
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
+          if constexpr (MASK) {
+            st[e] = ((mbits >> (kb * 16 + e)) & 1u) ? st[e] : -INFINITY;
+          } else {
           const int kk = t * BKV + kb * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
           bool ok = (kk < a.S) && (kk <= qi || kk < my_prefix);
           if constexpr (GENERAL) {
@@ -253,6 +341,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnBwdArgs a
             ok = ok && (kd == my_doc);
           }
           st[e] = ok ? st[e] : -INFINITY;
+          }
         }
       }
 #pragma unroll
@@ -350,8 +439,12 @@ typedef __attribute__((address_space(3))) bf16x8_t lds_bf16x8;
 typedef __attribute__((address_space(3))) f32x4_t lds_f32x4;
 #define DKV3_LDS_BYTES (0x10000 + 1024)
 
-template <bool GENERAL, bool STAMP = false, bool DS = false>
+template <int MODE, bool STAMP = false, bool DS = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv3_kernel(const AttnBwdArgs a, float* __restrict__ part) {
+  constexpr bool GENERAL = MODE == BWD_RULE;   // doc_ids / prefix_len
+  constexpr bool FLAGS = MODE != BWD_CAUSAL;   // tile classes come from flags
+  constexpr bool MASK = MODE == BWD_MASK;
+  static_assert(!(MASK && (STAMP || DS)), "the dense-mask mode exists on the default route only");
   extern __shared__ __attribute__((aligned(256))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -385,14 +478,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv3_kernel(const AttnBwdArgs
   }
   const int my_prefix = (GENERAL && a.prefix_len) ? a.prefix_len[b] : 0;
 
-  const int qt_first = GENERAL ? 0 : (kblk * DKV2_KEYS) / DKV_QT;
+  const int qt_first = FLAGS ? 0 : (kblk * DKV2_KEYS) / DKV_QT;
   // (general masks: the flag bytes of this key block's two tiles for 64 query blocks at a time in one register - lane i holds query
   // block 64*chunk + i - read by v_readlane; as byte loads they were three dependent memory round trips per query tile)
   uint32_t fpack = 0;
   int fchunk = -1;
   auto block_class = [&](int qt, int kt) -> int {
     if (kt >= nkt) return 0;
-    if constexpr (GENERAL) {
+    if constexpr (FLAGS) {
       const int qb128 = qt >> 1;
       if ((qb128 >> 6) != fchunk) {
         fchunk = qb128 >> 6;
@@ -459,7 +552,66 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv3_kernel(const AttnBwdArgs
 #pragma unroll
     for (int e = 0; e < 16; ++e) { dk[i][e] = 0.f; dv[i][e] = 0.f; }
 
+  // BWD_MASK: here the key sits on the lane and the 16 accumulator elements of a lane are 16 different mask rows, so per-element byte
+  // loads would be 32 load instructions per tile.  Instead lane i fetches the 32 bytes (this wave's 32 keys) of query row 64 qt + i -
+  // 8 unaligned dwords, clamped at the row's end and at row S - 1 exactly as in the dQ kernel - and squeezes them into ONE register
+  // (bit j = key j of the wave); an element then gathers its row's register by ds_bpermute, as the document ids are gathered, and tests
+  // the bit of its own key.
+  // When the words travel is decided by the registers (this kernel sits at 256 with none to spare).  Measured on the compiler's output:
+  // 8 words in flight one tile ahead, as in the dQ kernel, or across the first S chain, or across the second phase of the tile, or 4 + 4
+  // words in two rounds all push a K fragment (or more) out to scratch, and the reload of that fragment in front of every S chain waits
+  // for the next tile's LDS-DMA (the failure described above DKV3_LDS_BYTES).  So the words of the next class-1 tile are requested at the
+  // very END of a tile, behind its last MFMA, land under the `s_waitcnt vmcnt(0)` + barrier that close the tile, and are squeezed into
+  // the one register at the top of the next: nothing but that register is live while a tile computes, and the kernel has no scratch.
+  // The price: the part of the mask round trip that the wait for the other waves does not cover, once per class-1 tile.
+  uint32_t mwn[MASK ? 8 : 1];
+  auto mask_request = [&](int qt_) {
+    if constexpr (MASK) {
+      uint32_t l0;
+      asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l0));
+      const uint8_t* mr = a.mask + (int64_t)b * a.m_sb + (int64_t)min(qt_ * DKV_QT + (int)l0, a.S - 1) * a.m_sq;
+      const int key0 = kblk * DKV2_KEYS + wave * 32;
+      if (key0 + 32 <= a.S) {  // all 32 keys inside the row (wave-uniform): one address, immediate offsets
+#pragma unroll
+        for (int g = 0; g < 8; ++g) __builtin_memcpy(&mwn[g], mr + key0 + 4 * g, 4);
+      } else {
+#pragma unroll
+        for (int g = 0; g < 8; ++g) __builtin_memcpy(&mwn[g], mr + min(key0 + 4 * g, a.S - 4), 4);
+      }
+    }
+  };
+  auto mask_bits = [&]() -> uint32_t {
+    uint32_t bits = 0;
+    if constexpr (MASK) {
+#pragma unroll
+      for (int g = 0; g < 8; ++g) asm volatile("" : "+v"(mwn[g]));  // (the words are used HERE, in program order with the barriers)
+      const bool ragged = kblk * DKV2_KEYS + wave * 32 + 32 > a.S;  // wave-uniform: undo the clamp of mask_request
+#pragma unroll
+      for (int g = 0; g < 8; ++g) {
+        uint32_t w = mwn[g];
+        if (ragged) {
+          const int g0 = kblk * DKV2_KEYS + wave * 32 + 4 * g;
+          const int sh = g0 - min(g0, a.S - 4);
+          w = sh >= 4 ? 0u : w >> (8 * sh);
+        }
+        bits |= mask_nibble(w) << (4 * g);
+      }
+    }
+    return bits;
+  };
+
+  // (block_class reloads the flag register whenever the 64-query-block chunk changes: where qt and qtn lie in different chunks, next_qt,
+  // block_class(qt) and mask_wanted(qtn) reload it three times in one tile instead of twice - once per 8192 query rows)
+  auto mask_wanted = [&](int qt_) -> bool {  // wave-uniform: class 1, or class 2 demoted on the ragged last query tile
+    const int c = block_class(qt_, my_kt);
+    return c == 1 || (c == 2 && qt_ * DKV_QT + DKV_QT > a.S);
+  };
   int qt = next_qt(0);
+  if constexpr (MASK) {
+#pragma unroll
+    for (int g = 0; g < 8; ++g) mwn[g] = 0;
+    if (qt < nqt && mask_wanted(qt)) mask_request(qt);
+  }
   // (document masks: the tile's 64 query-row ids in one register - lane i holds row 64 qt + i - requested one tile ahead, gathered by
   // ds_bpermute where a partly masked block needs them)
   int qdoc = 0, qdoc_next = 0;
@@ -501,6 +653,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv3_kernel(const AttnBwdArgs
     const int key = kblk * DKV2_KEYS + wave * 32 + (int)lr_;
     int cls = block_class(qt, my_kt);
     if (cls == 2 && (qt * DKV_QT + DKV_QT > a.S)) cls = 1;
+    uint32_t rowbits = 0;  // BWD_MASK: lane i holds the 32 key bits of query row 64 qt + i
+    if constexpr (MASK) {
+      if (cls == 1) rowbits = mask_bits();
+      __builtin_amdgcn_sched_barrier(0);
+    }
     if (have_next) stage(cur ^ 1, qtn);
     if (GENERAL && docrow && have_next) qdoc_next = docrow[min(qtn * DKV_QT + (int)ln, a.S - 1)];
     stamp();  // 1: next tile's DMA issued
@@ -538,12 +695,17 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv3_kernel(const AttnBwdArgs
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
             const int qi = qt * DKV_QT + qb32 * 32 + 8 * (e >> 2) + 4 * hh + (e & 3);
+            if constexpr (MASK) {  // (a key past S has no bit set: the clamp of the mask words saw to that)
+              const uint32_t rb = (uint32_t)__builtin_amdgcn_ds_bpermute((qi - qt * DKV_QT) << 2, (int)rowbits);
+              st[e] = ((qi < a.S) && ((rb >> lr_) & 1u)) ? st[e] : -INFINITY;
+            } else {
             bool ok = (qi < a.S) && (key < a.S) && (key <= qi || key < my_prefix);
             if constexpr (GENERAL) {
               const int qd = docrow ? __builtin_amdgcn_ds_bpermute((qi - qt * DKV_QT) << 2, qdoc) : key_doc;
               ok = ok && (qd == key_doc);
             }
             st[e] = ok ? st[e] : -INFINITY;
+            }
           }
         }
 #pragma unroll
@@ -611,6 +773,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv3_kernel(const AttnBwdArgs
         }
         if (qb32 == 0) stamp();  // 6: 16 + 16 MFMAs of the second phase (first 32 rows)
       }
+    }
+    if constexpr (MASK) {
+#pragma unroll
+      for (int g = 0; g < 8; ++g) mwn[g] = 0;  // (so that the old words are dead during the tile: a conditional request alone carries them)
+      if (have_next && mask_wanted(qtn)) mask_request(qtn);
     }
     stamp();  // 7: second 32 rows
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -945,15 +1112,17 @@ static int attn_bwd_set_attrs() {
   std::call_once(once, [] {
     hipError_t e = hipSuccess;
     auto set = [&](const void* f, int bytes) { if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); };
-    set((const void*)attn_bwd_dq_kernel<false>, DQ_LDS_BYTES);
-    set((const void*)attn_bwd_dq_kernel<true>, DQ_LDS_BYTES);
+    set((const void*)attn_bwd_dq_kernel<BWD_CAUSAL>, DQ_LDS_BYTES);
+    set((const void*)attn_bwd_dq_kernel<BWD_RULE>, DQ_LDS_BYTES);
     set((const void*)attn_bwd_dq2_kernel<false>, DQ2_LDS_BYTES);
     set((const void*)attn_bwd_dq2_kernel<true>, DQ2_LDS_BYTES);
-    set((const void*)attn_bwd_dkv3_kernel<true, false, false>, DKV3_LDS_BYTES);
-    set((const void*)attn_bwd_dkv3_kernel<false, false, false>, DKV3_LDS_BYTES);
-    set((const void*)attn_bwd_dkv3_kernel<true, false, true>, DKV3_LDS_BYTES);
-    set((const void*)attn_bwd_dkv3_kernel<false, false, true>, DKV3_LDS_BYTES);
-    set((const void*)attn_bwd_dkv3_kernel<false, true, false>, DKV3_LDS_BYTES);
+    set((const void*)attn_bwd_dkv3_kernel<BWD_RULE, false, false>, DKV3_LDS_BYTES);
+    set((const void*)attn_bwd_dkv3_kernel<BWD_CAUSAL, false, false>, DKV3_LDS_BYTES);
+    set((const void*)attn_bwd_dkv3_kernel<BWD_RULE, false, true>, DKV3_LDS_BYTES);
+    set((const void*)attn_bwd_dkv3_kernel<BWD_CAUSAL, false, true>, DKV3_LDS_BYTES);
+    set((const void*)attn_bwd_dkv3_kernel<BWD_CAUSAL, true, false>, DKV3_LDS_BYTES);
+    set((const void*)attn_bwd_dq_kernel<BWD_MASK>, DQ_LDS_BYTES);
+    set((const void*)attn_bwd_dkv3_kernel<BWD_MASK, false, false>, DKV3_LDS_BYTES);
     ok = e == hipSuccess;
   });
   return ok ? LLX_OK : LLX_ERR_LAUNCH;
@@ -992,6 +1161,7 @@ extern "C" int llx_attn_bwd(const void* q, int64_t q_sb, int64_t q_ss, const voi
   a.doc_ids = doc_ids; a.prefix_len = prefix_len; a.flags = (doc_ids || prefix_len) ? (const uint8_t*)flags : nullptr;
   a.B = (int)B; a.S = (int)S; a.H = (int)H; a.KVH = (int)KVH;
   a.scale = scale; a.scale_log2 = scale * 1.4426950408889634f;
+  a.mask = nullptr; a.m_sb = 0; a.m_sq = 0;
   const dim3 qgrid((unsigned)H, (unsigned)cdiv64(S, BQ), (unsigned)B);
   // (with tile flags the dQ-from-dS kernel keeps its schedule in two 64-bit masks: up to 128 key tiles = 8192 positions)
   const bool use_ds = ds != nullptr && !g_bwd_stamps && !((doc_ids || prefix_len) && cdiv64(S, BKV) > 128);
@@ -1000,21 +1170,21 @@ extern "C" int llx_attn_bwd(const void* q, int64_t q_sb, int64_t q_ss, const voi
     LLX_LAUNCH_CHECK("llx_attn_bwd(delta)");
   } else {
     // dQ first: it also publishes delta = rowsum(dO . O) and the sanitised -lse that the dK/dV kernel stages from global memory
-    if (a.flags) hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, qgrid, dim3(256), DQ_LDS_BYTES, stream, a);
-    else hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, qgrid, dim3(256), DQ_LDS_BYTES, stream, a);
+    if (a.flags) hipLaunchKernelGGL(attn_bwd_dq_kernel<BWD_RULE>, qgrid, dim3(256), DQ_LDS_BYTES, stream, a);
+    else hipLaunchKernelGGL(attn_bwd_dq_kernel<BWD_CAUSAL>, qgrid, dim3(256), DQ_LDS_BYTES, stream, a);
     LLX_LAUNCH_CHECK("llx_attn_bwd(dq)");
   }
   float* part = delta + 2 * B * H * S;
   const int64_t nkb = cdiv64(S, DKV2_KEYS);
   const dim3 kgrid((unsigned)(nkb * B * H));
   if (use_ds) {
-    if (a.flags) hipLaunchKernelGGL((attn_bwd_dkv3_kernel<true, false, true>), kgrid, dim3(256), DKV3_LDS_BYTES, stream, a, part);
-    else hipLaunchKernelGGL((attn_bwd_dkv3_kernel<false, false, true>), kgrid, dim3(256), DKV3_LDS_BYTES, stream, a, part);
+    if (a.flags) hipLaunchKernelGGL((attn_bwd_dkv3_kernel<BWD_RULE, false, true>), kgrid, dim3(256), DKV3_LDS_BYTES, stream, a, part);
+    else hipLaunchKernelGGL((attn_bwd_dkv3_kernel<BWD_CAUSAL, false, true>), kgrid, dim3(256), DKV3_LDS_BYTES, stream, a, part);
   } else if (g_bwd_stamps && !a.flags) {
     a.stamps = g_bwd_stamps;
-    hipLaunchKernelGGL((attn_bwd_dkv3_kernel<false, true, false>), kgrid, dim3(256), DKV3_LDS_BYTES, stream, a, part);
-  } else if (a.flags) hipLaunchKernelGGL((attn_bwd_dkv3_kernel<true, false, false>), kgrid, dim3(256), DKV3_LDS_BYTES, stream, a, part);
-  else hipLaunchKernelGGL((attn_bwd_dkv3_kernel<false, false, false>), kgrid, dim3(256), DKV3_LDS_BYTES, stream, a, part);
+    hipLaunchKernelGGL((attn_bwd_dkv3_kernel<BWD_CAUSAL, true, false>), kgrid, dim3(256), DKV3_LDS_BYTES, stream, a, part);
+  } else if (a.flags) hipLaunchKernelGGL((attn_bwd_dkv3_kernel<BWD_RULE, false, false>), kgrid, dim3(256), DKV3_LDS_BYTES, stream, a, part);
+  else hipLaunchKernelGGL((attn_bwd_dkv3_kernel<BWD_CAUSAL, false, false>), kgrid, dim3(256), DKV3_LDS_BYTES, stream, a, part);
   LLX_LAUNCH_CHECK("llx_attn_bwd(dkv)");
   const int64_t plane = B * S * KVH * HD;
   hipLaunchKernelGGL(attn_dkv_reduce_kernel, dim3((unsigned)cdiv64(plane / 8, 256)), dim3(256), 0, stream, a, (const float*)part);
@@ -1025,5 +1195,56 @@ extern "C" int llx_attn_bwd(const void* q, int64_t q_sb, int64_t q_ss, const voi
     else hipLaunchKernelGGL(attn_bwd_dq2_kernel<false>, q2grid, dim3(512), DQ2_LDS_BYTES, stream, a);
     LLX_LAUNCH_CHECK("llx_attn_bwd(dq from dS)");
   }
+  return LLX_OK;
+}
+
+// Backward of llx_attn_mask_fwd with Sq = Skv = S: the gradients autograd produces for the reference's SDPA call with an arbitrary
+// dense mask and for flex_attention with an arbitrary mask_mod (modelling/llama.py:129-137).  Arguments as llx_attn_bwd (q / k / v / o /
+// d_o / dq / dk / dv rows [B,S,H|KVH,128] with batch and sequence strides in elements, lse [B,H,S] in log2 units as the forward wrote
+// it, delta: llx_attn_bwd_workspace_bytes() bytes, rope nullable) without doc_ids / prefix_len / ds; mask [B | 1, S, S] bool / uint8
+// with a dense last dim, m_sb / m_sq in bytes (m_sb = 0 broadcasts over the batch), flags from llx_attn_mask_tile_flags(mask, ..., B, S, S).
+// The default route (b) of this file in its BWD_MASK mode: the tile schedule comes from the flags alone, a partly masked tile tests the
+// mask bytes.  A key no row attends to gets exact zeros in dk / dv.  A row without any allowed key (NaN in the forward, as SDPA) has
+// meaningless gradients here as in the reference; the kernels stay memory-safe on it.
+extern "C" int llx_attn_mask_bwd(const void* q, int64_t q_sb, int64_t q_ss, const void* k, int64_t k_sb, int64_t k_ss, const void* v,
+                                 int64_t v_sb, int64_t v_ss, const void* o, int64_t o_sb, int64_t o_ss, const void* d_o, int64_t do_sb,
+                                 int64_t do_ss, const float* lse, float* delta, void* dq, int64_t dq_sb, int64_t dq_ss, void* dk,
+                                 int64_t dk_sb, int64_t dk_ss, void* dv, int64_t dv_sb, int64_t dv_ss, const void* mask, int64_t m_sb,
+                                 int64_t m_sq, const void* flags, const float* rope, int64_t B, int64_t S, int64_t H, int64_t KVH,
+                                 int64_t head_dim, float scale, hipStream_t stream) {
+  LLX_REQUIRE(q && k && v && o && d_o && lse && delta && dq && dk && dv && mask && flags, "llx_attn_mask_bwd: null pointer");
+  LLX_REQUIRE(head_dim == HD, "llx_attn_mask_bwd: head_dim=%lld unsupported (only 128)", (long long)head_dim);
+  LLX_REQUIRE(B > 0 && S > 0 && H > 0 && KVH > 0 && H % KVH == 0, "llx_attn_mask_bwd: bad B/S/H/KVH");
+  LLX_REQUIRE(S >= 4, "llx_attn_mask_bwd: S=%lld (>= 4: the mask is read 4 bytes at a time)", (long long)S);
+  LLX_REQUIRE(((q_ss | k_ss | v_ss | o_ss | do_ss | q_sb | k_sb | v_sb | o_sb | do_sb) % 8) == 0, "llx_attn_mask_bwd: input strides must keep 16-byte alignment");
+  LLX_REQUIRE(((dq_ss | dk_ss | dv_ss | dq_sb | dk_sb | dv_sb) % 4) == 0, "llx_attn_mask_bwd: output strides must keep 8-byte alignment");
+  LLX_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)d_o) % 16 == 0, "llx_attn_mask_bwd: unaligned input");
+  LLX_REQUIRE(((uintptr_t)dq) % 8 == 0 && ((uintptr_t)dk | (uintptr_t)dv) % 16 == 0 && ((dk_ss | dv_ss | dk_sb | dv_sb) % 8) == 0,
+              "llx_attn_mask_bwd: unaligned output");
+  LLX_REQUIRE(!rope || (uintptr_t)rope % 16 == 0, "llx_attn_mask_bwd: unaligned rope table");
+  LLX_REQUIRE(S < (1 << 24) && B * H < (1 << 16), "llx_attn_mask_bwd: S or B*H too large");
+  LLX_REQUIRE(m_sq >= S && m_sb >= 0, "llx_attn_mask_bwd: mask rows overlap");
+  if (attn_bwd_set_attrs() != LLX_OK) { llx_set_error("llx_attn_mask_bwd: cannot raise LDS limit"); return LLX_ERR_LAUNCH; }
+  AttnBwdArgs a;
+  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (const bf16_t*)o; a.d_o = (const bf16_t*)d_o;
+  a.lse = lse; a.delta = delta; a.nlse = delta + B * H * S; a.stamps = nullptr; a.rope = rope; a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv;
+  a.ds = nullptr; a.Sp = 0;
+  a.q_sb = q_sb; a.q_ss = q_ss; a.k_sb = k_sb; a.k_ss = k_ss; a.v_sb = v_sb; a.v_ss = v_ss; a.o_sb = o_sb; a.o_ss = o_ss;
+  a.do_sb = do_sb; a.do_ss = do_ss; a.dq_sb = dq_sb; a.dq_ss = dq_ss; a.dk_sb = dk_sb; a.dk_ss = dk_ss; a.dv_sb = dv_sb; a.dv_ss = dv_ss;
+  a.doc_ids = nullptr; a.prefix_len = nullptr; a.flags = (const uint8_t*)flags;
+  a.B = (int)B; a.S = (int)S; a.H = (int)H; a.KVH = (int)KVH;
+  a.scale = scale; a.scale_log2 = scale * 1.4426950408889634f;
+  a.mask = (const uint8_t*)mask; a.m_sb = m_sb; a.m_sq = m_sq;
+  // dQ first: it also publishes delta = rowsum(dO . O) and the sanitised -lse that the dK/dV kernel stages from global memory
+  hipLaunchKernelGGL(attn_bwd_dq_kernel<BWD_MASK>, dim3((unsigned)H, (unsigned)cdiv64(S, BQ), (unsigned)B), dim3(256), DQ_LDS_BYTES, stream, a);
+  LLX_LAUNCH_CHECK("llx_attn_mask_bwd(dq)");
+  float* part = delta + 2 * B * H * S;
+  // (a key block without a live tile runs no tile and still writes its zero partials: the reduce then stores exact zeros)
+  hipLaunchKernelGGL((attn_bwd_dkv3_kernel<BWD_MASK, false, false>), dim3((unsigned)(cdiv64(S, DKV2_KEYS) * B * H)), dim3(256), DKV3_LDS_BYTES,
+                     stream, a, part);
+  LLX_LAUNCH_CHECK("llx_attn_mask_bwd(dkv)");
+  const int64_t plane = B * S * KVH * HD;
+  hipLaunchKernelGGL(attn_dkv_reduce_kernel, dim3((unsigned)cdiv64(plane / 8, 256)), dim3(256), 0, stream, a, (const float*)part);
+  LLX_LAUNCH_CHECK("llx_attn_mask_bwd(dkv reduce)");
   return LLX_OK;
 }

@@ -196,6 +196,8 @@ class DevicePrefetcher:
             host = item if item.is_pinned() else item.pin_memory()
             return host.to(self.device, non_blocking=True)
         if isinstance(item, MaskSpec):
+            if item.dense is not None:
+                return MaskSpec(dense=self._to_device(item.dense))
             return MaskSpec(None if item.doc_ids is None else self._to_device(item.doc_ids.to(torch.int32)),
                             None if item.prefix_len is None else self._to_device(torch.as_tensor(item.prefix_len, dtype=torch.int32)))
         return item

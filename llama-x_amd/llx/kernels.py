@@ -501,21 +501,71 @@ def swiglu_bwd(dh: Tensor, g: Tensor, u: Tensor, dg: Tensor, du: Tensor) -> None
 
 # ------------------------------------------------------------------------------------------------- attention
 class MaskSpec:
-    """Per-token mask metadata (replaces FlexAttention's BlockMask in the ``block_mask=`` slot).
+    """Mask of a training step (replaces FlexAttention's BlockMask in the ``block_mask=`` slot).  Either the rule
 
-    allow(q, k) = (k <= q or k < prefix_len[b]) and (doc_ids is None or doc_ids[b, q] == doc_ids[b, k]).
-    ``doc_ids`` int32 [B, S] (or [S], broadcast), ``prefix_len`` int32 [B].  Tile classes are built once on device.
+    allow(q, k) = (k <= q or k < prefix_len[b]) and (doc_ids is None or doc_ids[b, q] == doc_ids[b, k])
+
+    from per-token metadata - ``doc_ids`` int32 [B, S] (or [S], broadcast), ``prefix_len`` int32 [B] - or ``dense``: ANY bool mask
+    [S, S], [B | 1, S, S] or [B | 1, 1, S, S] (True = attend; broadcast over heads), which nothing but its bytes describes: sliding
+    windows, non-contiguous documents, left padding, block-sparse or bidirectional patterns.  ``dense`` excludes the other two.  Both
+    forms train (attn_fwd / attn_bwd); the rule form is the faster one where it applies (MaskSpec.from_mask_mod picks it).  A query row
+    without any allowed key gives NaN, as SDPA does.  Tile classes are built once on device, at the first use with a given (B, S,
+    device): a ``dense`` mask must not be changed in place or replaced on the spec after that (a tile cached as fully masked or fully
+    allowed is never tested byte by byte again) - build a new MaskSpec for a new mask.
     """
 
-    def __init__(self, doc_ids: Optional[Tensor] = None, prefix_len: Optional[Tensor] = None):
+    def __init__(self, doc_ids: Optional[Tensor] = None, prefix_len: Optional[Tensor] = None, dense: Optional[Tensor] = None):
+        if dense is not None:
+            if doc_ids is not None or prefix_len is not None:
+                raise L.LlxError("MaskSpec: dense= is the whole mask; it cannot be combined with doc_ids / prefix_len")
+            if not isinstance(dense, Tensor) or dense.dtype is not torch.bool:
+                raise L.LlxError(f"MaskSpec: dense must be a bool tensor (True = attend), got {getattr(dense, 'dtype', type(dense))}")
+            if dense.dim() not in (2, 3, 4) or dense.shape[-1] != dense.shape[-2]:
+                raise L.LlxError(f"MaskSpec: dense must be [S, S], [B | 1, S, S] or [B | 1, 1, S, S], got {tuple(dense.shape)}")
+            if dense.dim() == 4 and dense.shape[1] != 1:
+                raise L.LlxError(f"MaskSpec: a per-head dense mask (shape {tuple(dense.shape)}) is not supported: the mask is broadcast over heads")
         self.doc_ids = doc_ids
         self.prefix_len = prefix_len
+        self.dense = dense
         self._flags = None
         self._key = None
+
+    @staticmethod
+    def from_mask_mod(mask_mod, B: int, S: int, device) -> "MaskSpec":
+        """The MaskSpec of a FlexAttention-style ``mask_mod(b, h, q_idx, kv_idx) -> bool`` (the argument of the reference's
+        create_block_mask, train_metamathqa.py:67-70), evaluated with h = 0 on [B, S, S] index grids.  Where the rule reproduces the
+        mask exactly (causal, contiguous documents, prefix-LM) the rule spec is returned - the faster kernels - else MaskSpec(dense=...).
+        One host synchronisation (that comparison), here at construction and never inside a forward."""
+        b = torch.arange(B, device=device).view(B, 1, 1)
+        q = torch.arange(S, device=device).view(1, S, 1)
+        k = torch.arange(S, device=device).view(1, 1, S)
+        m = torch.as_tensor(mask_mod(b, torch.zeros((), dtype=torch.int64, device=device), q, k), device=device)
+        if m.dtype is not torch.bool:
+            raise L.LlxError(f"MaskSpec.from_mask_mod: mask_mod must return bool, got {m.dtype}")
+        m = m.expand(B, S, S).contiguous()[:, None]  # [B, 1, S, S]
+        spec = maskspec_from_dense(m, B, S)
+        return spec if spec is not None else MaskSpec(dense=m)
 
     def prepared(self, B: int, S: int, device) -> "MaskSpec":
         key = (B, S, str(device))
         if self._key == key:
+            return self
+        if self.dense is not None:
+            m = self.dense
+            while m.dim() < 4:
+                m = m.unsqueeze(0)
+            if m.shape[0] not in (1, B) or m.shape[2:] != (S, S):
+                raise L.LlxError(f"MaskSpec: dense mask of shape {tuple(self.dense.shape)} does not fit batch {B}, sequence {S}")
+            if S < 4:
+                raise L.LlxError("MaskSpec: a dense mask needs S >= 4 (the kernels read it 4 bytes at a time)")
+            from . import ops  # (ops imports this module)
+
+            m = m.to(device)
+            if m.stride(3) != 1 or m.stride(2) < S:
+                m = m.contiguous()
+            self._rows = m  # [B | 1, 1, S, S], last dim dense: the tensor attn_mask_fwd / attn_mask_bwd are called with
+            self._flags = ops._cached(m, f"maskflags{B}", lambda: attn_mask_flags(m, B))  # (the cache those two look into)
+            self._key = key
             return self
         d = self.doc_ids
         if d is not None:
@@ -578,6 +628,10 @@ def attn_fwd(q: Tensor, k: Tensor, v: Tensor, mask: Optional[MaskSpec] = None) -
     KVH = k.shape[2]
     for t in (q, k, v):
         assert t.stride(3) == 1 and t.stride(2) == hd
+    if mask is not None and mask.dense is not None:  # any bool mask: the mask-driven tile loop, o as the rows `wo` reads
+        mask = mask.prepared(B, S, q.device)
+        o, lse = attn_mask_fwd(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), mask._rows, lse=True)
+        return o.view(B, S, H, hd), lse
     o = torch.empty(B, S, H, hd, device=q.device, dtype=BF16)
     lse = torch.empty(B, H, S, device=q.device, dtype=torch.float32)
     d = p = fl = None
@@ -620,6 +674,9 @@ def attn_bwd(q: Tensor, k: Tensor, v: Tensor, o: Tensor, do: Tensor, lse: Tensor
     KVH = k.shape[2]
     for t in (q, k, v, o, do, dq, dk, dv):
         assert t.stride(3) == 1 and t.stride(2) == hd
+    if mask is not None and mask.dense is not None:
+        mask = mask.prepared(B, S, q.device)
+        return attn_mask_bwd(q, k, v, o, do, lse, dq, dk, dv, mask._rows, rope=rope)
     delta = torch.empty(_lib().llx_attn_bwd_workspace_bytes(B, S, H, KVH) // 4, device=q.device, dtype=torch.float32)  # delta + dK/dV partials
     # LLX_ATTN_BWD_DS=1: dS^T scratch (bf16 [B, H, Sp, Sp], 1.07 GB at S = 4096; capped by LLX_ATTN_BWD_DS_MAX_GB, default 16): with it every
     # product of the backward is computed once and dQ becomes a tiled product over the stored dS^T.  Measured at S = 4096: the
@@ -704,10 +761,11 @@ def attn_mask_flags(mask: Tensor, B: int) -> Tensor:
     return fl
 
 
-def attn_mask_fwd(q: Tensor, k: Tensor, v: Tensor, mask: Tensor, out: Optional[Tensor] = None) -> Tensor:
-    """Inference attention with an explicit bool mask broadcast over heads, on the MFMA tile loop of the training forward (KV-cache
-    prefill): q [B,H,Sq,128] as the transposed view of a row buffer (head stride 128), k/v [B,KVH,Skv,128] with any head / position
-    strides (the caches, or views of the q|k|v rows), mask broadcastable to [B,1,Sq,Skv] -> o [B,Sq,H*128], the rows `wo` reads.
+def attn_mask_fwd(q: Tensor, k: Tensor, v: Tensor, mask: Tensor, out: Optional[Tensor] = None, lse: bool = False):
+    """Attention with an explicit bool mask broadcast over heads, on the MFMA tile loop of the training forward (KV-cache prefill, and
+    the forward of training through a dense mask): q [B,H,Sq,128] as the transposed view of a row buffer (head stride 128), k/v
+    [B,KVH,Skv,128] with any head / position strides (the caches, or views of the q|k|v rows), mask broadcastable to [B,1,Sq,Skv]
+    -> o [B,Sq,H*128], the rows `wo` reads; with ``lse=True`` -> (o, lse), lse fp32 [B,H,Sq] in log2 units (what attn_mask_bwd takes).
     The tile classes are computed once per mask tensor (cached on it: every layer of a call shares them).  No host synchronisation."""
     from . import ops  # (ops imports this module)
 
@@ -727,11 +785,44 @@ def attn_mask_fwd(q: Tensor, k: Tensor, v: Tensor, mask: Tensor, out: Optional[T
     if out is None:
         out = torch.empty(B, Sq, H * hd, device=q.device, dtype=BF16)
     assert out.shape == (B, Sq, H * hd) and out.dtype is BF16 and out.stride(2) == 1
+    lse_t = torch.empty(B, H, Sq, device=q.device, dtype=torch.float32) if lse else None
     L.check(_lib().llx_attn_mask_fwd(L.ptr(q), q.stride(0), q.stride(2), L.ptr(k), k.stride(0), k.stride(1), k.stride(2), L.ptr(v), v.stride(0),
-                                     v.stride(1), v.stride(2), L.ptr(out), out.stride(0), out.stride(1), None, L.ptr(m),
+                                     v.stride(1), v.stride(2), L.ptr(out), out.stride(0), out.stride(1), L.ptr(lse_t), L.ptr(m),
                                      m.stride(0) if m.shape[0] != 1 else 0, m.stride(1), L.ptr(fl), B, Sq, Skv, H, KVH, hd, 1.0 / math.sqrt(hd),
                                      L.stream()), "llx_attn_mask_fwd")
-    return out
+    return (out, lse_t) if lse else out
+
+
+def attn_mask_bwd(q: Tensor, k: Tensor, v: Tensor, o: Tensor, do: Tensor, lse: Tensor, dq: Tensor, dk: Tensor, dv: Tensor, mask: Tensor,
+                  rope: Optional[Tensor] = None) -> None:
+    """Backward of attn_mask_fwd with Sq = Skv = S: q / o / do / dq [B,S,H,128], k / v / dk / dv [B,S,KVH,128] (last two dims dense,
+    batch / sequence strides free: views of fused q|k|v rows work), lse [B,H,S] from attn_mask_fwd(..., lse=True), mask bool
+    broadcastable to [B,1,S,S].  rope as in attn_bwd.  A key that no row attends to gets exact zeros in dk / dv.  The tile classes are
+    the ones attn_mask_fwd cached on the mask tensor.  No host synchronisation."""
+    from . import ops  # (ops imports this module)
+
+    _chk_bf16(q, k, v, o, do, dq, dk, dv)
+    L.require_cuda(mask)
+    if rope is not None:
+        assert rope.dtype is torch.float32 and rope.is_contiguous() and rope.shape[0] >= q.shape[1] and rope.shape[1:] == (64, 2)
+    B, S, H, hd = q.shape
+    KVH = k.shape[2]
+    for t in (q, k, v, o, do, dq, dk, dv):
+        assert t.stride(3) == 1 and t.stride(2) == hd
+    assert mask.dtype is torch.bool and mask.shape[-2:] == (S, S) and lse.shape == (B, H, S) and lse.dtype is torch.float32 and lse.is_contiguous()
+    m = _mask_rows(mask, B, S, S)
+    if m is None:
+        raise L.LlxError("attn_mask_bwd: the mask must be broadcast over heads ([B | 1, 1, S, S])")
+    fl = ops._cached(mask, f"maskflags{B}", lambda: attn_mask_flags(mask, B))
+    delta = torch.empty(_lib().llx_attn_bwd_workspace_bytes(B, S, H, KVH) // 4, device=q.device, dtype=torch.float32)  # delta + dK/dV partials
+    ev = _trace_begin(ATTN_TRACE)
+    L.check(_lib().llx_attn_mask_bwd(L.ptr(q), q.stride(0), q.stride(1), L.ptr(k), k.stride(0), k.stride(1), L.ptr(v), v.stride(0), v.stride(1),
+                                     L.ptr(o), o.stride(0), o.stride(1), L.ptr(do), do.stride(0), do.stride(1), L.ptr(lse), L.ptr(delta),
+                                     L.ptr(dq), dq.stride(0), dq.stride(1), L.ptr(dk), dk.stride(0), dk.stride(1), L.ptr(dv), dv.stride(0),
+                                     dv.stride(1), L.ptr(m), m.stride(0) if m.shape[0] != 1 else 0, m.stride(1), L.ptr(fl), L.ptr(rope),
+                                     B, S, H, KVH, hd, 1.0 / math.sqrt(hd), L.stream()),
+            "llx_attn_mask_bwd")
+    _trace_end(ATTN_TRACE, ev, "bwd", B, S, H)
 
 
 # ------------------------------------------------------------------------------------------------- decode path (csrc/decode.hip)

@@ -6,9 +6,10 @@ training scripts can switch packages unchanged.  What differs is below the modul
 a layer is ONE autograd node (llx/ops.py) that calls the HIP kernels of llama-x_amd/csrc through the C-ABI; there
 is no SDPA / FlexAttention / aten matmul on the hot path and no CPU fallback (CPU tensors raise).
 
-``block_mask`` takes a :class:`llx.kernels.MaskSpec` (per-token ``doc_ids`` / per-sample ``prefix_len``) in place of
-FlexAttention's BlockMask; the mask rule is the reference's ``mask_mod`` (train_metamathqa.py:67-68) plus the
-prefix-LM term of README.md:16.
+``block_mask`` takes a :class:`llx.kernels.MaskSpec` in place of FlexAttention's BlockMask: per-token ``doc_ids`` /
+per-sample ``prefix_len`` (the mask rule is the reference's ``mask_mod``, train_metamathqa.py:67-68, plus the prefix-LM
+term of README.md:16), or ``dense=`` any bool mask; ``MaskSpec.from_mask_mod(mask_mod, B, S, device)`` stands where the
+reference calls ``create_block_mask(mask_mod, ...)`` (train_metamathqa.py:70).
 """
 import json
 import os
@@ -139,8 +140,8 @@ def _as_maskspec(block_mask):
     if block_mask is None or isinstance(block_mask, MaskSpec):
         return block_mask
     raise LlxError(
-        "block_mask must be an llx MaskSpec(doc_ids=..., prefix_len=...) - FlexAttention BlockMask objects are not "
-        "dispatched on this platform (the mask rule is evaluated on device from per-token metadata)"
+        "block_mask must be an llx MaskSpec(doc_ids=..., prefix_len=...) or MaskSpec(dense=bool_mask) - FlexAttention BlockMask "
+        "objects are not dispatched on this platform: build the mask with MaskSpec.from_mask_mod(mask_mod, B, S, device)"
     )
 
 
@@ -167,11 +168,12 @@ class Attention(nn.Module):
         if mask is not None and self.kv_cache is None and torch.is_grad_enabled() and (
                 x.requires_grad or any(p.requires_grad for p in self.parameters()) or (norm is not None and norm.weight.requires_grad)):
             # training through the reference's dense-mask route (llama.py:135-137): a mask that the MaskSpec rule reproduces exactly
-            # (causal / prefix-LM / contiguous documents) runs on the fused kernels with their backward; anything else has no backward here
+            # (causal / prefix-LM / contiguous documents) runs on the fused kernels with their backward; anything else trains through
+            # block_mask=MaskSpec(dense=mask) (this route keeps the reference's mask= semantics and does not guess)
             spec = ops._cached(mask, "maskspec", lambda: (K.maskspec_from_dense(mask, x.shape[0], x.shape[1]),))[0]
             if spec is None:
                 raise LlxError("training with a dense mask= needs a mask of the form (k <= q or k < prefix[b]) and same-document "
-                               "(contiguous documents): pass block_mask=MaskSpec(doc_ids=..., prefix_len=...) for anything else")
+                               "(contiguous documents): pass block_mask=MaskSpec(dense=mask) to train through any other bool mask")
             mask, block_mask = None, (spec if (spec.doc_ids is not None or spec.prefix_len is not None) else None)
         if self.kv_cache is not None or mask is not None:
             return self._run_dense(x, rope, norm, residual, mask, input_pos)
@@ -185,10 +187,10 @@ class Attention(nn.Module):
 
     def _run_dense(self, x: Tensor, rope: Tensor, norm, residual: bool, mask, input_pos) -> Tensor:
         """Inference path: KV cache and/or an explicit bool mask (SDPA branch with is_causal=False, llama.py:126-127,135-137).
-        Forward only: training uses block_mask=MaskSpec(...) which has a fused backward."""
+        Forward only: training uses block_mask=MaskSpec(...) - the rule or dense=mask - which has a fused backward."""
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             raise LlxError("dense-mask / KV-cache attention is forward-only here: run it under torch.no_grad() "
-                           "(for training use block_mask=MaskSpec(doc_ids=..., prefix_len=...))")
+                           "(for training use block_mask=MaskSpec(doc_ids=..., prefix_len=...) or MaskSpec(dense=mask))")
         B, L_, _ = x.shape
         H, KVH, hd = self.num_heads, self.num_kv_heads, self.head_dim
         xn = norm(x) if norm is not None else x
