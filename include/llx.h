@@ -325,6 +325,20 @@ int llx_gelu_bwd(const void* dy, int64_t dy_ld, const void* z, int64_t z_ld, voi
 int llx_col2im3(const void* dA, void* dpad, int64_t M, int64_t C, int64_t P, int64_t stride, llx_stream_t s);
 int llx_conv_w_reorder(const void* in, void* out, int64_t D, int64_t C, int to_gemm, llx_stream_t s);
 
+/* ---- token sampler (llx/generate.py; the reference has no generate(): this is the loop behind its `input_pos` branch,
+ *      modelling/llama.py:204-205).  One token for each of R rows of logits [R, V] (dtype 0 = bf16, 1 = fp32; row stride ld >= V elements,
+ *      rows may start at any element): temperature 0 = argmax (lowest index among ties); otherwise z = logit / temperature, top_k
+ *      (0 = off; ties at the k-th value all stay), top_p (1 = off; keep i iff the weight of z_j > z_i is < top_p * W), then the first
+ *      kept index whose running weight exceeds u * W, u = float(mix(mix(mix(seed) ^ pos[r]) ^ r) >> 40) * 2^-24 (splitmix64 finaliser).
+ *      pos: DEVICE int64 [R], the draw counter (read on the device; advance != 0 stores pos + 1 back after the read).  token_out: int64
+ *      [R].  history (nullable): int64 [R, cap], row stride hist_ld; the token goes to history[r, pos[r] - hist_base] when inside
+ *      [0, cap).  finished (nullable, int32 [R]): a row whose flag is set writes eos_id and nothing else; a row that samples eos_id
+ *      sets it.  aux_u / aux_thresh (fp32 [R]) / aux_kept (int32 [R]), nullable: the uniform, the raw logit of the smallest kept
+ *      token, the number of kept tokens (greedy: the maximum and the size of its tie group). --------------------------------- */
+int llx_sample_rows(const void* logits, int dtype, int64_t ld, int64_t R, int64_t V, float temperature, int64_t top_k, float top_p,
+                    uint64_t seed, int64_t* pos, int64_t* token_out, int64_t* history, int64_t hist_ld, int64_t hist_cap, int64_t hist_base,
+                    int advance, int64_t eos_id, int32_t* finished, float* aux_u, float* aux_thresh, int32_t* aux_kept, llx_stream_t s);
+
 /* ---- small utilities of the backward pass ---------------------------------------------------------------------- */
 int llx_scale(const void* x, int64_t x_ld, void* y, int64_t y_ld, const float* dev_scalar, float host_scale, const void* colscale,
               int64_t rows, int64_t cols, llx_stream_t s);   /* (g * scale) of subclasses/int8.py:127; loss-scale of dX */

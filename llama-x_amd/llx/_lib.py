@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_int64, c_void_p
+from ctypes import c_char_p, c_float, c_int, c_int64, c_uint64, c_void_p
 
 import torch  # noqa: F401  (must be imported first: it loads the HIP runtime this library binds to)
 
@@ -101,6 +101,7 @@ SIGNATURES: dict[str, tuple] = {
     "llx_gemm_tn_bf16": (c_int, [_P, _L, _P, _L, _P, _L, _L, _L, _L, _P]),
     "llx_gemm_tn_bf16_rows": (c_int, [_P, _L, _P, _L, _P, _L, _L, _L, _L, _P, _P]),
     "llx_gemm_nt_bf16_rope": (c_int, [_P, _L, _P, _L, _P, _L, _L, _L, _L, _P, _L, _P, _L, _L, _P, _L, _L, _P]),
+    "llx_sample_rows": (c_int, [_P, _I, _L, _L, _L, _F, _L, _F, c_uint64, _P, _P, _P, _L, _L, _L, _I, _L, _P, _P, _P, _P, _P]),
 }
 
 # include/llx_debug.h: diagnostic probes, bound for tools/ only

@@ -952,6 +952,56 @@ def attn_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, mask: Tensor, exten
     return out
 
 
+# ------------------------------------------------------------------------------------------------- token sampler
+def sample(logits: Tensor, *, temperature: float, top_k: int = 0, top_p: float = 1.0, seed: int = 0, pos: Tensor, out: Optional[Tensor] = None,
+           history: Optional[Tensor] = None, hist_base: int = 0, advance: bool = False, eos_id: Optional[int] = None,
+           finished: Optional[Tensor] = None, aux: bool = False):
+    """One token for each row of logits [R, V] or [1, R, V] (bf16 or fp32, last dim dense, any row stride and start offset), in one launch
+    and without a host read: greedy at temperature 0, else temperature / top-k / top-p by the rules of llx/sampling.py.  pos (device int64
+    [R]) is the counter of the random draw; advance stores pos + 1 back.  history (int64 [R, cap]) receives the token at pos - hist_base
+    when that lies inside it.  eos_id with finished (device int32 [R]): finished rows repeat eos_id and touch nothing, a sampled eos_id
+    sets the flag.  Returns the tokens (int64 [R]), with aux=True (tokens, u fp32, threshold logit fp32, kept int32)."""
+    from .sampling import check_params
+
+    check_params(temperature, top_k, top_p, seed)
+    L.require_cuda(logits, pos, out, history, finished)
+    if logits.dim() == 3:
+        if logits.shape[0] != 1:
+            raise L.LlxError(f"sample: logits [B, R, V] need B == 1 (got {tuple(logits.shape)})")
+        logits = logits[0]
+    if logits.dim() != 2 or logits.dtype not in (BF16, torch.float32):
+        raise L.LlxError(f"sample: logits must be bf16 or fp32 [R, V] (got {logits.dtype} {tuple(logits.shape)})")
+    if logits.stride(1) != 1 or (logits.shape[0] > 1 and logits.stride(0) < logits.shape[1]):
+        logits = logits.contiguous()
+    R, V = logits.shape
+    if pos.dtype is not torch.int64 or pos.shape != (R,) or not pos.is_contiguous():
+        raise L.LlxError(f"sample: pos must be a contiguous device int64 [{R}] (got {pos.dtype} {tuple(pos.shape)})")
+    if out is None:
+        out = torch.empty(R, device=logits.device, dtype=torch.int64)
+    elif out.dtype is not torch.int64 or out.numel() != R or not out.is_contiguous():
+        raise L.LlxError(f"sample: out must be a contiguous int64 tensor of {R} elements")
+    h_ld = h_cap = 0
+    if history is not None:
+        if history.dtype is not torch.int64 or history.dim() != 2 or history.shape[0] != R or history.stride(1) != 1:
+            raise L.LlxError(f"sample: history must be int64 [{R}, cap] with a dense last dim")
+        h_ld, h_cap = (history.stride(0) if R > 1 else history.shape[1]), history.shape[1]
+    if (eos_id is None) != (finished is None):
+        raise L.LlxError("sample: eos_id and finished go together")
+    if finished is not None and (finished.dtype is not torch.int32 or finished.shape != (R,) or not finished.is_contiguous()):
+        raise L.LlxError(f"sample: finished must be a contiguous device int32 [{R}]")
+    au = at = ak = None
+    if aux:
+        au = torch.empty(R, device=logits.device, dtype=torch.float32)
+        at = torch.empty(R, device=logits.device, dtype=torch.float32)
+        ak = torch.empty(R, device=logits.device, dtype=torch.int32)
+    L.check(_lib().llx_sample_rows(L.ptr(logits), 0 if logits.dtype is BF16 else 1, logits.stride(0) if R > 1 else V, R, V, float(temperature),
+                                   int(top_k), float(top_p), int(seed), L.ptr(pos), L.ptr(out), L.ptr(history), h_ld, h_cap, int(hist_base),
+                                   1 if advance else 0, int(eos_id) if eos_id is not None else -1, L.ptr(finished), L.ptr(au), L.ptr(at),
+                                   L.ptr(ak), L.stream()), "llx_sample_rows")
+    tokens = out.view(R)
+    return (tokens, au, at, ak) if aux else tokens
+
+
 # ------------------------------------------------------------------------------------------------- cross entropy
 def head_compact_index(labels: Tensor) -> tuple[Tensor, Tensor, Tensor, Tensor]:
     """(idx, inv, labels_c, count) for the labelled rows (labels != -100) in order; everything stays on the device."""

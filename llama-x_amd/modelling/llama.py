@@ -310,6 +310,13 @@ class Llama(nn.Module):
         x = self._run_layers(x, rope, mask=mask, input_pos=input_pos, block_mask=block_mask)
         return self._head(x, labels)
 
+    def generate(self, prompt: Tensor, max_new_tokens: int, **kwargs) -> Tensor:
+        """llx.generate.generate(self, ...): prefill + one forward and one on-device sampler launch per token (the reference has no
+        generate(); its input_pos branch above is what this drives)."""
+        from llx.generate import generate
+
+        return generate(self, prompt, max_new_tokens, **kwargs)
+
     @staticmethod
     def from_hf(model_id: str, **kwargs):
         config = _get_hf_config(model_id)._replace(**kwargs)
