@@ -197,6 +197,26 @@ int llx_mask_extent(const void* mask, int64_t row_stride, int64_t rows, int64_t 
 /* KVCache.update (:83-90): cache[b, h, input_pos[l], :] = src[b, h, l, :] for k and v (sources share strides, caches share strides). */
 int llx_kv_scatter(const void* k, const void* v, int64_t s_sb, int64_t s_sh, int64_t s_ss, void* k_cache, void* v_cache, int64_t c_sb, int64_t c_sh,
                    int64_t c_ss, const int64_t* input_pos, int64_t B, int64_t KVH, int64_t L, int64_t Smax, int64_t head_dim, llx_stream_t s);
+/* KVCache.update for a batch whose sequences sit at their own positions: cache[b, h, input_pos[b, l], :] = src[b, h, l, :]
+ * (input_pos int64 [B, L], row stride p_sb elements).  The kernel of llx_kv_scatter with a position row per batch element. */
+int llx_kv_scatter_rows(const void* k, const void* v, int64_t s_sb, int64_t s_sh, int64_t s_ss, void* k_cache, void* v_cache, int64_t c_sb,
+                        int64_t c_sh, int64_t c_ss, const int64_t* input_pos, int64_t p_sb, int64_t B, int64_t KVH, int64_t L, int64_t Smax,
+                        int64_t head_dim, llx_stream_t s);
+/* The product of llx_gemv_bf16 for 2 <= M <= 16 activation rows (a batch of sequences, one token each) on the matrix pipe:
+ * out = epilogue( [rmsnorm(x) | x][M, K] . [W0; W1; W2]^T ) with v_mfma_f32_16x16x32_bf16 (rows padded to 16 with zeros in registers),
+ * fp32 accumulation, every weight element read from HBM once whatever M is.  bf16 weights without adapters; W_s [n_s, K] row-major
+ * (inner n_s % 16 == 0), K % 8 == 0, K <= 32768.  K is split over workgroups where the tiles alone do not fill the machine; the
+ * fp32 partial tiles go through the workspace (llx_gemm_rows16_workspace_bytes(M, N, K, epilogue) bytes, 16-byte aligned, not shared
+ * with a call on another stream; 0 = no split) and a second small launch sums them in a fixed order and runs the epilogue:
+ * deterministic, repeat calls are bit-identical.
+ * Epilogues 0, 1, 3 as llx_gemv_bf16.  Epilogue 2 (q|k|v) is the BATCHED mode: row m is sequence m at token index 0 of the call, so
+ * apply_rope uses table row 0 on the q and k heads; q -> out [M, n_q]; k / v heads -> cache[m] at pos[m] (device int64 [M]; a position
+ * outside [0, Smax) writes nothing), caches [>= M, KVH, Smax, 128] through (batch, head, position) strides. */
+int64_t llx_gemm_rows16_workspace_bytes(int64_t M, int64_t N, int64_t K, int epilogue);
+int llx_gemm_rows16_bf16(const void* w0, int64_t ldw0, int64_t n0, const void* w1, int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2, int64_t n2,
+                         const void* x, int64_t ldx, int64_t M, int64_t K, const void* norm_w, float eps, int epilogue, void* out, int64_t ldo,
+                         const void* res, int64_t ldr, const float* rope, int64_t n_q, int64_t n_k, void* k_cache, void* v_cache, int64_t c_sb,
+                         int64_t c_sh, int64_t c_ss, int64_t Smax, const int64_t* pos, void* workspace, int64_t workspace_bytes, llx_stream_t s);
 /* SDPA(q, k_cache, v_cache, mask, is_causal=False, enable_gqa=True) (:135-137) for M query tokens with M * H / KVH <= 16: the cache of a
  * kv head is split over `nsplit` workgroups, the heads of its group share every K / V row read; partials merged in a second launch.
  * q / o [B, H, M, 128], caches [B, KVH, Skv, 128] through (batch, head, position) strides; mask bool [.., M, Skv] with broadcast

@@ -604,11 +604,11 @@ extern "C" int llx_mask_extent(const void* mask, int64_t row_stride, int64_t row
 // KVCache.update (modelling/llama.py:83-90): cache[b, h, input_pos[l], :] = src[b, h, l, :] for k and v in one launch.
 __global__ __launch_bounds__(256) void kv_scatter_kernel(const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, int64_t s_sb, int64_t s_sh, int64_t s_ss,
                                                          bf16_t* __restrict__ kc, bf16_t* __restrict__ vc, int64_t c_sb, int64_t c_sh, int64_t c_ss,
-                                                         const int64_t* __restrict__ pos, int L, int KVH, int Smax) {
+                                                         const int64_t* __restrict__ pos, int64_t p_sb, int L, int KVH, int Smax) {
   const int chunk = threadIdx.x & 15, which = (threadIdx.x >> 4) & 1, li = blockIdx.x * 8 + (threadIdx.x >> 5);
   const int h = blockIdx.y, b = blockIdx.z;
   if (li >= L) return;
-  const int64_t p = pos[li];
+  const int64_t p = pos[b * p_sb + li];  // p_sb = 0: one position row for every batch element
   if (p < 0 || p >= Smax) return;  // torch's index_put would raise; an out-of-range position must never write outside the cache
   const bf16_t* src = (which ? v : k) + b * s_sb + h * s_sh + (int64_t)li * s_ss + chunk * 8;
   bf16_t* dst = (which ? vc : kc) + b * c_sb + h * c_sh + p * c_ss + chunk * 8;
@@ -624,8 +624,24 @@ extern "C" int llx_kv_scatter(const void* k, const void* v, int64_t s_sb, int64_
   LLX_REQUIRE(((s_sb | s_sh | s_ss | c_sb | c_sh | c_ss) % 8) == 0 && ((uintptr_t)k | (uintptr_t)v | (uintptr_t)k_cache | (uintptr_t)v_cache) % 16 == 0,
               "llx_kv_scatter: rows must be 16-byte aligned");
   hipLaunchKernelGGL(kv_scatter_kernel, dim3((unsigned)cdiv64(L, 8), (unsigned)KVH, (unsigned)B), dim3(256), 0, stream, (const bf16_t*)k, (const bf16_t*)v,
-                     s_sb, s_sh, s_ss, (bf16_t*)k_cache, (bf16_t*)v_cache, c_sb, c_sh, c_ss, input_pos, (int)L, (int)KVH, (int)Smax);
+                     s_sb, s_sh, s_ss, (bf16_t*)k_cache, (bf16_t*)v_cache, c_sb, c_sh, c_ss, input_pos, (int64_t)0, (int)L, (int)KVH, (int)Smax);
   LLX_LAUNCH_CHECK("llx_kv_scatter");
+  return LLX_OK;
+}
+
+// KVCache.update with a position row per batch element: cache[b, h, input_pos[b, l], :] = src[b, h, l, :] (input_pos int64 [B, L] with
+// row stride p_sb): the sequences of a batch sit at their own positions.  Everything else as llx_kv_scatter.
+extern "C" int llx_kv_scatter_rows(const void* k, const void* v, int64_t s_sb, int64_t s_sh, int64_t s_ss, void* k_cache, void* v_cache, int64_t c_sb,
+                                   int64_t c_sh, int64_t c_ss, const int64_t* input_pos, int64_t p_sb, int64_t B, int64_t KVH, int64_t L, int64_t Smax,
+                                   int64_t head_dim, hipStream_t stream) {
+  LLX_REQUIRE(k && v && k_cache && v_cache && input_pos, "llx_kv_scatter_rows: null pointer");
+  LLX_REQUIRE(head_dim == HD, "llx_kv_scatter_rows: head_dim=%lld unsupported (only 128)", (long long)head_dim);
+  LLX_REQUIRE(B > 0 && KVH > 0 && L > 0 && Smax > 0 && B < 65536 && KVH < 65536 && p_sb >= L, "llx_kv_scatter_rows: bad sizes");
+  LLX_REQUIRE(((s_sb | s_sh | s_ss | c_sb | c_sh | c_ss) % 8) == 0 && ((uintptr_t)k | (uintptr_t)v | (uintptr_t)k_cache | (uintptr_t)v_cache) % 16 == 0,
+              "llx_kv_scatter_rows: rows must be 16-byte aligned");
+  hipLaunchKernelGGL(kv_scatter_kernel, dim3((unsigned)cdiv64(L, 8), (unsigned)KVH, (unsigned)B), dim3(256), 0, stream, (const bf16_t*)k, (const bf16_t*)v,
+                     s_sb, s_sh, s_ss, (bf16_t*)k_cache, (bf16_t*)v_cache, c_sb, c_sh, c_ss, input_pos, p_sb, (int)L, (int)KVH, (int)Smax);
+  LLX_LAUNCH_CHECK("llx_kv_scatter_rows");
   return LLX_OK;
 }
 

@@ -7,7 +7,7 @@ stalled by an `.item()`.  With `eos_id` the host looks at the finished flag once
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import Optional, Sequence
 
 import torch
 from torch import Tensor
@@ -17,7 +17,8 @@ from ._lib import LlxError
 from .sampling import check_params
 
 
-def _check(model, prompt: Tensor, max_new_tokens: int, eos_id, prefill_chunk, check_every) -> None:
+def _check(model, prompt: Tensor, max_new_tokens: int, eos_id, prefill_chunk, check_every, prompt_lens=None) -> Optional[list]:
+    """Raises LlxError on anything generate() cannot run, before any launch; returns the prompt lengths as a list (None: every row is P)."""
     from modelling.llama import Llama
 
     if not isinstance(model, Llama) or type(model)._embed is not Llama._embed:
@@ -26,26 +27,126 @@ def _check(model, prompt: Tensor, max_new_tokens: int, eos_id, prefill_chunk, ch
         raise LlxError("generate() needs the model in eval mode: call model.eval()")
     if any(layer.attention.kv_cache is None for layer in model.layers) or not hasattr(model, "causal_mask"):
         raise LlxError("generate() needs the KV cache: call model.build_cache(inference=True) first")
-    if not (isinstance(prompt, Tensor) and prompt.dtype is torch.int64 and prompt.dim() == 2 and prompt.shape[0] == 1 and prompt.shape[1] >= 1):
-        raise LlxError("generate(): prompt must be an int64 tensor [1, P] with P >= 1 (the KV cache is batch 1)")
+    if not (isinstance(prompt, Tensor) and prompt.dtype is torch.int64 and prompt.dim() == 2 and prompt.shape[0] >= 1 and prompt.shape[1] >= 1):
+        raise LlxError("generate(): prompt must be an int64 tensor [B, P] with B, P >= 1")
+    cache_b = model.layers[0].attention.kv_cache.k_cache.shape[0]
+    if prompt.shape[0] != cache_b:
+        raise LlxError(f"generate(): a batch of {prompt.shape[0]} prompts against a KV cache of batch {cache_b}: "
+                       f"call model.build_cache(inference=True, batch_size={prompt.shape[0]})")
+    lens = None
+    if prompt_lens is not None:
+        lens = prompt_lens.tolist() if isinstance(prompt_lens, Tensor) else list(prompt_lens)  # the one host read of the lengths
+        if len(lens) != prompt.shape[0] or not all(isinstance(v, int) and not isinstance(v, bool) for v in lens):
+            raise LlxError(f"prompt_lens must hold {prompt.shape[0]} integer lengths, one per row of prompt")
+        if not all(1 <= v <= prompt.shape[1] for v in lens):
+            raise LlxError(f"prompt_lens {lens} must lie in [1, {prompt.shape[1]}] (prompt is right-padded to P = {prompt.shape[1]})")
     if not prompt.is_cuda or model.tok_embeddings.weight.device != prompt.device:
         raise LlxError("generate() runs on the HIP device: model and prompt must be on the same GPU")
     if not (isinstance(max_new_tokens, int) and max_new_tokens >= 1):
         raise LlxError(f"max_new_tokens={max_new_tokens!r} must be an integer >= 1")
-    if prompt.shape[1] + max_new_tokens > model.config.max_seq_len:
-        raise LlxError(f"prompt ({prompt.shape[1]}) + max_new_tokens ({max_new_tokens}) exceeds max_seq_len ({model.config.max_seq_len})")
+    longest = max(lens) if lens is not None else prompt.shape[1]
+    if longest + max_new_tokens > model.config.max_seq_len:
+        raise LlxError(f"prompt ({longest}) + max_new_tokens ({max_new_tokens}) exceeds max_seq_len ({model.config.max_seq_len})")
     if eos_id is not None and not (isinstance(eos_id, int) and 0 <= eos_id < model.config.vocab_size):
         raise LlxError(f"eos_id={eos_id!r} must be a token id in [0, {model.config.vocab_size})")
     if prefill_chunk is not None and not (isinstance(prefill_chunk, int) and prefill_chunk >= 1):
         raise LlxError(f"prefill_chunk={prefill_chunk!r} must be None or an integer >= 1")
     if not (isinstance(check_every, int) and check_every >= 1):
         raise LlxError(f"check_every={check_every!r} must be an integer >= 1")
+    return lens
+
+
+# ---- history bookkeeping of a batch with prompts of different lengths (pure: no device, no model)
+def history_plan(lens: Sequence[int], n: int) -> tuple[int, int, list]:
+    """(columns, hist_base, shifts) of the sampler's history buffer for prompt lengths `lens` and `n` new tokens.  The sampler writes the
+    token drawn at counter pos to column pos - hist_base with ONE base for all rows; row b's first draw is at pos = lens[b] - 1, so with
+    hist_base = min(lens) - 1 its k-th token lands in column shifts[b] + k, shifts[b] = lens[b] - min(lens), and max - min + n columns
+    hold every row."""
+    lo = min(lens)
+    return max(lens) - lo + n, lo - 1, [v - lo for v in lens]
+
+
+def history_column(lens: Sequence[int], b: int, k: int) -> int:
+    """Column of the k-th generated token (k = 0 ..) of row b in the history buffer of history_plan."""
+    return lens[b] - min(lens) + k
+
+
+def history_rows(history: Tensor, shifts, counts: Tensor, T: int, pad: int) -> Tensor:
+    """[B, T]: row b of `history` shifted left by shifts[b], its first counts[b] tokens kept and the rest filled with `pad`."""
+    B = history.shape[0]
+    j = torch.arange(T, device=history.device)
+    sh = torch.as_tensor(shifts, device=history.device, dtype=torch.int64).view(B, 1)
+    got = history.gather(1, (sh + j).clamp_(max=history.shape[1] - 1))
+    return torch.where(j < counts.view(B, 1), got, torch.full_like(got, pad))
+
+
+@torch.no_grad()
+def prefill(model, prompt: Tensor, prompt_lens: Optional[Sequence[int]] = None, prefill_chunk: Optional[int] = None) -> Tensor:
+    """Fill the KV cache from `prompt` (int64 [B, P], right-padded; B = the cache's batch) and return the logits [B, 1, V] of each
+    sequence's last prompt token (row prompt_lens[b] - 1).  Positions 0 .. P-1 are shared by the batch: under the causal mask no
+    prompt token attends to a pad, which comes later, and the keys and values a pad leaves at positions >= prompt_lens[b] are
+    overwritten by sequence b's own decode step at that position before anything attends to them.  The [B, P, V] logits are never
+    built: the layers run, one hidden row per sequence is gathered, the head runs on [B, 1, D]."""
+    if prompt_lens is not None:
+        prompt_lens = prompt_lens.tolist() if isinstance(prompt_lens, Tensor) else list(prompt_lens)
+        prompt = prompt[:, : max(prompt_lens)]  # columns that are padding in every row are not run (P may exceed max_seq_len, the prompts may not)
+    dev, (B, P) = prompt.device, prompt.shape
+    chunk = P if prefill_chunk is None else prefill_chunk
+    positions = torch.arange(P, device=dev)
+    last = (torch.tensor(prompt_lens, device=dev, dtype=torch.int64) if prompt_lens is not None else torch.full((B,), P, device=dev)) - 1
+    hidden = None
+    table = model.rope  # a chunk runs with the table shifted to its first position (see generate below)
+    try:
+        for s in range(0, P, chunk):
+            model.rope = table[s:]
+            h = model._hidden(prompt[:, s : s + chunk], positions[s : s + chunk])  # [B, c, D]
+            c = h.shape[1]
+            idx = (last - s).clamp(0, c - 1).view(B, 1, 1).expand(B, 1, h.shape[2])
+            rows = h.gather(1, idx)
+            inside = ((last >= s) & (last < s + c)).view(B, 1, 1)
+            hidden = rows if hidden is None else torch.where(inside, rows, hidden)
+    finally:
+        model.rope = table
+    return model._head(hidden.contiguous(), None)
+
+
+def _generate_batch(model, prompt: Tensor, n: int, lens: list, sampling: dict, eos_id, prefill_chunk, check_every: int) -> Tensor:
+    dev, B = prompt.device, prompt.shape[0]
+    logits = prefill(model, prompt, lens, prefill_chunk)
+    cols, base, shifts = history_plan(lens, n)
+    start = torch.tensor(lens, device=dev, dtype=torch.int64) - 1
+    pos = start.clone()  # per row: the position of the logits row being sampled from = the draw counter; the sampler advances it
+    tok = torch.empty(B, 1, device=dev, dtype=torch.int64)
+    history = torch.zeros(B, cols, device=dev, dtype=torch.int64)
+    finished = torch.zeros(B, device=dev, dtype=torch.int32) if eos_id is not None else None
+    kw = dict(**sampling, pos=pos, out=tok.view(B), history=history, hist_base=base, advance=True, eos_id=eos_id, finished=finished)
+    K.sample(logits[:, 0], **kw)
+    T = n
+    for k in range(1, n + 1):
+        if finished is not None and (k % check_every == 0 or k == n):
+            # one host read: a finished row stops advancing, so pos - start is every row's length (eos included); all rows finished
+            # or the budget used up ends the loop, and the longest row is the width of the result
+            state = int(((pos - start).max() * 2 + finished.min()).item())
+            if state & 1 or k == n:
+                T = state >> 1
+                break
+        if k == n:
+            break
+        # a finished row feeds eos_id at its frozen position: it re-writes its own cache row there, nothing else
+        K.sample(model(tok, input_pos=pos[:, None])[:, 0], **kw)
+    counts = pos - start if finished is not None else torch.full((B,), n, device=dev, dtype=torch.int64)
+    return history_rows(history, shifts, counts, T, eos_id if eos_id is not None else 0)
 
 
 @torch.no_grad()
 def generate(model, prompt: Tensor, max_new_tokens: int, *, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
-             eos_id: Optional[int] = None, prefill_chunk: Optional[int] = None, check_every: int = 16) -> Tensor:
-    """Continue `prompt` (int64 [1, P]) by up to `max_new_tokens` tokens -> int64 [1, n_new] on the prompt's device.
+             eos_id: Optional[int] = None, prefill_chunk: Optional[int] = None, check_every: int = 16, prompt_lens=None) -> Tensor:
+    """Continue `prompt` (int64 [B, P], B = the batch the KV cache was built for) by up to `max_new_tokens` tokens -> int64 [B, n_new] on
+    the prompt's device.  `prompt_lens` (B lengths in [1, P], a sequence or an int64 tensor, read once on the host before the first
+    launch): the rows of `prompt` are right-padded prompts of these lengths; default: every row is P long.  For a batch the result is as
+    wide as the longest row; with `eos_id` a row that ended earlier is padded with `eos_id`, and the loop stops when every row has
+    ended.  The draw also takes the row index, and row r does not depend on what the other rows hold.  The decode steps of 2..16 sequences
+    with bf16 un-adapted linears stream every weight once for the whole batch (llx/decode.py); anything else runs the generic path.
 
     The draw for the token at absolute position q uses the counter q - 1 (the position of the logits row it is sampled from), so the
     same arguments give the same tokens whatever `prefill_chunk` and `check_every` are.  With `eos_id` the result ends at the first
@@ -57,8 +158,11 @@ def generate(model, prompt: Tensor, max_new_tokens: int, *, temperature: float =
     than nothing.  While a prefill chunk runs, `model.rope` is a shifted view of the table (restored before the first decode step, also
     on an exception): do not drive the same model from another thread meanwhile."""
     check_params(temperature, top_k, top_p, seed)
-    _check(model, prompt, max_new_tokens, eos_id, prefill_chunk, check_every)
+    lens = _check(model, prompt, max_new_tokens, eos_id, prefill_chunk, check_every, prompt_lens)
     dev, P, n = prompt.device, prompt.shape[1], max_new_tokens
+    if prompt.shape[0] > 1 or (lens is not None and lens != [P]):
+        return _generate_batch(model, prompt, n, lens if lens is not None else [P] * prompt.shape[0],
+                               dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed), eos_id, prefill_chunk, check_every)
     chunk = P if prefill_chunk is None else prefill_chunk
     positions = torch.arange(P, device=dev)
     # forward rotates a call's tokens by rope[:L] whatever input_pos says (the reference's modelling/llama.py:207).  For one whole-prompt

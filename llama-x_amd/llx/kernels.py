@@ -894,6 +894,49 @@ def gemv(ws: Sequence[Tensor], x: Tensor, *, norm: Optional[tuple[Tensor, float]
     return out
 
 
+_ROWS16_WS: dict = {}
+
+
+def gemm_rows16(ws: Sequence[Tensor], x: Tensor, *, norm: Optional[tuple[Tensor, float]] = None, epilogue: int = GV_NONE, out: Optional[Tensor] = None,
+                res: Optional[Tensor] = None, qkv: Optional[tuple] = None) -> Tensor:
+    """gemv's product for 2 <= M = x.shape[0] <= 16 rows - a batch of sequences, one token each - on the matrix pipe (llx_gemm_rows16_bf16):
+    the weights stream once whatever M is.  bf16 weights without adapters; norm, res and the GV_* epilogues as gemv, except GV_QKV, which
+    is the batched mode: qkv = (rope_table, n_q, n_k, k_cache, v_cache, pos) with caches [B >= M, KVH, Smax, 128] and pos int64 [M]; row m
+    is rotated by table row 0 and its k / v heads go to cache[m] at pos[m]; returns q [M, n_q]."""
+    _chk_bf16(x, *ws)
+    M, Kd = x.shape
+    assert 1 <= len(ws) <= 3 and all(w.dim() == 2 and w.shape[1] == Kd and w.stride(1) == 1 for w in ws) and x.stride(1) == 1
+    ns = [w.shape[0] for w in ws] + [0] * (3 - len(ws))
+    N = sum(ns)
+    wp = [L.ptr(w) for w in ws] + [None] * (3 - len(ws))
+    lw = [w.stride(0) for w in ws] + [0] * (3 - len(ws))
+    n_out = {GV_NONE: N, GV_RESIDUAL: N, GV_QKV: qkv[1] if qkv else 0, GV_SWIGLU: ns[0]}[epilogue]
+    if out is None:
+        out = torch.empty(M, n_out, device=x.device, dtype=BF16)
+    assert out.shape == (M, n_out) and out.stride(1) == 1
+    nw, eps = (norm[0], float(norm[1])) if norm is not None else (None, 0.0)
+    rope = kc = vc = pos = None
+    n_q = n_k = c_sb = c_sh = c_ss = smax = 0
+    if epilogue == GV_QKV:
+        rope, n_q, n_k, kc, vc, pos = qkv
+        assert rope.dtype is torch.float32 and rope.is_contiguous() and rope.shape[0] >= 1 and rope.shape[1:] == (64, 2)
+        assert kc.shape == vc.shape and kc.dim() == 4 and kc.shape[0] >= M and kc.shape[3] == 128 and kc.stride() == vc.stride() and kc.stride(3) == 1
+        assert pos.dtype is torch.int64 and pos.shape == (M,) and pos.is_contiguous() and pos.is_cuda
+        c_sb, c_sh, c_ss, smax = kc.stride(0), kc.stride(1), kc.stride(2), kc.shape[2]
+    if epilogue == GV_RESIDUAL:
+        assert res is not None and res.shape == (M, N) and res.stride(1) == 1 and res.dtype is BF16
+    nbytes = _lib().llx_gemm_rows16_workspace_bytes(M, N, Kd, epilogue)
+    key = (x.device, torch.cuda.current_stream(x.device).cuda_stream)
+    wsp = _ROWS16_WS.get(key)
+    if wsp is None or wsp.numel() < nbytes:
+        wsp = _ROWS16_WS[key] = torch.empty(max(nbytes, 1 << 20), device=x.device, dtype=torch.uint8)
+    L.check(_lib().llx_gemm_rows16_bf16(wp[0], lw[0], ns[0], wp[1], lw[1], ns[1], wp[2], lw[2], ns[2], L.ptr(x), x.stride(0), M, Kd, L.ptr(nw), eps,
+                                        epilogue, L.ptr(out), out.stride(0), L.ptr(res), res.stride(0) if res is not None else 0, L.ptr(rope), n_q,
+                                        n_k, L.ptr(kc), L.ptr(vc), c_sb, c_sh, c_ss, smax, L.ptr(pos), L.ptr(wsp), wsp.numel(), L.stream()),
+            "llx_gemm_rows16_bf16")
+    return out
+
+
 def mask_extent(mask: Tensor) -> Tensor:
     """Device int32 [1]: 1 + the largest key index any row of the bool mask [..., Skv] allows (0 if none)."""
     L.require_cuda(mask)
@@ -907,13 +950,19 @@ def mask_extent(mask: Tensor) -> Tensor:
 
 
 def kv_scatter(k: Tensor, v: Tensor, k_cache: Tensor, v_cache: Tensor, input_pos: Tensor) -> None:
-    """k_cache[:, :, input_pos] = k ; v_cache[:, :, input_pos] = v  (KVCache.update, modelling/llama.py:83-90); k / v [B, KVH, L, 128] views."""
+    """k_cache[:, :, input_pos] = k ; v_cache[:, :, input_pos] = v  (KVCache.update, modelling/llama.py:83-90); k / v [B, KVH, L, 128] views.
+    input_pos [L], or [B, L]: sequence b at its own positions, cache[b, :, input_pos[b, l]] = k[b, :, l] (llx_kv_scatter_rows)."""
     _chk_bf16(k, v, k_cache, v_cache)
     L.require_cuda(input_pos)
     B, KVH, Lq, hd = k.shape
     assert v.shape == k.shape and k.stride() == v.stride() and k.stride(3) == 1 and k_cache.stride() == v_cache.stride() and k_cache.stride(3) == 1
-    assert k_cache.shape[0] == B and k_cache.shape[1] == KVH and k_cache.shape[3] == hd and input_pos.shape == (Lq,)
+    assert k_cache.shape[0] == B and k_cache.shape[1] == KVH and k_cache.shape[3] == hd and input_pos.shape in ((Lq,), (B, Lq))
     pos = input_pos.to(torch.int64).contiguous()
+    if pos.dim() == 2:
+        L.check(_lib().llx_kv_scatter_rows(L.ptr(k), L.ptr(v), k.stride(0), k.stride(1), k.stride(2), L.ptr(k_cache), L.ptr(v_cache), k_cache.stride(0),
+                                           k_cache.stride(1), k_cache.stride(2), L.ptr(pos), pos.stride(0), B, KVH, Lq, k_cache.shape[2], hd,
+                                           L.stream()), "llx_kv_scatter_rows")
+        return
     L.check(_lib().llx_kv_scatter(L.ptr(k), L.ptr(v), k.stride(0), k.stride(1), k.stride(2), L.ptr(k_cache), L.ptr(v_cache), k_cache.stride(0),
                                   k_cache.stride(1), k_cache.stride(2), L.ptr(pos), B, KVH, Lq, k_cache.shape[2], hd, L.stream()), "llx_kv_scatter")
 

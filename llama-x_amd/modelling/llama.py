@@ -126,10 +126,14 @@ class KVCache(nn.Module):
         self.register_buffer("v_cache", torch.zeros(shape, dtype=dtype), persistent=False)
 
     def update(self, input_pos: Tensor, k: Tensor, v: Tensor):
-        # input_pos: [S], k/v: [B, KVH, S, hd]
-        assert input_pos.shape[0] == k.shape[2], (input_pos.shape, k.shape)
+        # input_pos: [S], or [B, S] (sequence b at its own positions); k/v: [B, KVH, S, hd]
+        assert input_pos.shape[-1] == k.shape[2], (input_pos.shape, k.shape)
         if k.is_cuda and k.dtype is torch.bfloat16 and k.shape[0] == self.k_cache.shape[0] and k.stride() == v.stride() and k.stride(3) == 1:
             K.kv_scatter(k, v, self.k_cache, self.v_cache, input_pos)  # both caches from one HIP launch, straight from the q|k|v buffer's views
+        elif input_pos.dim() == 2:
+            for b in range(k.shape[0]):
+                self.k_cache[b, :, input_pos[b]] = k[b]
+                self.v_cache[b, :, input_pos[b]] = v[b]
         else:
             self.k_cache[:, :, input_pos] = k
             self.v_cache[:, :, input_pos] = v
@@ -275,11 +279,15 @@ class Llama(nn.Module):
         self.output = Linear(config.embed_dim, config.vocab_size, bias=False)
         self.config = config
 
-    def build_cache(self, inference: bool = False):
+    def build_cache(self, inference: bool = False, batch_size: int = 1):
+        """The RoPE table and, for inference, a KV cache of `batch_size` sequences per layer (the reference's KVCache, update() and
+        Attention.forward are written for a batch; only its build_cache fixes the batch at 1)."""
         self.register_buffer("rope", build_rope(self.config), persistent=False)
         if inference:
+            if not (isinstance(batch_size, int) and batch_size >= 1):
+                raise LlxError(f"build_cache: batch_size={batch_size!r} must be an integer >= 1")
             for layer in self.layers:
-                layer.attention.kv_cache = KVCache(1, self.config, self.tok_embeddings.weight.dtype)
+                layer.attention.kv_cache = KVCache(batch_size, self.config, self.tok_embeddings.weight.dtype)
             L = self.config.max_seq_len
             self.register_buffer("causal_mask", torch.tril(torch.ones(L, L, dtype=torch.bool)), persistent=False)
 
@@ -303,16 +311,32 @@ class Llama(nn.Module):
         """(hidden states [B, S, D], number of leading positions that are dropped before the head)."""
         return self.tok_embeddings(x), 0
 
-    def forward(self, x: Tensor, *, input_pos: Tensor | None = None, block_mask=None, labels: Tensor | None = None) -> Tensor:
-        mask = self.causal_mask[None, None, input_pos] if input_pos is not None else None  # inference path (generate)
+    def _hidden(self, x: Tensor, input_pos: Tensor | None = None, block_mask=None) -> Tensor:
+        """forward() up to the head: the hidden states [B, S, D] after the last layer."""
+        mask = None
+        if input_pos is not None:  # inference path (generate)
+            cache = self.layers[0].attention.kv_cache if len(self.layers) else None
+            if cache is not None and x.shape[0] != cache.k_cache.shape[0]:
+                raise LlxError(f"batch of {x.shape[0]} against a KV cache of batch {cache.k_cache.shape[0]}: "
+                               f"call build_cache(inference=True, batch_size={x.shape[0]})")
+            if input_pos.dim() == 2:
+                # [B, L]: sequence b writes its keys and values at input_pos[b] and attends through causal_mask[input_pos[b]]
+                if input_pos.shape[0] != x.shape[0]:
+                    raise LlxError(f"input_pos {tuple(input_pos.shape)} must be [L] or [B, L] with B = {x.shape[0]}")
+                mask = self.causal_mask[input_pos][:, None]  # [B, 1, L, Skv]
+            else:
+                mask = self.causal_mask[None, None, input_pos]
         x, _ = self._embed(x)
         rope = self.rope[: x.shape[1]]
-        x = self._run_layers(x, rope, mask=mask, input_pos=input_pos, block_mask=block_mask)
-        return self._head(x, labels)
+        return self._run_layers(x, rope, mask=mask, input_pos=input_pos, block_mask=block_mask)
+
+    def forward(self, x: Tensor, *, input_pos: Tensor | None = None, block_mask=None, labels: Tensor | None = None) -> Tensor:
+        return self._head(self._hidden(x, input_pos, block_mask), labels)
 
     def generate(self, prompt: Tensor, max_new_tokens: int, **kwargs) -> Tensor:
         """llx.generate.generate(self, ...): prefill + one forward and one on-device sampler launch per token (the reference has no
-        generate(); its input_pos branch above is what this drives)."""
+        generate(); its input_pos branch above is what this drives).  prompt [B, P] with B the cache's batch; prompt_lens=... for
+        right-padded prompts of different lengths."""
         from llx.generate import generate
 
         return generate(self, prompt, max_new_tokens, **kwargs)
