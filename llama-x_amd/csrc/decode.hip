@@ -17,26 +17,16 @@
 // bytes sign-extended to fp32, EPI_COLSCALE's rounding points) and dynamic (the prologue quantises the activation rows as
 // int8_quant.hip does, v_dot4c_i32_i8 into int32, EPI_ROWCOLSCALE's dequantisation).
 // HBM-bound: the step moves (weights + live K/V) bytes once; bench.py --config decode reports that against the 8 TB/s peak.
-#include "common.h"
+// The operand block, the norm-on-load pieces, the epilogues and the host-side operand checks of gemv_kernel are wstream.h's, shared
+// with the batched stream of decode_rows.hip.
+#include "wstream.h"
 #include <type_traits>
 
-#define HD 128
-
 // ------------------------------------------------------------------------------------------------- weight-streaming GEMV
-enum { GV_NONE = 0, GV_RESIDUAL = 1, GV_QKV = 2, GV_SWIGLU = 3 };
 // weight kind: bf16 | int8 rows x bf16 activations (weight-only) | int8 rows x int8 activations quantised in the prologue (dynamic)
 enum { WK_BF16 = 0, WK_I8W = 1, WK_I8D = 2 };
 
-struct GemvArgs {
-  const bf16_t* W[3]; int64_t ldw[3]; int seg_end[3];  // output rows [seg_end[s-1], seg_end[s]) come from W[s] (row-major [rows, K])
-  const bf16_t* x; int64_t ldx;                         // [M, K]
-  const bf16_t* norm_w; float eps;                      // NORM: x <- rmsnorm(x) * norm_w, rounded to bf16 (nn.RMSNorm, single rounding)
-  int M, N, K;
-  bf16_t* out; int64_t ldo;                             // NONE / RESIDUAL: [M, N]; QKV: q rows [M, n_q]; SWIGLU: h [M, N / 2]
-  const bf16_t* res; int64_t ldr;                       // RESIDUAL: [M, N]
-  const float* rope; int n_q, n_k;                      // QKV: rows [0, n_q) = q heads, [n_q, n_q + n_k) = k heads, then v; table [>= M, 64, 2]
-  bf16_t* kc; bf16_t* vc; int64_t c_sh, c_ss;           //      caches [KVH, Smax, 128] through (head, position) strides
-  const int64_t* pos;                                   //      input_pos[M]
+struct GemvArgs : StreamArgs {  // QKV: table row m and cache position pos[m] for activation row m, caches of batch 1
   // LoRA (modelling/lora.py:43): out += scale * (t . Bext[row]) with t = x . A^T computed by a previous launch of this kernel
   const bf16_t* bext[3]; int64_t ldb[3]; int t_off[3]; int rank[3];
   const bf16_t* t; int64_t ldt; float lora_scale;
@@ -171,38 +161,23 @@ __global__ __launch_bounds__(256, 2) void gemv_kernel(const GemvArgs a) {
     float rstd = 1.f;
     if constexpr (NORM) {
       float ss = 0.f;
-      for (int i = tid * 8; i < K; i += 2048) {
-        const u32x4_t v = *reinterpret_cast<const u32x4_t*>(xr + i);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) ss += bflo(v[e]) * bflo(v[e]) + bfhi(v[e]) * bfhi(v[e]);
-      }
+      for (int i = tid * 8; i < K; i += 2048) ss = sumsq8(*reinterpret_cast<const u32x4_t*>(xr + i), ss);
       ss = block_sum(ss, red);
       rstd = rsqrtf(ss / (float)K + a.eps);
     }
+    // 8 elements of the (normalised, bf16-rounded) row: what the linear of the reference sees
+    auto xrow8 = [&](int i) -> u32x4_t {
+      const u32x4_t v = *reinterpret_cast<const u32x4_t*>(xr + i);
+      if constexpr (NORM) return norm8(v, rstd, a.norm_w + i);
+      else return v;
+    };
     if constexpr (WK == WK_BF16) {
       for (int i = tid * 8; i < Kp; i += 2048) {
         u32x4_t v = {0u, 0u, 0u, 0u};
-        if (i < K) {
-          v = *reinterpret_cast<const u32x4_t*>(xr + i);
-          if constexpr (NORM) {
-            const u32x4_t w = *reinterpret_cast<const u32x4_t*>(a.norm_w + i);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = pack_bf2(bflo(v[e]) * rstd * bflo(w[e]), bfhi(v[e]) * rstd * bfhi(w[e]));
-          }
-        }
+        if (i < K) v = xrow8(i);
         *reinterpret_cast<u32x4_t*>(xs + (size_t)m * Kp + i) = v;
       }
     } else {
-      // 8 elements of the (normalised, bf16-rounded) row: what the linear of the reference sees
-      auto xrow8 = [&](int i) -> u32x4_t {
-        u32x4_t v = *reinterpret_cast<const u32x4_t*>(xr + i);
-        if constexpr (NORM) {
-          const u32x4_t w = *reinterpret_cast<const u32x4_t*>(a.norm_w + i);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = pack_bf2(bflo(v[e]) * rstd * bflo(w[e]), bfhi(v[e]) * rstd * bfhi(w[e]));
-        }
-        return v;
-      };
       if constexpr (WK == WK_I8W) {
         for (int i = tid * 8; i < Kp; i += 2048) {
           u32x4_t v = {0u, 0u, 0u, 0u};
@@ -348,44 +323,9 @@ __global__ __launch_bounds__(256, 2) void gemv_kernel(const GemvArgs a) {
           if (any_lora) v[r] = bf2f(f2bf(v[r] + ls));
         }
       }
+      // q|k|v: the table row is the token's index IN THIS CALL (modelling/llama.py:207); the position is not checked against the cache
       const int m = lane;
-      if constexpr (EPI == GV_SWIGLU) {
-        // h = silu(g) * u with the roundings of the bf16 eager graph (modelling/llama.py:150-152), as swiglu_fwd8
-        const int half = a.N / 2;
-#pragma unroll
-        for (int j = 0; j < UPG; ++j) {
-          const float gg = v[j], uu = v[UPG + j];
-          const float sg = bf2f(f2bf(gg * sigmoidf_(gg)));
-          if (row0 + j < half) a.out[(int64_t)m * a.ldo + row0 + j] = f2bf(sg * uu);
-        }
-      } else if constexpr (EPI == GV_QKV) {
-        // apply_rope on q and k (modelling/llama.py:63-73,122-123; the table row is the token's index IN THIS CALL, :207), then
-        // KVCache.update (:83-90) for k and v
-        const bool is_q = row0 < a.n_q, is_k = !is_q && row0 < a.n_q + a.n_k;
-        const int hrow = is_q ? row0 : (is_k ? row0 - a.n_q : row0 - a.n_q - a.n_k);
-        const int d = hrow & (HD - 1);
-        if (is_q || is_k) {
-          const float* tp = a.rope + ((int64_t)m * 64 + (d >> 1)) * 2;
-          const float c0 = tp[0], s0 = tp[1], c1 = RPW == 4 ? tp[2] : 1.f, s1 = RPW == 4 ? tp[3] : 0.f;
-          const float y0 = v[0] * c0 - v[1] * s0, y1 = v[1] * c0 + v[0] * s0, y2 = v[2] * c1 - v[3] * s1, y3 = v[3] * c1 + v[2] * s1;
-          v[0] = y0; v[1] = y1; v[2] = y2; v[3] = y3;
-        }
-        u32x2_t pk;
-        pk[0] = pack_bf2(v[0], v[1]);
-        pk[1] = pack_bf2(v[2], v[3]);
-        bf16_t* dst = is_q ? a.out + (int64_t)m * a.ldo + row0 : (is_k ? a.kc : a.vc) + (int64_t)(hrow >> 7) * a.c_sh + a.pos[m] * a.c_ss + d;
-        if constexpr (RPW == 4) *reinterpret_cast<u32x2_t*>(dst) = pk;
-        else *reinterpret_cast<uint32_t*>(dst) = pk[0];  // one rotation pair
-      } else {
-#pragma unroll
-        for (int r = 0; r < RPW; ++r) {
-          if (row0 + r < a.N) {
-            float o = v[r];
-            if constexpr (EPI == GV_RESIDUAL) o += bf2f(a.res[(int64_t)m * a.ldr + row0 + r]);  // bf16 output + bf16 residual, rounded
-            a.out[(int64_t)m * a.ldo + row0 + r] = f2bf(o);
-          }
-        }
-      }
+      stream_epilogue<EPI, RPW>(a, row0, m, a.rope + (int64_t)m * 128, [&] { return a.pos[m] * a.c_ss; }, v);
     }
 #pragma unroll
     for (int r = 0; r < RPW; ++r)
@@ -453,9 +393,8 @@ static int launch_gemv_mt(const GemvArgs& a, int MT, int epi, int grid, size_t l
 // out[M, N] = epilogue( x[M, K] . [W0; W1; W2]^T ), M <= 4, bf16, fp32 accumulate; F.linear at decode shapes
 // (modelling/llama.py:118-120,140,152,216).  W_s: [n_s, K] row-major with row stride ldw_s (nullable from s = 1 on; n_s % 4 == 0 except
 // the last), K % 8 == 0.  norm_w (nullable): x is RMS-normalised with this weight first (llama.py:172-173,215).
-// epilogue 0: out [M, N] | 1: + res [M, N] | 2 (q|k|v): rows [0, n_q) RoPE -> out [M, n_q]; [n_q, n_q + n_k) RoPE -> k cache;
-// rest -> v cache, at input_pos[m] (device int64), caches through (head, position) strides | 3 (gate|up = W0|W1, N = 2 n_0):
-// out [M, N/2] = silu(gate) * up.  LoRA (nullable bext_s [n_s, rank_s], t [M, sum rank] bf16 = x . A^T, offsets t_off_s, scale):
+// The epilogues are wstream.h's; q|k|v rotates row m by table row m and writes its k / v heads at input_pos[m] (device int64), caches
+// through (head, position) strides.  LoRA (nullable bext_s [n_s, rank_s], t [M, sum rank] bf16 = x . A^T, offsets t_off_s, scale):
 // out += scale * t_s . bext_s[row].
 // the two entry points below: fn = the caller's name for messages, wk = weight kind, ws_s = per-row scales of W_s (int8 kinds)
 static int gemv_run(const char* fn, int wk, const void* ws0, const void* ws1, const void* ws2, const void* w0, int64_t ldw0, int64_t n0, const void* w1, int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2,
@@ -464,39 +403,18 @@ static int gemv_run(const char* fn, int wk, const void* ws0, const void* ws1, co
                              void* v_cache, int64_t c_sh, int64_t c_ss, const int64_t* input_pos, const void* bext0, const void* bext1,
                              const void* bext2, int64_t rank0, int64_t rank1, int64_t rank2, const void* t, int64_t ldt, float lora_scale,
                     hipStream_t stream) {
-  LLX_REQUIRE(w0 && x && out, "%s: null pointer", fn);
-  LLX_REQUIRE(M >= 1 && M <= 4, "%s: M=%lld outside 1..4 (larger row counts run the MFMA GEMM)", fn, (long long)M);
-  const int wa = wk == WK_BF16 ? 8 : 16;  // weight elements per 16-byte lane load: K and the weight row strides are multiples of it
-  LLX_REQUIRE(K > 0 && K % wa == 0 && K <= 32768, "%s: K=%lld must be a multiple of %d and at most 32768", fn, (long long)K, wa);
-  LLX_REQUIRE(n0 > 0 && n1 >= 0 && n2 >= 0 && (w1 || n1 == 0) && (w2 || n2 == 0), "%s: bad segment sizes", fn);
-  LLX_REQUIRE((n1 == 0 || n0 % 4 == 0) && (n2 == 0 || n1 % 4 == 0), "%s: inner segment sizes must be multiples of 4", fn);
-  LLX_REQUIRE(ldw0 % wa == 0 && ldw1 % wa == 0 && ldw2 % wa == 0 && ldx % 8 == 0, "%s: row strides must be multiples of 16 bytes", fn);
+  const int wa = wk == WK_BF16 ? 8 : 16;  // weight elements per 16-byte lane load
+  GemvArgs a;
+  const int rc0 = stream_check_fill(fn, a, 1, 4, "larger row counts run the MFMA GEMM", wa, 4, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps,
+                                    epilogue, out, ldo, res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sh, c_ss, input_pos);
+  if (rc0 != LLX_OK) return rc0;
   LLX_REQUIRE(wk == WK_BF16 || (ws0 && (ws1 || n1 == 0) && (ws2 || n2 == 0)), "%s: null scale (every int8 weight needs its per-row scales)", fn);
   LLX_REQUIRE(((uintptr_t)ws0 | (uintptr_t)ws1 | (uintptr_t)ws2) % 2 == 0, "%s: scale pointers must be 2-byte aligned", fn);
-  LLX_REQUIRE(((uintptr_t)w0 | (uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)x | (uintptr_t)norm_w) % 16 == 0, "%s: pointers must be 16-byte aligned", fn);
-  LLX_REQUIRE(epilogue >= GV_NONE && epilogue <= GV_SWIGLU, "%s: unknown epilogue %d", fn, epilogue);
-  const int64_t N = n0 + n1 + n2;
-  LLX_REQUIRE(N < (1 << 30), "%s: too many rows", fn);
-  LLX_REQUIRE(epilogue != GV_RESIDUAL || res, "%s: residual missing", fn);
-  LLX_REQUIRE(epilogue != GV_SWIGLU || (n0 == n1 && n2 == 0 && w1), "%s: the SwiGLU epilogue takes gate and up weights of equal size", fn);
-  LLX_REQUIRE(epilogue != GV_QKV || (rope && k_cache && v_cache && input_pos && n_q % HD == 0 && n_k % HD == 0 && (N - n_q - n_k) % HD == 0 &&
-                                     n_q + n_k <= N && (uintptr_t)rope % 8 == 0 && ((uintptr_t)out | (uintptr_t)k_cache | (uintptr_t)v_cache) % 8 == 0 &&
-                                     ldo % 4 == 0 && c_sh % 4 == 0 && c_ss % 4 == 0),
-              "%s: bad q|k|v epilogue arguments", fn);
   const bool lora = bext0 || bext1 || bext2;
   LLX_REQUIRE(!lora || (t && ldt % 8 == 0 && (uintptr_t)t % 16 == 0 && rank0 % 8 == 0 && rank1 % 8 == 0 && rank2 % 8 == 0 && rank0 <= 512 && rank1 <= 512 &&
                         rank2 <= 512 && ((uintptr_t)bext0 | (uintptr_t)bext1 | (uintptr_t)bext2) % 16 == 0),
               "%s: bad LoRA operands (ranks must be multiples of 8, at most 512)", fn);
-  GemvArgs a;
-  a.W[0] = (const bf16_t*)w0; a.W[1] = (const bf16_t*)(w1 ? w1 : w0); a.W[2] = (const bf16_t*)(w2 ? w2 : w0);
-  a.ldw[0] = ldw0; a.ldw[1] = w1 ? ldw1 : ldw0; a.ldw[2] = w2 ? ldw2 : ldw0;
-  a.seg_end[0] = (int)n0; a.seg_end[1] = (int)(n0 + n1); a.seg_end[2] = (int)N;
-  if (n1 == 0) { a.seg_end[0] = a.seg_end[1] = (int)N; }       // single source: every row is segment 0
-  else if (n2 == 0) { a.seg_end[1] = (int)N; }
-  a.x = (const bf16_t*)x; a.ldx = ldx; a.norm_w = (const bf16_t*)norm_w; a.eps = eps;
-  a.M = (int)M; a.N = (int)N; a.K = (int)K;
-  a.out = (bf16_t*)out; a.ldo = ldo; a.res = (const bf16_t*)res; a.ldr = ldr;
-  a.rope = rope; a.n_q = (int)n_q; a.n_k = (int)n_k; a.kc = (bf16_t*)k_cache; a.vc = (bf16_t*)v_cache; a.c_sh = c_sh; a.c_ss = c_ss; a.pos = input_pos;
+  const int64_t N = a.N;
   a.bext[0] = (const bf16_t*)bext0; a.bext[1] = (const bf16_t*)bext1; a.bext[2] = (const bf16_t*)bext2;
   a.ldb[0] = rank0; a.ldb[1] = rank1; a.ldb[2] = rank2;
   a.rank[0] = (int)rank0; a.rank[1] = (int)rank1; a.rank[2] = (int)rank2;
@@ -615,34 +533,34 @@ __global__ __launch_bounds__(256) void kv_scatter_kernel(const bf16_t* __restric
   *reinterpret_cast<u32x4_t*>(dst) = *reinterpret_cast<const u32x4_t*>(src);
 }
 
-extern "C" int llx_kv_scatter(const void* k, const void* v, int64_t s_sb, int64_t s_sh, int64_t s_ss, void* k_cache, void* v_cache, int64_t c_sb,
-                              int64_t c_sh, int64_t c_ss, const int64_t* input_pos, int64_t B, int64_t KVH, int64_t L, int64_t Smax,
-                              int64_t head_dim, hipStream_t stream) {
-  LLX_REQUIRE(k && v && k_cache && v_cache && input_pos, "llx_kv_scatter: null pointer");
-  LLX_REQUIRE(head_dim == HD, "llx_kv_scatter: head_dim=%lld unsupported (only 128)", (long long)head_dim);
-  LLX_REQUIRE(B > 0 && KVH > 0 && L > 0 && Smax > 0 && B < 65536 && KVH < 65536, "llx_kv_scatter: bad sizes");
+// p_sb = the row stride of input_pos [B, L]; 0: one position row [L] for every batch element
+static int kv_scatter_run(const char* fn, const void* k, const void* v, int64_t s_sb, int64_t s_sh, int64_t s_ss, void* k_cache, void* v_cache, int64_t c_sb,
+                          int64_t c_sh, int64_t c_ss, const int64_t* input_pos, int64_t p_sb, int64_t B, int64_t KVH, int64_t L, int64_t Smax, int64_t head_dim,
+                          hipStream_t stream) {
+  LLX_REQUIRE(k && v && k_cache && v_cache && input_pos, "%s: null pointer", fn);
+  LLX_REQUIRE(head_dim == HD, "%s: head_dim=%lld unsupported (only 128)", fn, (long long)head_dim);
+  LLX_REQUIRE(B > 0 && KVH > 0 && L > 0 && Smax > 0 && B < 65536 && KVH < 65536, "%s: bad sizes", fn);
   LLX_REQUIRE(((s_sb | s_sh | s_ss | c_sb | c_sh | c_ss) % 8) == 0 && ((uintptr_t)k | (uintptr_t)v | (uintptr_t)k_cache | (uintptr_t)v_cache) % 16 == 0,
-              "llx_kv_scatter: rows must be 16-byte aligned");
+              "%s: rows must be 16-byte aligned", fn);
   hipLaunchKernelGGL(kv_scatter_kernel, dim3((unsigned)cdiv64(L, 8), (unsigned)KVH, (unsigned)B), dim3(256), 0, stream, (const bf16_t*)k, (const bf16_t*)v,
-                     s_sb, s_sh, s_ss, (bf16_t*)k_cache, (bf16_t*)v_cache, c_sb, c_sh, c_ss, input_pos, (int64_t)0, (int)L, (int)KVH, (int)Smax);
-  LLX_LAUNCH_CHECK("llx_kv_scatter");
+                     s_sb, s_sh, s_ss, (bf16_t*)k_cache, (bf16_t*)v_cache, c_sb, c_sh, c_ss, input_pos, p_sb, (int)L, (int)KVH, (int)Smax);
+  LLX_LAUNCH_CHECK(fn);
   return LLX_OK;
 }
 
+extern "C" int llx_kv_scatter(const void* k, const void* v, int64_t s_sb, int64_t s_sh, int64_t s_ss, void* k_cache, void* v_cache, int64_t c_sb,
+                              int64_t c_sh, int64_t c_ss, const int64_t* input_pos, int64_t B, int64_t KVH, int64_t L, int64_t Smax,
+                              int64_t head_dim, hipStream_t stream) {
+  return kv_scatter_run("llx_kv_scatter", k, v, s_sb, s_sh, s_ss, k_cache, v_cache, c_sb, c_sh, c_ss, input_pos, 0, B, KVH, L, Smax, head_dim, stream);
+}
+
 // KVCache.update with a position row per batch element: cache[b, h, input_pos[b, l], :] = src[b, h, l, :] (input_pos int64 [B, L] with
-// row stride p_sb): the sequences of a batch sit at their own positions.  Everything else as llx_kv_scatter.
+// row stride p_sb >= L): the sequences of a batch sit at their own positions.  Everything else as llx_kv_scatter.
 extern "C" int llx_kv_scatter_rows(const void* k, const void* v, int64_t s_sb, int64_t s_sh, int64_t s_ss, void* k_cache, void* v_cache, int64_t c_sb,
                                    int64_t c_sh, int64_t c_ss, const int64_t* input_pos, int64_t p_sb, int64_t B, int64_t KVH, int64_t L, int64_t Smax,
                                    int64_t head_dim, hipStream_t stream) {
-  LLX_REQUIRE(k && v && k_cache && v_cache && input_pos, "llx_kv_scatter_rows: null pointer");
-  LLX_REQUIRE(head_dim == HD, "llx_kv_scatter_rows: head_dim=%lld unsupported (only 128)", (long long)head_dim);
-  LLX_REQUIRE(B > 0 && KVH > 0 && L > 0 && Smax > 0 && B < 65536 && KVH < 65536 && p_sb >= L, "llx_kv_scatter_rows: bad sizes");
-  LLX_REQUIRE(((s_sb | s_sh | s_ss | c_sb | c_sh | c_ss) % 8) == 0 && ((uintptr_t)k | (uintptr_t)v | (uintptr_t)k_cache | (uintptr_t)v_cache) % 16 == 0,
-              "llx_kv_scatter_rows: rows must be 16-byte aligned");
-  hipLaunchKernelGGL(kv_scatter_kernel, dim3((unsigned)cdiv64(L, 8), (unsigned)KVH, (unsigned)B), dim3(256), 0, stream, (const bf16_t*)k, (const bf16_t*)v,
-                     s_sb, s_sh, s_ss, (bf16_t*)k_cache, (bf16_t*)v_cache, c_sb, c_sh, c_ss, input_pos, p_sb, (int)L, (int)KVH, (int)Smax);
-  LLX_LAUNCH_CHECK("llx_kv_scatter_rows");
-  return LLX_OK;
+  LLX_REQUIRE(p_sb >= L, "llx_kv_scatter_rows: bad sizes (a position row shorter than L)");
+  return kv_scatter_run("llx_kv_scatter_rows", k, v, s_sb, s_sh, s_ss, k_cache, v_cache, c_sb, c_sh, c_ss, input_pos, p_sb, B, KVH, L, Smax, head_dim, stream);
 }
 
 // ------------------------------------------------------------------------------------------------- decode attention

@@ -16,23 +16,12 @@
 //     (DESIGN 8.11): with a 16-row tile as the unit every wave item pays an agent-scope release, which drains its loads in flight;
 //   * accumulator lane (q = l / 16, m = l % 16) holds output features 4q .. 4q+3 of the tile for sequence m: a RoPE pair, and (SwiGLU,
 //     whose tile interleaves the gate and up rows of 8 hidden units) gate and up of two units, sit in one lane.
-// Epilogues as llx_gemv_bf16: none | + residual | q|k|v in batched mode (row m = sequence m at token index 0 of the call: RoPE table
-// row 0, k / v into cache[m] at pos[m]) | SwiGLU.
-#include "common.h"
+// The operand block, the norm-on-load pieces, the epilogues and the host-side operand checks are wstream.h's, shared with gemv_kernel.
+// q|k|v here is the batched mode: row m = sequence m at token index 0 of its call, so RoPE table row 0 and k / v into cache[m] at pos[m].
+#include "wstream.h"
 
-#define HD 128
-enum { GV_NONE = 0, GV_RESIDUAL = 1, GV_QKV = 2, GV_SWIGLU = 3 };
-
-struct Rows16Args {
-  const bf16_t* W[3]; int64_t ldw[3]; int seg_end[3];
-  const bf16_t* x; int64_t ldx;
-  const bf16_t* norm_w; float eps;
-  int M, N, K;
-  bf16_t* out; int64_t ldo;
-  const bf16_t* res; int64_t ldr;
-  const float* rope; int n_q, n_k;
-  bf16_t* kc; bf16_t* vc; int64_t c_sb, c_sh, c_ss; int Smax;
-  const int64_t* pos;
+struct Rows16Args : StreamArgs {
+  int64_t c_sb; int Smax;  // q|k|v: the caches' batch stride (row m goes to slot m); a row whose pos[m] is outside [0, Smax) writes no k / v
   int S, KS, ntiles, wgs;  // K slices, slice length (multiple of 256), 16-row tiles, workgroups per slice
   float* slab;             // S > 1: [ntiles][S][64 lanes][4] fp32 partial tiles
 };
@@ -43,55 +32,20 @@ struct Rows16Args {
 // bytes per instruction - was built as well and is gone again: DESIGN 8.11.)
 __device__ __forceinline__ int chunk_k(int j, int q) { return (j >> 1) * 64 + q * 16 + (j & 1) * 8; }
 
-// The epilogue of one finished 16 x 16 tile: lane (q = lane / 16, m = lane % 16) holds output features 4q .. 4q+3 of sequence m.
+// The epilogue of one finished 16 x 16 tile: lane (q = lane / 16, m = lane % 16) holds output features 4q .. 4q+3 of sequence m (SwiGLU:
+// gate and up of hidden units 8 tile + 2q, + 1).
 template <int EPI>
 __device__ __forceinline__ void rows16_epilogue(const Rows16Args& a, int tile, int lane, const f32x4_t& acc) {
-  const int q = lane >> 4, m = lane & 15, M = a.M;
-  if (m >= M) return;
+  const int q = lane >> 4, m = lane & 15;
+  if (m >= a.M) return;
   float v[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) v[e] = bf2f(f2bf(acc[e]));  // the linear's bf16 output
-  if constexpr (EPI == GV_SWIGLU) {
-    // h = silu(g) * u with the roundings of the bf16 eager graph (modelling/llama.py:150-152), as swiglu_fwd8
-    const int half = a.N / 2, u0 = 8 * tile + 2 * q;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const float sg = bf2f(f2bf(v[j] * sigmoidf_(v[j])));
-      if (u0 + j < half) a.out[(int64_t)m * a.ldo + u0 + j] = f2bf(sg * v[2 + j]);
-    }
-  } else if constexpr (EPI == GV_QKV) {
-    // apply_rope with table row 0 (every row is token 0 of its sequence's call, modelling/llama.py:207), then KVCache.update of
-    // sequence m at pos[m]; a position outside the cache writes nothing
-    const int n0 = 16 * tile + 4 * q;
-    const bool is_q = n0 < a.n_q, is_k = !is_q && n0 < a.n_q + a.n_k;
-    const int hrow = is_q ? n0 : (is_k ? n0 - a.n_q : n0 - a.n_q - a.n_k);
-    const int d = hrow & (HD - 1);
-    if (is_q || is_k) {
-      const float* tp = a.rope + (d >> 1) * 2;
-      const float c0 = tp[0], s0 = tp[1], c1 = tp[2], s1 = tp[3];
-      const float y0 = v[0] * c0 - v[1] * s0, y1 = v[1] * c0 + v[0] * s0, y2 = v[2] * c1 - v[3] * s1, y3 = v[3] * c1 + v[2] * s1;
-      v[0] = y0; v[1] = y1; v[2] = y2; v[3] = y3;
-    }
-    u32x2_t pk;
-    pk[0] = pack_bf2(v[0], v[1]);
-    pk[1] = pack_bf2(v[2], v[3]);
-    if (is_q) {
-      *reinterpret_cast<u32x2_t*>(a.out + (int64_t)m * a.ldo + n0) = pk;
-    } else {
-      const int64_t p = a.pos[m];
-      if (p >= 0 && p < a.Smax) *reinterpret_cast<u32x2_t*>((is_k ? a.kc : a.vc) + (int64_t)m * a.c_sb + (int64_t)(hrow >> 7) * a.c_sh + p * a.c_ss + d) = pk;
-    }
-  } else {
-    const int n0 = 16 * tile + 4 * q;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      if (n0 + e < a.N) {
-        float o = v[e];
-        if constexpr (EPI == GV_RESIDUAL) o += bf2f(a.res[(int64_t)m * a.ldr + n0 + e]);  // bf16 output + bf16 residual, rounded
-        a.out[(int64_t)m * a.ldo + n0 + e] = f2bf(o);
-      }
-    }
-  }
+  auto kv_off = [&]() -> int64_t {
+    const int64_t p = a.pos[m];
+    return p >= 0 && p < a.Smax ? (int64_t)m * a.c_sb + p * a.c_ss : -1;
+  };
+  stream_epilogue<EPI, 4>(a, EPI == GV_SWIGLU ? 8 * tile + 2 * q : 16 * tile + 4 * q, m, a.rope, kv_off, v);
 }
 
 template <int EPI, bool NORM>
@@ -139,11 +93,7 @@ __global__ __launch_bounds__(256, 2) void rows16_kernel(const Rows16Args a) {
     for (int r = wave; r < M; r += 4) {
       const bf16_t* xr = a.x + (int64_t)r * a.ldx;
       float ss = 0.f;
-      for (int i = lane * 8; i < K; i += 512) {
-        const u32x4_t v = *reinterpret_cast<const u32x4_t*>(xr + i);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) ss += bflo(v[e]) * bflo(v[e]) + bfhi(v[e]) * bfhi(v[e]);
-      }
+      for (int i = lane * 8; i < K; i += 512) ss = sumsq8(*reinterpret_cast<const u32x4_t*>(xr + i), ss);
       ss = wave_sum(ss);
       if (lane == 0) rs[r] = rsqrtf(ss / (float)K + a.eps);
     }
@@ -155,12 +105,7 @@ __global__ __launch_bounds__(256, 2) void rows16_kernel(const Rows16Args a) {
     u32x4_t v = {0u, 0u, 0u, 0u};
     if (k < K) {
       v = *reinterpret_cast<const u32x4_t*>(a.x + (int64_t)r * a.ldx + k);
-      if constexpr (NORM) {
-        const float rstd = rs[r];
-        const u32x4_t w = *reinterpret_cast<const u32x4_t*>(a.norm_w + k);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = pack_bf2(bflo(v[e]) * rstd * bflo(w[e]), bfhi(v[e]) * rstd * bfhi(w[e]));
-      }
+      if constexpr (NORM) v = norm8(v, rs[r], a.norm_w + k);
     }
     xs[u] = v;
   }
@@ -283,37 +228,16 @@ extern "C" int llx_gemm_rows16_bf16(const void* w0, int64_t ldw0, int64_t n0, co
                                     void* k_cache, void* v_cache, int64_t c_sb, int64_t c_sh, int64_t c_ss, int64_t Smax, const int64_t* pos,
                                     void* workspace, int64_t workspace_bytes, hipStream_t stream) {
   const char* fn = "llx_gemm_rows16_bf16";
-  LLX_REQUIRE(w0 && x && out, "%s: null pointer", fn);
-  LLX_REQUIRE(M >= 2 && M <= 16, "%s: M=%lld outside 2..16 (one row runs llx_gemv_bf16, more than 16 the MFMA GEMM)", fn, (long long)M);
-  LLX_REQUIRE(K > 0 && K % 8 == 0 && K <= 32768, "%s: K=%lld must be a multiple of 8 and at most 32768", fn, (long long)K);
-  LLX_REQUIRE(n0 > 0 && n1 >= 0 && n2 >= 0 && (w1 || n1 == 0) && (w2 || n2 == 0) && (n1 > 0 || n2 == 0), "%s: bad segment sizes", fn);
-  LLX_REQUIRE(epilogue >= GV_NONE && epilogue <= GV_SWIGLU, "%s: unknown epilogue %d", fn, epilogue);
-  LLX_REQUIRE(epilogue == GV_SWIGLU || ((n1 == 0 || n0 % 16 == 0) && (n2 == 0 || n1 % 16 == 0)), "%s: inner segment sizes must be multiples of 16", fn);
-  LLX_REQUIRE(ldw0 % 8 == 0 && ldw1 % 8 == 0 && ldw2 % 8 == 0 && ldx % 8 == 0, "%s: row strides must be multiples of 16 bytes", fn);
-  LLX_REQUIRE(((uintptr_t)w0 | (uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)x | (uintptr_t)norm_w) % 16 == 0, "%s: pointers must be 16-byte aligned", fn);
-  const int64_t N = n0 + n1 + n2;
-  LLX_REQUIRE(N < (1 << 30), "%s: too many rows", fn);
-  LLX_REQUIRE(epilogue != GV_RESIDUAL || res, "%s: residual missing", fn);
-  LLX_REQUIRE(epilogue != GV_SWIGLU || (n0 == n1 && n2 == 0 && w1), "%s: the SwiGLU epilogue takes gate and up weights of equal size", fn);
-  LLX_REQUIRE(epilogue != GV_QKV || (rope && k_cache && v_cache && pos), "%s: the q|k|v epilogue needs the RoPE table, both caches and the positions", fn);
-  LLX_REQUIRE(epilogue != GV_QKV || (n_q > 0 && n_q % HD == 0 && n_k % HD == 0 && (N - n_q - n_k) % HD == 0 && n_q + n_k <= N && Smax > 0 && Smax < (1ll << 31) &&
-                                     (uintptr_t)rope % 8 == 0 && ((uintptr_t)out | (uintptr_t)k_cache | (uintptr_t)v_cache) % 8 == 0 && ldo % 4 == 0 &&
-                                     c_sb % 4 == 0 && c_sh % 4 == 0 && c_ss % 4 == 0),
-              "%s: bad q|k|v epilogue arguments", fn);
-  const Rows16Plan p = rows16_plan(M, N, K, epilogue);
+  Rows16Args a;
+  const int rc = stream_check_fill(fn, a, 2, 16, "one row runs llx_gemv_bf16, more than 16 the MFMA GEMM", 8, epilogue == GV_SWIGLU ? 1 : 16, w0, ldw0, n0, w1, ldw1,
+                                   n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue, out, ldo, res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sh, c_ss, pos);
+  if (rc != LLX_OK) return rc;
+  LLX_REQUIRE(epilogue != GV_QKV || (n_q > 0 && Smax > 0 && Smax < (1ll << 31) && c_sb % 4 == 0),
+              "%s: the q|k|v epilogue needs q heads, a cache length below 2^31 and 8-byte aligned cache slots", fn);
+  const Rows16Plan p = rows16_plan(M, a.N, K, epilogue);
   LLX_REQUIRE(p.S == 1 || (workspace && (uintptr_t)workspace % 16 == 0 && workspace_bytes >= (int64_t)p.ntiles * p.S * 1024),
               "%s: workspace missing or smaller than llx_gemm_rows16_workspace_bytes()", fn);
-  Rows16Args a;
-  a.W[0] = (const bf16_t*)w0; a.W[1] = (const bf16_t*)(w1 ? w1 : w0); a.W[2] = (const bf16_t*)(w2 ? w2 : w0);
-  a.ldw[0] = ldw0; a.ldw[1] = w1 ? ldw1 : ldw0; a.ldw[2] = w2 ? ldw2 : ldw0;
-  a.seg_end[0] = (int)n0; a.seg_end[1] = (int)(n0 + n1); a.seg_end[2] = (int)N;
-  if (n1 == 0) { a.seg_end[0] = a.seg_end[1] = (int)N; }
-  else if (n2 == 0) { a.seg_end[1] = (int)N; }
-  a.x = (const bf16_t*)x; a.ldx = ldx; a.norm_w = (const bf16_t*)norm_w; a.eps = eps;
-  a.M = (int)M; a.N = (int)N; a.K = (int)K;
-  a.out = (bf16_t*)out; a.ldo = ldo; a.res = (const bf16_t*)res; a.ldr = ldr;
-  a.rope = rope; a.n_q = (int)n_q; a.n_k = (int)n_k; a.kc = (bf16_t*)k_cache; a.vc = (bf16_t*)v_cache;
-  a.c_sb = c_sb; a.c_sh = c_sh; a.c_ss = c_ss; a.Smax = (int)Smax; a.pos = pos;
+  a.c_sb = c_sb; a.Smax = (int)Smax;
   a.S = p.S; a.KS = p.KS; a.ntiles = p.ntiles; a.wgs = p.wgs;
   a.slab = (float*)workspace;
   const int grid = p.wgs * p.S;

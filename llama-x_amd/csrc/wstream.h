@@ -1,0 +1,130 @@
+// What the two weight streams of the decode step share: gemv_kernel (decode.hip: 1-4 activation rows, fp32 FMA in the vector pipe, bf16
+// or int8 weights, LoRA) and rows16_kernel / rows16_combine_kernel (decode_rows.hip: 2-16 rows on the matrix pipe).  Both compute
+//   out[M, N] = epilogue( [rmsnorm(x) | x][M, K] . [W0; W1; W2]^T )
+// and differ only in how a group of output features is summed.  Here: the constants, the operand block, the norm-on-load pieces, the
+// epilogue (one place where the roundings of the four epilogues live) and the host-side checks and fill of the operand block.
+#pragma once
+#include "common.h"
+
+#define HD 128
+
+// epilogue 0: out [M, N] | 1: + res [M, N] | 2 (q|k|v): rows [0, n_q) RoPE -> out [M, n_q]; [n_q, n_q + n_k) RoPE -> k cache; rest ->
+// v cache | 3 (gate|up = W0|W1, N = 2 n_0): out [M, N/2] = silu(gate) * up
+enum { GV_NONE = 0, GV_RESIDUAL = 1, GV_QKV = 2, GV_SWIGLU = 3 };
+
+struct StreamArgs {
+  const bf16_t* W[3]; int64_t ldw[3]; int seg_end[3];  // output rows [seg_end[s-1], seg_end[s]) come from W[s] (row-major [rows, K])
+  const bf16_t* x; int64_t ldx;                         // [M, K]
+  const bf16_t* norm_w; float eps;                      // NORM: x <- rmsnorm(x) * norm_w, rounded to bf16 (nn.RMSNorm, single rounding)
+  int M, N, K;
+  bf16_t* out; int64_t ldo;                             // NONE / RESIDUAL: [M, N]; QKV: q rows [M, n_q]; SWIGLU: h [M, N / 2]
+  const bf16_t* res; int64_t ldr;                       // RESIDUAL: [M, N]
+  const float* rope; int n_q, n_k;                      // QKV: rows [0, n_q) = q heads, [n_q, n_q + n_k) = k heads, then v; table [.., 64, 2]
+  bf16_t* kc; bf16_t* vc; int64_t c_sh, c_ss;           //      caches [.., KVH, Smax, 128] through (head, position) strides
+  const int64_t* pos;                                   //      the cache position of every activation row
+};
+
+// ---- norm on load: the pieces of x <- bf16(x * rstd * norm_w) on 8 packed bf16 elements
+__device__ __forceinline__ float sumsq8(const u32x4_t& v, float ss) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) ss += bflo(v[e]) * bflo(v[e]) + bfhi(v[e]) * bfhi(v[e]);
+  return ss;
+}
+__device__ __forceinline__ u32x4_t norm8(u32x4_t v, float rstd, const bf16_t* norm_w) {
+  const u32x4_t w = *reinterpret_cast<const u32x4_t*>(norm_w);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = pack_bf2(bflo(v[e]) * rstd * bflo(w[e]), bfhi(v[e]) * rstd * bfhi(w[e]));
+  return v;
+}
+
+// ---- the epilogue of NV (2 or 4) consecutive output features of activation row m, starting at feature row0 (SwiGLU: at hidden unit
+// row0).  v: the linear's outputs, already rounded to bf16; SwiGLU: v[0 .. NV/2) gates, v[NV/2 .. NV) ups of the same units.
+// q|k|v: rope_row = the RoPE table row of this activation row, kv_off() = the element offset of its (batch slot, position) in the
+// caches; negative: the k / v heads of this row are not written.  (A callable, so that the position is read where the parent
+// kernels read it, after the rotation: as a value it cost the q|k|v instances of decode_rows.hip two VGPRs.)
+template <int EPI, int NV, class KvOff>
+__device__ __forceinline__ void stream_epilogue(const StreamArgs& a, int row0, int m, const float* rope_row, KvOff&& kv_off, float (&v)[4]) {
+  static_assert(NV == 2 || NV == 4, "features per call");
+  if constexpr (EPI == GV_SWIGLU) {
+    // h = silu(g) * u with the roundings of the bf16 eager graph (modelling/llama.py:150-152), as swiglu_fwd8
+    const int half = a.N / 2;
+#pragma unroll
+    for (int j = 0; j < NV / 2; ++j) {
+      const float gg = v[j], uu = v[NV / 2 + j];
+      const float sg = bf2f(f2bf(gg * sigmoidf_(gg)));
+      if (row0 + j < half) a.out[(int64_t)m * a.ldo + row0 + j] = f2bf(sg * uu);
+    }
+  } else if constexpr (EPI == GV_QKV) {
+    // apply_rope on q and k (modelling/llama.py:63-73,122-123), then KVCache.update (:83-90) for k and v
+    const bool is_q = row0 < a.n_q, is_k = !is_q && row0 < a.n_q + a.n_k;
+    const int hrow = is_q ? row0 : (is_k ? row0 - a.n_q : row0 - a.n_q - a.n_k);
+    const int d = hrow & (HD - 1);
+    if (is_q || is_k) {
+      const float* tp = rope_row + (d >> 1) * 2;
+      const float c0 = tp[0], s0 = tp[1], c1 = NV == 4 ? tp[2] : 1.f, s1 = NV == 4 ? tp[3] : 0.f;
+      const float y0 = v[0] * c0 - v[1] * s0, y1 = v[1] * c0 + v[0] * s0, y2 = v[2] * c1 - v[3] * s1, y3 = v[3] * c1 + v[2] * s1;
+      v[0] = y0; v[1] = y1; v[2] = y2; v[3] = y3;
+    }
+    u32x2_t pk;
+    pk[0] = pack_bf2(v[0], v[1]);
+    pk[1] = pack_bf2(v[2], v[3]);
+    auto store = [&](bf16_t* dst) {
+      if constexpr (NV == 4) *reinterpret_cast<u32x2_t*>(dst) = pk;
+      else *reinterpret_cast<uint32_t*>(dst) = pk[0];  // one rotation pair
+    };
+    if (is_q) {
+      store(a.out + (int64_t)m * a.ldo + row0);
+    } else {
+      const int64_t off = kv_off();
+      if (off >= 0) store((is_k ? a.kc : a.vc) + (int64_t)(hrow >> 7) * a.c_sh + off + d);
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < NV; ++r) {
+      if (row0 + r < a.N) {
+        float o = v[r];
+        if constexpr (EPI == GV_RESIDUAL) o += bf2f(a.res[(int64_t)m * a.ldr + row0 + r]);  // bf16 output + bf16 residual, rounded
+        a.out[(int64_t)m * a.ldo + row0 + r] = f2bf(o);
+      }
+    }
+  }
+}
+
+// ---- host: the checks every entry point of the two streams makes on the common operands, then their fill into `a`.  fn = the entry
+// point's name (every message begins with it); m_lo .. m_hi = its row counts (m_note says where other counts go); epl = weight
+// elements per 16-byte load (K and the weight row strides are multiples of it); seg_gran = what the inner segments' row counts must
+// be multiples of (a row group or tile never straddles two weights).  W[] / ldw[] of absent segments repeat segment 0, seg_end[] of
+// the last present segment is N.
+static inline int stream_check_fill(const char* fn, StreamArgs& a, int m_lo, int m_hi, const char* m_note, int epl, int seg_gran, const void* w0,
+                                    int64_t ldw0, int64_t n0, const void* w1, int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2, int64_t n2,
+                                    const void* x, int64_t ldx, int64_t M, int64_t K, const void* norm_w, float eps, int epilogue, void* out, int64_t ldo,
+                                    const void* res, int64_t ldr, const float* rope, int64_t n_q, int64_t n_k, void* k_cache, void* v_cache, int64_t c_sh,
+                                    int64_t c_ss, const int64_t* pos) {
+  LLX_REQUIRE(w0 && x && out, "%s: null pointer", fn);
+  LLX_REQUIRE(M >= m_lo && M <= m_hi, "%s: M=%lld outside %d..%d (%s)", fn, (long long)M, m_lo, m_hi, m_note);
+  LLX_REQUIRE(K > 0 && K % epl == 0 && K <= 32768, "%s: K=%lld must be a multiple of %d and at most 32768", fn, (long long)K, epl);
+  LLX_REQUIRE(epilogue >= GV_NONE && epilogue <= GV_SWIGLU, "%s: unknown epilogue %d", fn, epilogue);
+  LLX_REQUIRE(n0 > 0 && n1 >= 0 && n2 >= 0 && (w1 || n1 == 0) && (w2 || n2 == 0) && (n1 > 0 || n2 == 0), "%s: bad segment sizes", fn);
+  LLX_REQUIRE((n1 == 0 || n0 % seg_gran == 0) && (n2 == 0 || n1 % seg_gran == 0), "%s: inner segment sizes must be multiples of %d", fn, seg_gran);
+  LLX_REQUIRE(ldw0 % epl == 0 && ldw1 % epl == 0 && ldw2 % epl == 0 && ldx % 8 == 0, "%s: row strides must be multiples of 16 bytes", fn);
+  LLX_REQUIRE(((uintptr_t)w0 | (uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)x | (uintptr_t)norm_w) % 16 == 0, "%s: pointers must be 16-byte aligned", fn);
+  const int64_t N = n0 + n1 + n2;
+  LLX_REQUIRE(N < (1 << 30), "%s: too many rows", fn);
+  LLX_REQUIRE(epilogue != GV_RESIDUAL || res, "%s: residual missing", fn);
+  LLX_REQUIRE(epilogue != GV_SWIGLU || (n0 == n1 && n2 == 0 && w1), "%s: the SwiGLU epilogue takes gate and up weights of equal size", fn);
+  LLX_REQUIRE(epilogue != GV_QKV || (rope && k_cache && v_cache && pos && n_q % HD == 0 && n_k % HD == 0 && (N - n_q - n_k) % HD == 0 && n_q + n_k <= N &&
+                                     (uintptr_t)rope % 8 == 0 && ((uintptr_t)out | (uintptr_t)k_cache | (uintptr_t)v_cache) % 8 == 0 && ldo % 4 == 0 &&
+                                     c_sh % 4 == 0 && c_ss % 4 == 0),
+              "%s: bad q|k|v epilogue arguments (the RoPE table, both caches and the positions; whole heads of 128; 8-byte aligned rows)", fn);
+  a.W[0] = (const bf16_t*)w0; a.W[1] = (const bf16_t*)(w1 ? w1 : w0); a.W[2] = (const bf16_t*)(w2 ? w2 : w0);
+  a.ldw[0] = ldw0; a.ldw[1] = w1 ? ldw1 : ldw0; a.ldw[2] = w2 ? ldw2 : ldw0;
+  a.seg_end[0] = (int)n0; a.seg_end[1] = (int)(n0 + n1); a.seg_end[2] = (int)N;
+  if (n1 == 0) { a.seg_end[0] = a.seg_end[1] = (int)N; }  // single source: every row is segment 0
+  else if (n2 == 0) { a.seg_end[1] = (int)N; }
+  a.x = (const bf16_t*)x; a.ldx = ldx; a.norm_w = (const bf16_t*)norm_w; a.eps = eps;
+  a.M = (int)M; a.N = (int)N; a.K = (int)K;
+  a.out = (bf16_t*)out; a.ldo = ldo; a.res = (const bf16_t*)res; a.ldr = ldr;
+  a.rope = rope; a.n_q = (int)n_q; a.n_k = (int)n_k; a.kc = (bf16_t*)k_cache; a.vc = (bf16_t*)v_cache;
+  a.c_sh = c_sh; a.c_ss = c_ss; a.pos = pos;
+  return LLX_OK;
+}

@@ -69,41 +69,26 @@ def _bf16_plain(mods) -> bool:
     return all(_plain(m) == KIND_BF16 and int(getattr(m, "rank", 0) or 0) == 0 for m in mods)
 
 
-def _layer_ok_batched(layer, x: Tensor, mask: Optional[Tensor]) -> bool:
-    """x [B, 1, D], 2 <= B <= 16: a cache of batch B, a bool mask [B | 1, 1, 1, Skv], bf16 linears without adapters, head_dim 128."""
-    att, ff = layer.attention, layer.feed_forward
-    if att.kv_cache is None or mask is None or x.dtype is not BF16 or not x.is_cuda or att.kv_cache.k_cache.shape[0] != x.shape[0]:
-        return False
-    Skv = att.kv_cache.k_cache.shape[2]
-    if mask.dtype is not torch.bool or mask.dim() != 4 or mask.shape[0] not in (1, x.shape[0]) or tuple(mask.shape[1:]) != (1, 1, Skv):
-        return False
-    if att.head_dim != 128 or att.num_heads // att.num_kv_heads > 16 or x.shape[2] % 8 != 0 or ff.w2.in_features % 8 != 0:
-        return False
-    if not _bf16_plain((att.wq, att.wk, att.wv, att.wo, ff.w1, ff.w3, ff.w2)):
-        return False
-    return ff.w1.out_features == ff.w3.out_features
-
-
 def layer_ok(layer, x: Tensor, mask: Optional[Tensor]) -> bool:
-    if _batched(x):
-        return _layer_ok_batched(layer, x, mask)
-    att = layer.attention
-    if att.kv_cache is None or mask is None or x.dim() != 3 or x.shape[0] != 1 or x.dtype is not BF16 or not x.is_cuda:
+    """x [1, M <= 4, D], or x [B, 1, D] with 2 <= B <= 16: a cache of batch B, a bool mask [B | 1, 1, 1, Skv], bf16 linears without adapters."""
+    att, ff = layer.attention, layer.feed_forward
+    if att.kv_cache is None or mask is None or x.dim() != 3 or x.dtype is not BF16 or not x.is_cuda or mask.dtype is not torch.bool:
         return False
-    M = x.shape[1]
-    if M > MAX_TOKENS or M * (att.num_heads // att.num_kv_heads) > 16 or att.head_dim != 128 or mask.dtype is not torch.bool:
+    if att.head_dim != 128 or x.shape[2] % 8 != 0 or ff.w2.in_features % 8 != 0 or ff.w1.out_features != ff.w3.out_features:
         return False
-    if x.shape[2] % 8 != 0 or layer.feed_forward.w2.in_features % 8 != 0:
-        return False
-    ff = layer.feed_forward
     lins = (att.wq, att.wk, att.wv, att.wo, ff.w1, ff.w3, ff.w2)
-    if not all(_plain(m) is not None for m in lins):
+    G = att.num_heads // att.num_kv_heads
+    if _batched(x):
+        B, Skv = x.shape[0], att.kv_cache.k_cache.shape[2]
+        return (att.kv_cache.k_cache.shape[0] == B and mask.dim() == 4 and mask.shape[0] in (1, B) and tuple(mask.shape[1:]) == (1, 1, Skv)
+                and G <= 16 and _bf16_plain(lins))
+    if x.shape[0] != 1 or x.shape[1] > MAX_TOKENS or x.shape[1] * G > 16 or not all(_plain(m) is not None for m in lins):
         return False
     for grp in ((att.wq, att.wk, att.wv), (ff.w1, ff.w3)):  # one t vector, one scale and one weight kind per fused group
         ranks = {int(getattr(m, "rank", 0) or 0) > 0 for m in grp}
         if len(ranks) != 1 or len({float(getattr(m, "scale", 1.0)) for m in grp}) != 1 or len({_plain(m) for m in grp}) != 1:
             return False
-    return att.wq.out_features % 4 == 0 and att.wk.out_features % 4 == 0 and ff.w1.out_features == ff.w3.out_features
+    return att.wq.out_features % 4 == 0 and att.wk.out_features % 4 == 0
 
 
 def _lora(mods, x: Tensor, norm):
@@ -119,61 +104,45 @@ def mask_extent(mask: Tensor) -> Tensor:
     return ops._cached(mask, "extent", lambda: K.mask_extent(mask))
 
 
-def _layer_forward_batched(layer, x: Tensor, rope: Tensor, mask: Tensor, input_pos: Tensor) -> Tensor:
-    """B sequences, one token each: the launches of the batch-1 layer, every weight read once for all rows."""
-    att, ff = layer.attention, layer.feed_forward
-    B, D = x.shape[0], x.shape[2]
-    H, KVH, hd = att.num_heads, att.num_kv_heads, att.head_dim
-    x2 = x.reshape(B, D)
-    cache = att.kv_cache
-    pos = input_pos.to(torch.int64)
-    pos = (pos.reshape(B) if pos.dim() == 2 else pos.expand(B)).contiguous()  # [B, 1]: a position per sequence; [1]: shared
-    q = K.gemm_rows16([att.wq.weight.detach(), att.wk.weight.detach(), att.wv.weight.detach()], x2,
-                      norm=(layer.attention_norm.weight.detach(), layer.attention_norm.eps), epilogue=K.GV_QKV,
-                      qkv=(rope, H * hd, KVH * hd, cache.k_cache, cache.v_cache, pos))
-    o = K.attn_decode(q.view(B, 1, H, hd).transpose(1, 2), cache.k_cache, cache.v_cache, mask, mask_extent(mask))  # [B, 1, H*hd]
-    x1 = K.gemm_rows16([att.wo.weight.detach()], o.view(B, H * hd), epilogue=K.GV_RESIDUAL, res=x2)
-    h = K.gemm_rows16([ff.w1.weight.detach(), ff.w3.weight.detach()], x1, norm=(layer.ffn_norm.weight.detach(), layer.ffn_norm.eps),
-                      epilogue=K.GV_SWIGLU)
-    x3 = K.gemm_rows16([ff.w2.weight.detach()], h, epilogue=K.GV_RESIDUAL, res=x1)
-    return x3.view(B, 1, D)
+def _lin(batched: bool):
+    """lin(mods, x, **kw): the fused product of a group of linears on the rows of x - the GEMV (any streamed kind, adapters) at batch 1,
+    the MFMA weight stream for a batch."""
+    if batched:
+        return lambda mods, x, **kw: K.gemm_rows16([m.weight.detach() for m in mods], x, **kw)
+    return lambda mods, x, norm=None, **kw: K.gemv(x=x, norm=norm, lora=_lora(mods, x, norm), **_w(mods), **kw)
 
 
 def layer_forward(layer, x: Tensor, rope: Tensor, mask: Tensor, input_pos: Tensor) -> Tensor:
-    if x.shape[0] > 1:
-        return _layer_forward_batched(layer, x, rope, mask, input_pos)
+    """x [1, M, D]: M tokens of one sequence; x [B, 1, D]: B sequences, one token each - the same launches, every weight read once."""
     att, ff = layer.attention, layer.feed_forward
-    M, D = x.shape[1], x.shape[2]
+    batched = x.shape[0] > 1
+    lin = _lin(batched)
+    R, D = x.shape[0] * x.shape[1], x.shape[2]  # activation rows
     H, KVH, hd = att.num_heads, att.num_kv_heads, att.head_dim
-    x2 = x.view(M, D)
-    n1 = (layer.attention_norm.weight.detach(), layer.attention_norm.eps)
-    qkv_mods = (att.wq, att.wk, att.wv)
+    x2 = x.reshape(R, D)
     cache = att.kv_cache
-    pos = input_pos.to(torch.int64).reshape(-1).contiguous()  # [M], or [1, M]: batch 1 with a position row of its own
-    q = K.gemv(x=x2, norm=n1, epilogue=K.GV_QKV, **_w(qkv_mods),
-               qkv=(rope, H * hd, KVH * hd, cache.k_cache, cache.v_cache, pos), lora=_lora(qkv_mods, x2, n1))
-    o = K.attn_decode(q.view(1, M, H, hd).transpose(1, 2), cache.k_cache, cache.v_cache, mask, mask_extent(mask))  # [1, M, H*hd]
-    o2 = o.view(M, H * hd)
-    x1 = K.gemv(x=o2, epilogue=K.GV_RESIDUAL, res=x2, lora=_lora((att.wo,), o2, None), **_w((att.wo,)))
-    n2 = (layer.ffn_norm.weight.detach(), layer.ffn_norm.eps)
-    h = K.gemv(x=x1, norm=n2, epilogue=K.GV_SWIGLU, lora=_lora((ff.w1, ff.w3), x1, n2), **_w((ff.w1, ff.w3)))
-    x3 = K.gemv(x=h, epilogue=K.GV_RESIDUAL, res=x1, lora=_lora((ff.w2,), h, None), **_w((ff.w2,)))
-    return x3.view(1, M, D)
+    pos = input_pos.to(torch.int64)
+    if batched and pos.dim() != 2:
+        pos = pos.expand(R)  # [1]: one position shared by the batch ([B, 1]: a position per sequence)
+    pos = pos.reshape(R).contiguous()  # batch 1: [M], or [1, M] (a position row of its own)
+    q = lin((att.wq, att.wk, att.wv), x2, norm=(layer.attention_norm.weight.detach(), layer.attention_norm.eps), epilogue=K.GV_QKV,
+            qkv=(rope, H * hd, KVH * hd, cache.k_cache, cache.v_cache, pos))
+    o = K.attn_decode(q.view(*x.shape[:2], H, hd).transpose(1, 2), cache.k_cache, cache.v_cache, mask, mask_extent(mask))  # [.., .., H*hd]
+    x1 = lin((att.wo,), o.view(R, H * hd), epilogue=K.GV_RESIDUAL, res=x2)
+    h = lin((ff.w1, ff.w3), x1, norm=(layer.ffn_norm.weight.detach(), layer.ffn_norm.eps), epilogue=K.GV_SWIGLU)
+    x3 = lin((ff.w2,), h, epilogue=K.GV_RESIDUAL, res=x1)
+    return x3.view(x.shape)
 
 
 def head_ok(model, x: Tensor) -> bool:
+    if x.dim() != 3 or not x.is_cuda or x.dtype is not BF16 or x.shape[2] % 8 != 0:
+        return False
     if _batched(x):
-        return x.is_cuda and x.dtype is BF16 and x.shape[2] % 8 == 0 and _bf16_plain((model.output,))
-    return (x.dim() == 3 and x.shape[0] == 1 and x.shape[1] <= MAX_TOKENS and x.is_cuda and x.dtype is BF16 and _plain(model.output) is not None
-            and x.shape[2] % 8 == 0)
+        return _bf16_plain((model.output,))
+    return x.shape[0] == 1 and x.shape[1] <= MAX_TOKENS and _plain(model.output) is not None
 
 
 def head_forward(model, x: Tensor) -> Tensor:
-    """logits = output(norm(x)) (modelling/llama.py:216) for M <= 4 rows: the 1 GB head weight streamed once."""
-    M, D = x.shape[1], x.shape[2]
-    nw = (model.norm.weight.detach(), model.norm.eps)
-    if x.shape[0] > 1:  # [B, 1, D]: the same product on the MFMA weight stream
-        return K.gemm_rows16([model.output.weight.detach()], x.reshape(x.shape[0], D), norm=nw).view(x.shape[0], 1, -1)
-    x2 = x.reshape(M, D)
-    logits = K.gemv(x=x2, norm=nw, lora=_lora((model.output,), x2, nw), **_w((model.output,)))
-    return logits.view(1, M, -1)
+    """logits = output(norm(x)) (modelling/llama.py:216) for M <= 4 rows, or a batch of one-token rows: the 1 GB head weight streamed once."""
+    logits = _lin(x.shape[0] > 1)((model.output,), x.reshape(-1, x.shape[2]), norm=(model.norm.weight.detach(), model.norm.eps))
+    return logits.view(*x.shape[:2], -1)

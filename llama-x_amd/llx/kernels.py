@@ -826,7 +826,46 @@ def attn_mask_bwd(q: Tensor, k: Tensor, v: Tensor, o: Tensor, do: Tensor, lse: T
 
 
 # ------------------------------------------------------------------------------------------------- decode path (csrc/decode.hip)
-GV_NONE, GV_RESIDUAL, GV_QKV, GV_SWIGLU = 0, 1, 2, 3
+GV_NONE, GV_RESIDUAL, GV_QKV, GV_SWIGLU = 0, 1, 2, 3  # csrc/wstream.h
+
+
+def _workspace(cache: dict, device, nbytes: int, floor: int = 0) -> Tensor:
+    """The grow-only uint8 workspace of the current stream of `device`, at least nbytes long (first allocation: at least floor bytes)."""
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    ws = cache.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = cache[key] = torch.empty(max(nbytes, floor), device=device, dtype=torch.uint8)
+    return ws
+
+
+def _stream_operands(ws, x: Tensor, norm, epilogue: int, out: Optional[Tensor], res: Optional[Tensor], qkv: Optional[tuple], batched: bool):
+    """What gemv and gemm_rows16 share (the StreamArgs of csrc/wstream.h): the checks on the common operands, the output tensor and the
+    leading arguments of the C entry points, w0 .. v_cache.  Returns (arguments, out, N, k_cache, pos).  batched: the q|k|v mode of
+    gemm_rows16 (table row 0 for every row, row m into cache[m]); else row m takes table row m and the cache has batch 1."""
+    M, Kd = x.shape
+    assert 1 <= len(ws) <= 3 and all(w.dim() == 2 and w.shape[1] == Kd and w.stride(1) == 1 for w in ws) and x.stride(1) == 1
+    ns = [w.shape[0] for w in ws] + [0] * (3 - len(ws))
+    N = sum(ns)
+    wp = [L.ptr(w) for w in ws] + [None] * (3 - len(ws))
+    lw = [w.stride(0) for w in ws] + [0] * (3 - len(ws))
+    n_out = {GV_NONE: N, GV_RESIDUAL: N, GV_QKV: qkv[1] if qkv else 0, GV_SWIGLU: ns[0]}[epilogue]
+    if out is None:
+        out = torch.empty(M, n_out, device=x.device, dtype=BF16)
+    assert out.shape == (M, n_out) and out.stride(1) == 1
+    nw, eps = (norm[0], float(norm[1])) if norm is not None else (None, 0.0)
+    rope = kc = vc = pos = None
+    n_q = n_k = 0
+    if epilogue == GV_QKV:
+        rope, n_q, n_k, kc, vc, pos = qkv
+        assert rope.dtype is torch.float32 and rope.is_contiguous() and rope.shape[0] >= (1 if batched else M) and rope.shape[1:] == (64, 2)
+        assert kc.shape == vc.shape and kc.dim() == 4 and kc.shape[3] == 128 and kc.stride() == vc.stride() and kc.stride(3) == 1
+        assert kc.shape[0] >= M if batched else kc.shape[0] == 1
+        assert pos.dtype is torch.int64 and pos.shape == (M,) and pos.is_contiguous() and pos.is_cuda
+    if epilogue == GV_RESIDUAL:
+        assert res is not None and res.shape == (M, N) and res.stride(1) == 1 and res.dtype is BF16
+    args = [wp[0], lw[0], ns[0], wp[1], lw[1], ns[1], wp[2], lw[2], ns[2], L.ptr(x), x.stride(0), M, Kd, L.ptr(nw), eps, epilogue, L.ptr(out), out.stride(0),
+            L.ptr(res), res.stride(0) if res is not None else 0, L.ptr(rope), n_q, n_k, L.ptr(kc), L.ptr(vc)]
+    return args, out, N, kc, pos
 
 
 def gemv(ws: Sequence[Tensor], x: Tensor, *, norm: Optional[tuple[Tensor, float]] = None, epilogue: int = GV_NONE, out: Optional[Tensor] = None,
@@ -850,47 +889,23 @@ def gemv(ws: Sequence[Tensor], x: Tensor, *, norm: Optional[tuple[Tensor, float]
     else:
         assert wscale is None and not dynamic, "wscale / dynamic belong to int8 weights"
         _chk_bf16(x, *ws)
-    M, Kd = x.shape
-    assert 1 <= len(ws) <= 3 and all(w.dim() == 2 and w.shape[1] == Kd and w.stride(1) == 1 for w in ws) and x.stride(1) == 1
-    ns = [w.shape[0] for w in ws] + [0] * (3 - len(ws))
-    N = sum(ns)
-    wp = [L.ptr(w) for w in ws] + [None] * (3 - len(ws))
-    lw = [w.stride(0) for w in ws] + [0] * (3 - len(ws))
-    n_out = {GV_NONE: N, GV_RESIDUAL: N, GV_QKV: qkv[1] if qkv else 0, GV_SWIGLU: ns[0]}[epilogue]
-    if out is None:
-        out = torch.empty(M, n_out, device=x.device, dtype=BF16)
-    assert out.shape == (M, n_out) and out.stride(1) == 1
-    nw, eps = (norm[0], float(norm[1])) if norm is not None else (None, 0.0)
-    rope = kc = vc = pos = None
-    n_q = n_k = c_sh = c_ss = 0
-    if epilogue == GV_QKV:
-        rope, n_q, n_k, kc, vc, pos = qkv
-        assert rope.dtype is torch.float32 and rope.is_contiguous() and rope.shape[0] >= M and rope.shape[1:] == (64, 2)
-        assert kc.shape == vc.shape and kc.dim() == 4 and kc.shape[0] == 1 and kc.shape[3] == 128 and kc.stride() == vc.stride() and kc.stride(3) == 1
-        assert pos.dtype is torch.int64 and pos.shape == (M,) and pos.is_contiguous() and pos.is_cuda
-        c_sh, c_ss = kc.stride(1), kc.stride(2)
-    if epilogue == GV_RESIDUAL:
-        assert res is not None and res.shape == (M, N) and res.stride(1) == 1 and res.dtype is BF16
+    args, out, _, kc, pos = _stream_operands(ws, x, norm, epilogue, out, res, qkv, batched=False)
+    args += [kc.stride(1), kc.stride(2)] if kc is not None else [0, 0]
     bs, ranks, t, ldt, lscale = [None] * 3, [0] * 3, None, 0, 0.0
     if lora is not None:
         b_list, t, lscale = lora
-        assert len(b_list) == len(ws) and t.dtype is BF16 and t.shape[0] == M and t.stride(1) == 1
+        assert len(b_list) == len(ws) and t.dtype is BF16 and t.shape[0] == x.shape[0] and t.stride(1) == 1
         for i, b in enumerate(b_list):
-            assert b.dtype is BF16 and b.is_contiguous() and b.shape[0] == ns[i]
+            assert b.dtype is BF16 and b.is_contiguous() and b.shape[0] == ws[i].shape[0]
             bs[i], ranks[i] = b, b.shape[1]
         assert t.shape[1] == sum(ranks)
         ldt = t.stride(0)
+    args += [L.ptr(pos), L.ptr(bs[0]), L.ptr(bs[1]), L.ptr(bs[2]), ranks[0], ranks[1], ranks[2], L.ptr(t), ldt, float(lscale)]
     if any(i8):
         sp = [L.ptr(sc) for sc in wscale] + [None] * (3 - len(ws))
-        L.check(_lib().llx_gemv_i8(wp[0], lw[0], ns[0], wp[1], lw[1], ns[1], wp[2], lw[2], ns[2], L.ptr(x), x.stride(0), M, Kd, L.ptr(nw), eps, epilogue,
-                                   L.ptr(out), out.stride(0), L.ptr(res), res.stride(0) if res is not None else 0, L.ptr(rope), n_q, n_k, L.ptr(kc), L.ptr(vc),
-                                   c_sh, c_ss, L.ptr(pos), L.ptr(bs[0]), L.ptr(bs[1]), L.ptr(bs[2]), ranks[0], ranks[1], ranks[2], L.ptr(t), ldt, float(lscale),
-                                   sp[0], sp[1], sp[2], int(bool(dynamic)), L.stream()), "llx_gemv_i8")
-        return out
-    L.check(_lib().llx_gemv_bf16(wp[0], lw[0], ns[0], wp[1], lw[1], ns[1], wp[2], lw[2], ns[2], L.ptr(x), x.stride(0), M, Kd, L.ptr(nw), eps, epilogue,
-                                 L.ptr(out), out.stride(0), L.ptr(res), res.stride(0) if res is not None else 0, L.ptr(rope), n_q, n_k, L.ptr(kc), L.ptr(vc),
-                                 c_sh, c_ss, L.ptr(pos), L.ptr(bs[0]), L.ptr(bs[1]), L.ptr(bs[2]), ranks[0], ranks[1], ranks[2], L.ptr(t), ldt, float(lscale),
-                                 L.stream()), "llx_gemv_bf16")
+        L.check(_lib().llx_gemv_i8(*args, sp[0], sp[1], sp[2], int(bool(dynamic)), L.stream()), "llx_gemv_i8")
+    else:
+        L.check(_lib().llx_gemv_bf16(*args, L.stream()), "llx_gemv_bf16")
     return out
 
 
@@ -904,36 +919,10 @@ def gemm_rows16(ws: Sequence[Tensor], x: Tensor, *, norm: Optional[tuple[Tensor,
     is the batched mode: qkv = (rope_table, n_q, n_k, k_cache, v_cache, pos) with caches [B >= M, KVH, Smax, 128] and pos int64 [M]; row m
     is rotated by table row 0 and its k / v heads go to cache[m] at pos[m]; returns q [M, n_q]."""
     _chk_bf16(x, *ws)
-    M, Kd = x.shape
-    assert 1 <= len(ws) <= 3 and all(w.dim() == 2 and w.shape[1] == Kd and w.stride(1) == 1 for w in ws) and x.stride(1) == 1
-    ns = [w.shape[0] for w in ws] + [0] * (3 - len(ws))
-    N = sum(ns)
-    wp = [L.ptr(w) for w in ws] + [None] * (3 - len(ws))
-    lw = [w.stride(0) for w in ws] + [0] * (3 - len(ws))
-    n_out = {GV_NONE: N, GV_RESIDUAL: N, GV_QKV: qkv[1] if qkv else 0, GV_SWIGLU: ns[0]}[epilogue]
-    if out is None:
-        out = torch.empty(M, n_out, device=x.device, dtype=BF16)
-    assert out.shape == (M, n_out) and out.stride(1) == 1
-    nw, eps = (norm[0], float(norm[1])) if norm is not None else (None, 0.0)
-    rope = kc = vc = pos = None
-    n_q = n_k = c_sb = c_sh = c_ss = smax = 0
-    if epilogue == GV_QKV:
-        rope, n_q, n_k, kc, vc, pos = qkv
-        assert rope.dtype is torch.float32 and rope.is_contiguous() and rope.shape[0] >= 1 and rope.shape[1:] == (64, 2)
-        assert kc.shape == vc.shape and kc.dim() == 4 and kc.shape[0] >= M and kc.shape[3] == 128 and kc.stride() == vc.stride() and kc.stride(3) == 1
-        assert pos.dtype is torch.int64 and pos.shape == (M,) and pos.is_contiguous() and pos.is_cuda
-        c_sb, c_sh, c_ss, smax = kc.stride(0), kc.stride(1), kc.stride(2), kc.shape[2]
-    if epilogue == GV_RESIDUAL:
-        assert res is not None and res.shape == (M, N) and res.stride(1) == 1 and res.dtype is BF16
-    nbytes = _lib().llx_gemm_rows16_workspace_bytes(M, N, Kd, epilogue)
-    key = (x.device, torch.cuda.current_stream(x.device).cuda_stream)
-    wsp = _ROWS16_WS.get(key)
-    if wsp is None or wsp.numel() < nbytes:
-        wsp = _ROWS16_WS[key] = torch.empty(max(nbytes, 1 << 20), device=x.device, dtype=torch.uint8)
-    L.check(_lib().llx_gemm_rows16_bf16(wp[0], lw[0], ns[0], wp[1], lw[1], ns[1], wp[2], lw[2], ns[2], L.ptr(x), x.stride(0), M, Kd, L.ptr(nw), eps,
-                                        epilogue, L.ptr(out), out.stride(0), L.ptr(res), res.stride(0) if res is not None else 0, L.ptr(rope), n_q,
-                                        n_k, L.ptr(kc), L.ptr(vc), c_sb, c_sh, c_ss, smax, L.ptr(pos), L.ptr(wsp), wsp.numel(), L.stream()),
-            "llx_gemm_rows16_bf16")
+    args, out, N, kc, pos = _stream_operands(ws, x, norm, epilogue, out, res, qkv, batched=True)
+    args += [kc.stride(0), kc.stride(1), kc.stride(2), kc.shape[2]] if kc is not None else [0, 0, 0, 0]
+    wsp = _workspace(_ROWS16_WS, x.device, _lib().llx_gemm_rows16_workspace_bytes(x.shape[0], N, x.shape[1], epilogue), 1 << 20)
+    L.check(_lib().llx_gemm_rows16_bf16(*args, L.ptr(pos), L.ptr(wsp), wsp.numel(), L.stream()), "llx_gemm_rows16_bf16")
     return out
 
 
@@ -988,10 +977,7 @@ def attn_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, mask: Tensor, exten
     m_sh = m.stride(1) if m.shape[1] != 1 else 0
     nsplit = max(1, min(-(-Skv // 32), -(-_DECODE_WGS // (B * KVH)), 128))  # workgroups = nsplit * B * KVH: two or more per CU keep more rows in flight
     nbytes = _lib().llx_attn_decode_workspace_bytes(B, H, M, nsplit)
-    key = (q.device, torch.cuda.current_stream(q.device).cuda_stream)
-    ws = _DECODE_WS.get(key)
-    if ws is None or ws.numel() * 4 < nbytes:
-        ws = _DECODE_WS[key] = torch.empty(nbytes // 4, device=q.device, dtype=torch.float32)
+    ws = _workspace(_DECODE_WS, q.device, nbytes)
     if out is None:
         out = torch.empty(B, M, H * hd, device=q.device, dtype=BF16)
     o4 = out.view(B, M, H, hd)
