@@ -217,6 +217,19 @@ int llx_gemm_rows16_bf16(const void* w0, int64_t ldw0, int64_t n0, const void* w
                          const void* x, int64_t ldx, int64_t M, int64_t K, const void* norm_w, float eps, int epilogue, void* out, int64_t ldo,
                          const void* res, int64_t ldr, const float* rope, int64_t n_q, int64_t n_k, void* k_cache, void* v_cache, int64_t c_sb,
                          int64_t c_sh, int64_t c_ss, int64_t Smax, const int64_t* pos, void* workspace, int64_t workspace_bytes, llx_stream_t s);
+/* llx_gemm_rows16_bf16 on int8 weight rows of the DYNAMIC kind (dynamic_int8_act, subclasses/int8.py:112-113; there is no flag: the
+ * weight-only kind has no batched stream): W_s [n_s, K] int8 row-major (ldw_s in bytes, % 16), scale_s [n_s] bf16 per-row scales,
+ * K % 16 == 0.  Each (normalised) row of x is quantised in the prologue as llx_quantize_int8_rowwise does (absmax of the whole row),
+ * v_mfma_i32_16x16x64_i8 into int32, out = bf16(((float)acc * x_scale[m]) * scale[row]) - bit-exact with the reference
+ * (int8_mm.py:93-118) and with llx_gemv_i8(dynamic = 1) when no norm is fused - then the epilogues of llx_gemm_rows16_bf16.  A split K
+ * sums int32 partial tiles (exact in any order); the workspace (llx_gemm_rows16_i8_workspace_bytes() bytes, 16-byte aligned; 0 = no
+ * split) holds a 16-float header of activation-row scales in front of them. */
+int64_t llx_gemm_rows16_i8_workspace_bytes(int64_t M, int64_t N, int64_t K, int epilogue);
+int llx_gemm_rows16_i8(const void* w0, int64_t ldw0, int64_t n0, const void* w1, int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2, int64_t n2,
+                       const void* x, int64_t ldx, int64_t M, int64_t K, const void* norm_w, float eps, int epilogue, void* out, int64_t ldo,
+                       const void* res, int64_t ldr, const float* rope, int64_t n_q, int64_t n_k, void* k_cache, void* v_cache, int64_t c_sb,
+                       int64_t c_sh, int64_t c_ss, int64_t Smax, const int64_t* pos, void* workspace, int64_t workspace_bytes,
+                       const void* scale0, const void* scale1, const void* scale2, llx_stream_t s);
 /* SDPA(q, k_cache, v_cache, mask, is_causal=False, enable_gqa=True) (:135-137) for M query tokens with M * H / KVH <= 16: the cache of a
  * kv head is split over `nsplit` workgroups, the heads of its group share every K / V row read; partials merged in a second launch.
  * q / o [B, H, M, 128], caches [B, KVH, Skv, 128] through (batch, head, position) strides; mask bool [.., M, Skv] with broadcast

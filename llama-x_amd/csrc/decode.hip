@@ -23,14 +23,11 @@
 #include <type_traits>
 
 // ------------------------------------------------------------------------------------------------- weight-streaming GEMV
-// weight kind: bf16 | int8 rows x bf16 activations (weight-only) | int8 rows x int8 activations quantised in the prologue (dynamic)
-enum { WK_BF16 = 0, WK_I8W = 1, WK_I8D = 2 };
-
+// (the weight kinds WK_* and the per-row scale pointers of the int8 kinds are wstream.h's)
 struct GemvArgs : StreamArgs {  // QKV: table row m and cache position pos[m] for activation row m, caches of batch 1
   // LoRA (modelling/lora.py:43): out += scale * (t . Bext[row]) with t = x . A^T computed by a previous launch of this kernel
   const bf16_t* bext[3]; int64_t ldb[3]; int t_off[3]; int rank[3];
   const bf16_t* t; int64_t ldt; float lora_scale;
-  const bf16_t* wscale[3];                              // int8 kinds: per-row scales of W[s] (W[s] then points at int8 rows, ldw in bytes)
 };
 
 // 16 int8 weights (sign-extended to fp32: one v_cvt_f32_i32 with a byte selector each) against 16 fp32 activations, chained onto s
@@ -408,8 +405,10 @@ static int gemv_run(const char* fn, int wk, const void* ws0, const void* ws1, co
   const int rc0 = stream_check_fill(fn, a, 1, 4, "larger row counts run the MFMA GEMM", wa, 4, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps,
                                     epilogue, out, ldo, res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sh, c_ss, input_pos);
   if (rc0 != LLX_OK) return rc0;
-  LLX_REQUIRE(wk == WK_BF16 || (ws0 && (ws1 || n1 == 0) && (ws2 || n2 == 0)), "%s: null scale (every int8 weight needs its per-row scales)", fn);
-  LLX_REQUIRE(((uintptr_t)ws0 | (uintptr_t)ws1 | (uintptr_t)ws2) % 2 == 0, "%s: scale pointers must be 2-byte aligned", fn);
+  if (wk != WK_BF16) {
+    const int rc1 = stream_check_fill_scales(fn, a, ws0, ws1, ws2, n1, n2);
+    if (rc1 != LLX_OK) return rc1;
+  }
   const bool lora = bext0 || bext1 || bext2;
   LLX_REQUIRE(!lora || (t && ldt % 8 == 0 && (uintptr_t)t % 16 == 0 && rank0 % 8 == 0 && rank1 % 8 == 0 && rank2 % 8 == 0 && rank0 <= 512 && rank1 <= 512 &&
                         rank2 <= 512 && ((uintptr_t)bext0 | (uintptr_t)bext1 | (uintptr_t)bext2) % 16 == 0),
@@ -420,7 +419,6 @@ static int gemv_run(const char* fn, int wk, const void* ws0, const void* ws1, co
   a.rank[0] = (int)rank0; a.rank[1] = (int)rank1; a.rank[2] = (int)rank2;
   a.t_off[0] = 0; a.t_off[1] = (int)rank0; a.t_off[2] = (int)(rank0 + rank1);
   a.t = (const bf16_t*)t; a.ldt = ldt; a.lora_scale = lora_scale;
-  a.wscale[0] = (const bf16_t*)ws0; a.wscale[1] = (const bf16_t*)(ws1 ? ws1 : ws0); a.wscale[2] = (const bf16_t*)(ws2 ? ws2 : ws0);
   if (n1 == 0 && lora) { a.bext[1] = a.bext[2] = a.bext[0]; a.ldb[1] = a.ldb[2] = a.ldb[0]; a.rank[1] = a.rank[2] = a.rank[0]; a.t_off[1] = a.t_off[2] = 0; }
   // rows per wave: 2 (steps of 2048 elements per row: half the dependent steps of the 4-row form on every product of the decode step and
   // twice the waves where N <= 4096 would fill only half of the 2048 slots: 3.51 -> 3.39 ms per token; one row per wave: 3.43);

@@ -18,29 +18,58 @@
 //     whose tile interleaves the gate and up rows of 8 hidden units) gate and up of two units, sit in one lane.
 // The operand block, the norm-on-load pieces, the epilogues and the host-side operand checks are wstream.h's, shared with gemv_kernel.
 // q|k|v here is the batched mode: row m = sequence m at token index 0 of its call, so RoPE table row 0 and k / v into cache[m] at pos[m].
+//
+// The dynamic int8 kind (WK_I8D: int8 weight rows with bf16 per-row scales, subclasses/int8.py:106-121 with dynamic_int8_act) is the same
+// kernel at one byte per element: a lane's 16-byte load is 16 elements = one A operand of v_mfma_i32_16x16x64_i8 (same lane -> row /
+// k-chunk map, same accumulator layout), a batch of 8 loads is 16 rows x 512 elements.  The prologue quantises every (normalised)
+// activation row as gemv_kernel<.., WK_I8D> does - absmax of the WHOLE row (one wave per row, every workgroup: it adds no launch),
+// scale = absmax / 127, codes = rint(x / max(scale, 1e-12)) - and the LDS image holds the int8 codes, M x KS bytes.  The int32 sums
+// are exact in any order; a finished sum is dequantised as the reference does, bf16(((float)acc * x_scale[m]) * w_scale[row]), and
+// then takes the same epilogue.  Split K: the partial tiles are int32, and the M activation-row scales travel to the combine launch
+// in a 16-float header of the workspace (every workgroup computes identical bits; workgroup 0 stores them).
 #include "wstream.h"
+#include <type_traits>
 
 struct Rows16Args : StreamArgs {
   int64_t c_sb; int Smax;  // q|k|v: the caches' batch stride (row m goes to slot m); a row whose pos[m] is outside [0, Smax) writes no k / v
   int S, KS, ntiles, wgs;  // K slices, slice length (multiple of 256), 16-row tiles, workgroups per slice
-  float* slab;             // S > 1: [ntiles][S][64 lanes][4] fp32 partial tiles
+  float* slab;             // S > 1: [ntiles][S][64 lanes][4] partial tiles, fp32 (WK_I8D: int32)
+  float* xscale;           // WK_I8D, S > 1: [16] the activation rows' scales for the combine launch (the workspace's header)
 };
 
-// element offset inside a 256-element batch of the 8-element chunk that lane group q (= lane / 16) takes with load j of the batch: a
-// lane's loads 2i and 2i+1 are adjacent (32 contiguous bytes per lane), so one wave-instruction touches the whole 128-byte line of
-// each of its 16 rows and the next one hits the same lines.  (The fragment's native order, j * 32 + q * 8 - 16 rows x 64 contiguous
-// bytes per instruction - was built as well and is gone again: DESIGN 8.11.)
-__device__ __forceinline__ int chunk_k(int j, int q) { return (j >> 1) * 64 + q * 16 + (j & 1) * 8; }
+// element offset inside a batch (32 chunks of EPL elements = 16 bytes: 256 bf16 or 512 int8 elements) of the chunk that lane group q
+// (= lane / 16) takes with load j of the batch: a lane's loads 2i and 2i+1 are adjacent (32 contiguous bytes per lane), so one
+// wave-instruction touches the whole 128-byte line of each of its 16 rows and the next one hits the same lines.  (The fragment's
+// native order, j * 32 + q * 8 - 16 rows x 64 contiguous bytes per instruction - was built as well and is gone again: DESIGN 8.11.)
+template <int EPL>
+__device__ __forceinline__ int chunk_k(int j, int q) { return ((j >> 1) * 8 + q * 2 + (j & 1)) * EPL; }
 
 // The epilogue of one finished 16 x 16 tile: lane (q = lane / 16, m = lane % 16) holds output features 4q .. 4q+3 of sequence m (SwiGLU:
-// gate and up of hidden units 8 tile + 2q, + 1).
-template <int EPI>
-__device__ __forceinline__ void rows16_epilogue(const Rows16Args& a, int tile, int lane, const f32x4_t& acc) {
+// gate and up of hidden units 8 tile + 2q, + 1).  WK_I8D: acc = the int32 sums, xscale = the scale of activation row m.
+template <int EPI, int WK, class Acc>
+__device__ __forceinline__ void rows16_epilogue(const Rows16Args& a, int tile, int lane, const Acc& acc, float xscale) {
   const int q = lane >> 4, m = lane & 15;
   if (m >= a.M) return;
   float v[4];
+  if constexpr (WK == WK_BF16) {
 #pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = bf2f(f2bf(acc[e]));  // the linear's bf16 output
+    for (int e = 0; e < 4; ++e) v[e] = bf2f(f2bf(acc[e]));  // the linear's bf16 output
+  } else {
+    // int32 sum x activation-row scale x weight-row scale in fp32, rounded (int8_mm.py:93-118), as gemv_kernel<.., WK_I8D>
+    float wsc[4];
+    if constexpr (EPI == GV_SWIGLU) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) wsc[e] = bf2f(a.wscale[e >> 1][min(8 * tile + 2 * q + (e & 1), a.N / 2 - 1)]);
+    } else {
+      const int n0 = 16 * tile;
+      const int seg = n0 >= a.seg_end[0] ? (n0 >= a.seg_end[1] ? 2 : 1) : 0;
+      const int base = seg == 0 ? 0 : a.seg_end[seg - 1];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) wsc[e] = bf2f(a.wscale[seg][min(n0 - base + 4 * q + e, a.seg_end[seg] - 1 - base)]);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = bf2f(f2bf(((float)acc[e] * xscale) * wsc[e]));
+  }
   auto kv_off = [&]() -> int64_t {
     const int64_t p = a.pos[m];
     return p >= 0 && p < a.Smax ? (int64_t)m * a.c_sb + p * a.c_ss : -1;
@@ -48,84 +77,120 @@ __device__ __forceinline__ void rows16_epilogue(const Rows16Args& a, int tile, i
   stream_epilogue<EPI, 4>(a, EPI == GV_SWIGLU ? 8 * tile + 2 * q : 16 * tile + 4 * q, m, a.rope, kv_off, v);
 }
 
-template <int EPI, bool NORM>
+template <int EPI, bool NORM, int WK>
 __global__ __launch_bounds__(256, 2) void rows16_kernel(const Rows16Args a) {
+  static_assert(WK == WK_BF16 || WK == WK_I8D, "weight kinds of the batched stream");
+  using WT = std::conditional_t<WK == WK_BF16, bf16_t, int8_t>;      // a stored weight element
+  using acc_t = std::conditional_t<WK == WK_BF16, f32x4_t, i32x4_t>;
+  constexpr int EPL = 16 / (int)sizeof(WT), BATCH = 32 * EPL;        // elements per 16-byte load; per batch of 8 loads x 4 lane groups
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ float rs[16];
-  u32x4_t* xs = reinterpret_cast<u32x4_t*>(smem);  // [KS / 8 chunks in consumption order][M]
+  __shared__ float qdiv[WK == WK_I8D ? 16 : 1], xsc[WK == WK_I8D ? 16 : 1];  // WK_I8D: the rows' divisors and (bf16-rounded) scales
+  u32x4_t* xs = reinterpret_cast<u32x4_t*>(smem);  // [KS / EPL chunks in consumption order][M] (WK_I8D: 16 int8 codes per chunk)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int q = lane >> 4, m = lane & 15;
   const int K = a.K, M = a.M;
   const int s = blockIdx.x % a.S, wg = blockIdx.x / a.S;
   const int k_lo = s * a.KS;
-  const int nb = (min(a.KS, K - k_lo) + 255) >> 8;  // 256-element batches of this slice (the last may run past K: zeros in LDS)
+  const int nb = (min(a.KS, K - k_lo) + BATCH - 1) / BATCH;  // batches of this slice (the last may run past K: zeros in LDS)
 
   // ---- the weight row of this lane in tile t.  SwiGLU: tile row 4j + i = gate (i < 2) or up row of hidden unit 8t + 2j + (i & 1)
-  auto row_ptr = [&](int t) -> const bf16_t* {
+  auto row_ptr = [&](int t) -> const WT* {
     const int r = lane & 15;
     if constexpr (EPI == GV_SWIGLU) {
       const int mat = (r >> 1) & 1, unit = min(8 * t + 2 * (r >> 2) + (r & 1), a.N / 2 - 1);
-      return a.W[mat] + (int64_t)unit * a.ldw[mat];
+      return reinterpret_cast<const WT*>(a.W[mat]) + (int64_t)unit * a.ldw[mat];
     } else {
       const int n0 = 16 * t;  // segment boundaries are multiples of 16: a tile lies in one segment
       const int seg = n0 >= a.seg_end[0] ? (n0 >= a.seg_end[1] ? 2 : 1) : 0;
       const int base = seg == 0 ? 0 : a.seg_end[seg - 1];
-      return a.W[seg] + (int64_t)min(n0 - base + r, a.seg_end[seg] - 1 - base) * a.ldw[seg];
+      return reinterpret_cast<const WT*>(a.W[seg]) + (int64_t)min(n0 - base + r, a.seg_end[seg] - 1 - base) * a.ldw[seg];
     }
   };
-  auto load_batch = [&](u32x4_t (&w)[8], const bf16_t* wr, int b) {
+  auto load_batch = [&](u32x4_t (&w)[8], const WT* wr, int b) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const int k = k_lo + b * 256 + chunk_k(j, q);
+      const int k = k_lo + b * BATCH + chunk_k<EPL>(j, q);
       w[j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(wr + (k < K ? k : 0)));  // chunks past the row end: their x is zero
     }
   };
   const int wave_stride = a.wgs * 4;
   int t = wg * 4 + wave, b = 0;
-  const bf16_t *cur = nullptr, *nxt = nullptr;
+  const WT *cur = nullptr, *nxt = nullptr;
   u32x4_t WA[8], WB[8];
   // the first weight loads do not depend on x: they fly while the activation rows are staged (and normalised)
   if (t < a.ntiles) { cur = row_ptr(t); load_batch(WA, cur, 0); }
 
-  // ---- the slice of the activation rows into LDS; NORM: 1 / rms of the WHOLE row first, one wave per row
-  if constexpr (NORM) {
+  // ---- the slice of the activation rows into LDS; NORM: 1 / rms of the WHOLE row first, one wave per row.  WK_I8D:
+  // quantize_int8_rowwise on the (normalised, bf16-rounded) row, the pieces and the order of gemv_kernel<.., WK_I8D>: the absmax of the
+  // WHOLE row in the same pass structure (an all-zero row: scale 0, divisor 1e-12, zero codes, zero output)
+  if constexpr (NORM || WK == WK_I8D) {
     for (int r = wave; r < M; r += 4) {
       const bf16_t* xr = a.x + (int64_t)r * a.ldx;
-      float ss = 0.f;
-      for (int i = lane * 8; i < K; i += 512) ss = sumsq8(*reinterpret_cast<const u32x4_t*>(xr + i), ss);
-      ss = wave_sum(ss);
-      if (lane == 0) rs[r] = rsqrtf(ss / (float)K + a.eps);
+      float rstd = 1.f;
+      if constexpr (NORM) {
+        float ss = 0.f;
+        for (int i = lane * 8; i < K; i += 512) ss = sumsq8(*reinterpret_cast<const u32x4_t*>(xr + i), ss);
+        ss = wave_sum(ss);
+        rstd = rsqrtf(ss / (float)K + a.eps);
+        if (lane == 0) rs[r] = rstd;
+      }
+      if constexpr (WK == WK_I8D) {
+        float amax = 0.f;
+        for (int i = lane * 8; i < K; i += 512) {
+          u32x4_t v = *reinterpret_cast<const u32x4_t*>(xr + i);
+          if constexpr (NORM) v = norm8(v, rstd, a.norm_w + i);
+          amax = q8_absmax8(v, amax);
+        }
+        amax = wave_max(amax);
+        const float scale = q8_scale(amax);
+        if (lane == 0) { qdiv[r] = q8_divisor(scale); xsc[r] = bf2f(f2bf(scale)); }
+      }
     }
     __syncthreads();
   }
+  if constexpr (WK == WK_I8D) {
+    if (a.S > 1 && blockIdx.x == 0 && tid < M) a.xscale[tid] = xsc[tid];  // for the combine launch
+  }
   for (int u = tid; u < nb * 32 * M; u += 256) {
     const int c = u / M, r = u - c * M;  // chunk c of the image = (batch c / 32, load (c / 4) % 8, lane group c % 4)
-    const int k = k_lo + (c >> 5) * 256 + chunk_k((c >> 2) & 7, c & 3);
+    const int k = k_lo + (c >> 5) * BATCH + chunk_k<EPL>((c >> 2) & 7, c & 3);
     u32x4_t v = {0u, 0u, 0u, 0u};
-    if (k < K) {
-      v = *reinterpret_cast<const u32x4_t*>(a.x + (int64_t)r * a.ldx + k);
+    if (k < K) {  // (K is a multiple of EPL: a chunk is live or past the row end as a whole)
+      const bf16_t* xp = a.x + (int64_t)r * a.ldx + k;
+      v = *reinterpret_cast<const u32x4_t*>(xp);
       if constexpr (NORM) v = norm8(v, rs[r], a.norm_w + k);
+      if constexpr (WK == WK_I8D) {
+        u32x4_t v1 = *reinterpret_cast<const u32x4_t*>(xp + 8);
+        if constexpr (NORM) v1 = norm8(v1, rs[r], a.norm_w + k + 8);
+        const float div = qdiv[r];
+        const u32x2_t c0 = q8_quant8(v, div), c1 = q8_quant8(v1, div);
+        v = u32x4_t{c0[0], c0[1], c1[0], c1[1]};
+      }
     }
     xs[u] = v;
   }
   __syncthreads();
 
-  f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+  acc_t acc = {};
   auto compute_batch = [&](const u32x4_t (&w)[8], int bb) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       u32x4_t xv = {0u, 0u, 0u, 0u};
       if (m < M) xv = xs[((bb * 8 + j) * 4 + q) * M + m];  // columns M .. 15 of the activation operand are zeros
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, w[j]), __builtin_bit_cast(bf16x8_t, xv), acc, 0, 0, 0);
+      if constexpr (WK == WK_BF16) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, w[j]), __builtin_bit_cast(bf16x8_t, xv), acc, 0, 0, 0);
+      else acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4_t, w[j]), __builtin_bit_cast(i32x4_t, xv), acc, 0, 0, 0);
     }
   };
   auto finish = [&](int tile) {
     if (a.S > 1) {  // the partial tile of this slice; rows16_combine_kernel sums the slices and runs the epilogue
-      *reinterpret_cast<f32x4_t*>(a.slab + ((((int64_t)tile * a.S) + s) << 8) + lane * 4) = acc;
+      *reinterpret_cast<acc_t*>(a.slab + ((((int64_t)tile * a.S) + s) << 8) + lane * 4) = acc;
       return;
     }
-    rows16_epilogue<EPI>(a, tile, lane, acc);
+    float xm = 0.f;
+    if constexpr (WK == WK_I8D) xm = xsc[min(m, M - 1)];
+    rows16_epilogue<EPI, WK>(a, tile, lane, acc, xm);
   };
   // software pipeline over the flattened (tile, batch) sequence of this wave: while one register set is consumed the next batch's 8
   // loads (of this tile or of the wave's next tile) are in flight
@@ -141,7 +206,7 @@ __global__ __launch_bounds__(256, 2) void rows16_kernel(const Rows16Args a) {
     compute_batch(wc, b);
     if (newt) {
       finish(t);
-      acc = f32x4_t{0.f, 0.f, 0.f, 0.f};
+      acc = acc_t{};
       cur = nxt;
     }
     t = t2; b = b2;
@@ -156,70 +221,116 @@ __global__ __launch_bounds__(256, 2) void rows16_kernel(const Rows16Args a) {
 }
 
 // S > 1: one wave per tile sums the S partial tiles in slice order and runs the epilogue
-template <int EPI>
+template <int EPI, int WK>
 __global__ __launch_bounds__(256) void rows16_combine_kernel(const Rows16Args a) {
+  using acc_t = std::conditional_t<WK == WK_BF16, f32x4_t, i32x4_t>;
   const int lane = threadIdx.x & 63;
   const int tile = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (tile >= a.ntiles) return;
   const float* sl = a.slab + (((int64_t)tile * a.S) << 8) + lane * 4;
-  f32x4_t sum = *reinterpret_cast<const f32x4_t*>(sl);
-  for (int s2 = 1; s2 < a.S; ++s2) sum += *reinterpret_cast<const f32x4_t*>(sl + ((int64_t)s2 << 8));
-  rows16_epilogue<EPI>(a, tile, lane, sum);
+  acc_t sum = *reinterpret_cast<const acc_t*>(sl);
+  for (int s2 = 1; s2 < a.S; ++s2) sum += *reinterpret_cast<const acc_t*>(sl + ((int64_t)s2 << 8));
+  float xm = 0.f;
+  if constexpr (WK == WK_I8D) xm = a.xscale[min(lane & 15, a.M - 1)];
+  rows16_epilogue<EPI, WK>(a, tile, lane, sum, xm);
 }
 
-template <int EPI>
+template <int EPI, int WK>
 static int launch_rows16(const Rows16Args& a, int grid, size_t lds, hipStream_t stream) {
-  if (a.norm_w) hipLaunchKernelGGL((rows16_kernel<EPI, true>), dim3(grid), dim3(256), lds, stream, a);
-  else hipLaunchKernelGGL((rows16_kernel<EPI, false>), dim3(grid), dim3(256), lds, stream, a);
-  LLX_LAUNCH_CHECK("llx_gemm_rows16_bf16");
+  if (a.norm_w) hipLaunchKernelGGL((rows16_kernel<EPI, true, WK>), dim3(grid), dim3(256), lds, stream, a);
+  else hipLaunchKernelGGL((rows16_kernel<EPI, false, WK>), dim3(grid), dim3(256), lds, stream, a);
+  LLX_LAUNCH_CHECK(WK == WK_BF16 ? "llx_gemm_rows16_bf16" : "llx_gemm_rows16_i8");
   if (a.S > 1) {
-    hipLaunchKernelGGL((rows16_combine_kernel<EPI>), dim3((a.ntiles + 3) / 4), dim3(256), 0, stream, a);
-    LLX_LAUNCH_CHECK("llx_gemm_rows16_bf16(combine)");
+    hipLaunchKernelGGL((rows16_combine_kernel<EPI, WK>), dim3((a.ntiles + 3) / 4), dim3(256), 0, stream, a);
+    LLX_LAUNCH_CHECK(WK == WK_BF16 ? "llx_gemm_rows16_bf16(combine)" : "llx_gemm_rows16_i8(combine)");
   }
   return LLX_OK;
 }
 
+template <int WK>
 static int launch_rows16_epi(const Rows16Args& a, int epi, int grid, size_t lds, hipStream_t stream) {
   switch (epi) {
-    case GV_NONE: return launch_rows16<GV_NONE>(a, grid, lds, stream);
-    case GV_RESIDUAL: return launch_rows16<GV_RESIDUAL>(a, grid, lds, stream);
-    case GV_QKV: return launch_rows16<GV_QKV>(a, grid, lds, stream);
-    default: return launch_rows16<GV_SWIGLU>(a, grid, lds, stream);
+    case GV_NONE: return launch_rows16<GV_NONE, WK>(a, grid, lds, stream);
+    case GV_RESIDUAL: return launch_rows16<GV_RESIDUAL, WK>(a, grid, lds, stream);
+    case GV_QKV: return launch_rows16<GV_QKV, WK>(a, grid, lds, stream);
+    default: return launch_rows16<GV_SWIGLU, WK>(a, grid, lds, stream);
   }
 }
 
-// The launcher's dispatch decisions, all of them:
+// The launcher's dispatch decisions, all of them.  esz = bytes per weight / staged activation element (2: bf16, 1: the dynamic int8
+// kind, whose LDS image holds int8 codes); a batch = 8 loads x 4 lane groups x 16 bytes = 512 / esz elements (256 bf16, 512 int8):
 //   ntiles = ceil(N / 16) (SwiGLU: ceil(n_0 / 8): a tile is the gate and up rows of 8 hidden units);
-//   S (K slices): at least ceil(K / ks_max) with ks_max = the largest multiple of 256 whose M-row LDS image fits 60 KiB, and as many
-//     as bring ntiles * S to 2048 wave items while a slice keeps >= 256 elements, at most 64; from there the first count up to twice
-//     that which cuts K into equal slices of whole 256-element batches, if there is one;
-//   KS = ceil(K / S) rounded up to 256 (the last slice may be shorter, and its last batch may run past K);
+//   S (K slices): at least ceil(K / ks_max) with ks_max = the largest multiple of a batch whose M-row LDS image (M x KS x esz bytes)
+//     fits 60 KiB, and as many as bring ntiles * S to 2048 wave items while a slice keeps >= one batch, at most 64; from there the
+//     first count up to twice that which cuts K into equal slices of whole batches, if there is one;
+//   KS = ceil(K / S) rounded up to a batch (the last slice may be shorter, and its last batch may run past K);
 //   workgroups per slice: the tiles are dealt to ceil(ntiles / tiles_per_wave) waves with tiles_per_wave = ceil(ntiles * S / 2048).
 struct Rows16Plan { int ntiles, S, KS, wgs; };
-static Rows16Plan rows16_plan(int64_t M, int64_t N, int64_t K, int epilogue) {
+static Rows16Plan rows16_plan(int64_t M, int64_t N, int64_t K, int epilogue, int64_t esz) {
   Rows16Plan p;
+  const int64_t batch = 512 / esz;
   p.ntiles = (int)(epilogue == GV_SWIGLU ? cdiv64(N / 2, 8) : cdiv64(N, 16));
-  const int64_t ks_max = (60 * 1024 / (2 * M)) / 256 * 256;
+  const int64_t ks_max = (60 * 1024 / (esz * M)) / batch * batch;
   const int64_t s_min = cdiv64(K, ks_max);
   int64_t s_req = cdiv64(2048, p.ntiles);
-  if (s_req > cdiv64(K, 256)) s_req = cdiv64(K, 256);
+  if (s_req > cdiv64(K, batch)) s_req = cdiv64(K, batch);
   if (s_req > 64) s_req = 64;
   if (s_req < s_min) s_req = s_min;
   int64_t S = s_req;
   for (int64_t c = s_req; c <= 2 * s_req && c <= 64; ++c)
-    if (K % (c * 256) == 0) { S = c; break; }
-  p.KS = (int)(cdiv64(cdiv64(K, S), 256) * 256);
+    if (K % (c * batch) == 0) { S = c; break; }
+  p.KS = (int)(cdiv64(cdiv64(K, S), batch) * batch);
   p.S = (int)cdiv64(K, p.KS);
   const int64_t per_wave = cdiv64((int64_t)p.ntiles * p.S, 2048);
   p.wgs = (int)cdiv64(cdiv64(p.ntiles, per_wave), 4);
   return p;
 }
 
-// bytes of the workspace llx_gemm_rows16_bf16 needs for this product: the fp32 partial tiles of a split K (0 without a split)
-extern "C" int64_t llx_gemm_rows16_workspace_bytes(int64_t M, int64_t N, int64_t K, int epilogue) {
+// bytes of the workspace of one product: the partial tiles of a split K (fp32 or int32, 1 KiB each; 0 without a split) behind `header`
+// bytes (the int8 kind's 16 activation-row scales)
+static int64_t rows16_workspace(int64_t M, int64_t N, int64_t K, int epilogue, int64_t esz, int64_t header) {
   if (M < 2 || M > 16 || N < 1 || K < 1 || N >= (1 << 30) || K > 32768) return 0;
-  const Rows16Plan p = rows16_plan(M, N, K, epilogue);
-  return p.S > 1 ? (int64_t)p.ntiles * p.S * 1024 : 0;
+  const Rows16Plan p = rows16_plan(M, N, K, epilogue, esz);
+  return p.S > 1 ? header + (int64_t)p.ntiles * p.S * 1024 : 0;
+}
+#define ROWS16_I8_HEADER 64  // 16 floats
+
+// bytes of the workspace llx_gemm_rows16_bf16 needs for this product: the fp32 partial tiles of a split K (0 without a split)
+extern "C" int64_t llx_gemm_rows16_workspace_bytes(int64_t M, int64_t N, int64_t K, int epilogue) { return rows16_workspace(M, N, K, epilogue, 2, 0); }
+// the same for llx_gemm_rows16_i8: the int32 partial tiles behind the 16-float header of activation-row scales (0 without a split)
+extern "C" int64_t llx_gemm_rows16_i8_workspace_bytes(int64_t M, int64_t N, int64_t K, int epilogue) {
+  return rows16_workspace(M, N, K, epilogue, 1, ROWS16_I8_HEADER);
+}
+
+// the two entry points below: fn = the caller's name for messages, wk = WK_BF16 | WK_I8D, ws_s = per-row scales of W_s (WK_I8D)
+static int rows16_run(const char* fn, int wk, const void* ws0, const void* ws1, const void* ws2, const void* w0, int64_t ldw0, int64_t n0, const void* w1,
+                      int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2, int64_t n2, const void* x, int64_t ldx, int64_t M, int64_t K,
+                      const void* norm_w, float eps, int epilogue, void* out, int64_t ldo, const void* res, int64_t ldr, const float* rope, int64_t n_q,
+                      int64_t n_k, void* k_cache, void* v_cache, int64_t c_sb, int64_t c_sh, int64_t c_ss, int64_t Smax, const int64_t* pos,
+                      void* workspace, int64_t workspace_bytes, hipStream_t stream) {
+  const int esz = wk == WK_BF16 ? 2 : 1;
+  const int64_t header = wk == WK_BF16 ? 0 : ROWS16_I8_HEADER;
+  Rows16Args a;
+  const int rc = stream_check_fill(fn, a, 2, 16, wk == WK_BF16 ? "one row runs llx_gemv_bf16, more than 16 the MFMA GEMM" : "one row runs llx_gemv_i8, more than 16 the MFMA GEMM",
+                                   16 / esz, epilogue == GV_SWIGLU ? 1 : 16, w0, ldw0, n0, w1, ldw1,
+                                   n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue, out, ldo, res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sh, c_ss, pos);
+  if (rc != LLX_OK) return rc;
+  if (wk != WK_BF16) {
+    const int rc1 = stream_check_fill_scales(fn, a, ws0, ws1, ws2, n1, n2);
+    if (rc1 != LLX_OK) return rc1;
+  }
+  LLX_REQUIRE(epilogue != GV_QKV || (n_q > 0 && Smax > 0 && Smax < (1ll << 31) && c_sb % 4 == 0),
+              "%s: the q|k|v epilogue needs q heads, a cache length below 2^31 and 8-byte aligned cache slots", fn);
+  const Rows16Plan p = rows16_plan(M, a.N, K, epilogue, esz);
+  LLX_REQUIRE(p.S == 1 || (workspace && (uintptr_t)workspace % 16 == 0 && workspace_bytes >= header + (int64_t)p.ntiles * p.S * 1024),
+              "%s: workspace missing or smaller than %s()", fn, wk == WK_BF16 ? "llx_gemm_rows16_workspace_bytes" : "llx_gemm_rows16_i8_workspace_bytes");
+  a.c_sb = c_sb; a.Smax = (int)Smax;
+  a.S = p.S; a.KS = p.KS; a.ntiles = p.ntiles; a.wgs = p.wgs;
+  a.xscale = (float*)workspace;
+  a.slab = (float*)((char*)workspace + header);
+  const int grid = p.wgs * p.S;
+  const size_t lds = (size_t)M * p.KS * esz;
+  return wk == WK_BF16 ? launch_rows16_epi<WK_BF16>(a, epilogue, grid, lds, stream) : launch_rows16_epi<WK_I8D>(a, epilogue, grid, lds, stream);
 }
 
 extern "C" int llx_gemm_rows16_bf16(const void* w0, int64_t ldw0, int64_t n0, const void* w1, int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2,
@@ -227,20 +338,21 @@ extern "C" int llx_gemm_rows16_bf16(const void* w0, int64_t ldw0, int64_t n0, co
                                     void* out, int64_t ldo, const void* res, int64_t ldr, const float* rope, int64_t n_q, int64_t n_k,
                                     void* k_cache, void* v_cache, int64_t c_sb, int64_t c_sh, int64_t c_ss, int64_t Smax, const int64_t* pos,
                                     void* workspace, int64_t workspace_bytes, hipStream_t stream) {
-  const char* fn = "llx_gemm_rows16_bf16";
-  Rows16Args a;
-  const int rc = stream_check_fill(fn, a, 2, 16, "one row runs llx_gemv_bf16, more than 16 the MFMA GEMM", 8, epilogue == GV_SWIGLU ? 1 : 16, w0, ldw0, n0, w1, ldw1,
-                                   n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue, out, ldo, res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sh, c_ss, pos);
-  if (rc != LLX_OK) return rc;
-  LLX_REQUIRE(epilogue != GV_QKV || (n_q > 0 && Smax > 0 && Smax < (1ll << 31) && c_sb % 4 == 0),
-              "%s: the q|k|v epilogue needs q heads, a cache length below 2^31 and 8-byte aligned cache slots", fn);
-  const Rows16Plan p = rows16_plan(M, a.N, K, epilogue);
-  LLX_REQUIRE(p.S == 1 || (workspace && (uintptr_t)workspace % 16 == 0 && workspace_bytes >= (int64_t)p.ntiles * p.S * 1024),
-              "%s: workspace missing or smaller than llx_gemm_rows16_workspace_bytes()", fn);
-  a.c_sb = c_sb; a.Smax = (int)Smax;
-  a.S = p.S; a.KS = p.KS; a.ntiles = p.ntiles; a.wgs = p.wgs;
-  a.slab = (float*)workspace;
-  const int grid = p.wgs * p.S;
-  const size_t lds = (size_t)M * p.KS * 2;
-  return launch_rows16_epi(a, epilogue, grid, lds, stream);
+  return rows16_run("llx_gemm_rows16_bf16", WK_BF16, nullptr, nullptr, nullptr, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue, out, ldo,
+                    res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sb, c_sh, c_ss, Smax, pos, workspace, workspace_bytes, stream);
+}
+
+// The same product on int8 weight rows of the DYNAMIC kind (subclasses/int8.py:112-113, int8_mm.py:93-118; the weight-only kind has
+// no batched stream): W_s [n_s, K] int8 row-major (ldw_s in bytes, multiples of 16), scale_s [n_s] bf16 per-row scales, K % 16 == 0.
+// Every (normalised) row of x is quantised as llx_quantize_int8_rowwise does, v_mfma_i32_16x16x64_i8 into int32,
+// out = bf16(((float)acc * x_scale[m]) * scale[row]) - bit-exact with the reference and with llx_gemv_i8(dynamic = 1) when no norm is
+// fused - then the epilogues of llx_gemm_rows16_bf16.  Workspace: llx_gemm_rows16_i8_workspace_bytes().
+extern "C" int llx_gemm_rows16_i8(const void* w0, int64_t ldw0, int64_t n0, const void* w1, int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2,
+                                  int64_t n2, const void* x, int64_t ldx, int64_t M, int64_t K, const void* norm_w, float eps, int epilogue,
+                                  void* out, int64_t ldo, const void* res, int64_t ldr, const float* rope, int64_t n_q, int64_t n_k,
+                                  void* k_cache, void* v_cache, int64_t c_sb, int64_t c_sh, int64_t c_ss, int64_t Smax, const int64_t* pos,
+                                  void* workspace, int64_t workspace_bytes, const void* scale0, const void* scale1, const void* scale2,
+                                  hipStream_t stream) {
+  return rows16_run("llx_gemm_rows16_i8", WK_I8D, scale0, scale1, scale2, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue, out, ldo,
+                    res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sb, c_sh, c_ss, Smax, pos, workspace, workspace_bytes, stream);
 }

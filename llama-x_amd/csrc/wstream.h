@@ -1,7 +1,8 @@
 // What the two weight streams of the decode step share: gemv_kernel (decode.hip: 1-4 activation rows, fp32 FMA in the vector pipe, bf16
-// or int8 weights, LoRA) and rows16_kernel / rows16_combine_kernel (decode_rows.hip: 2-16 rows on the matrix pipe).  Both compute
+// or int8 weights, LoRA) and rows16_kernel / rows16_combine_kernel (decode_rows.hip: 2-16 rows on the matrix pipe, bf16 or dynamic
+// int8 weights).  Both compute
 //   out[M, N] = epilogue( [rmsnorm(x) | x][M, K] . [W0; W1; W2]^T )
-// and differ only in how a group of output features is summed.  Here: the constants, the operand block, the norm-on-load pieces, the
+// and differ only in how a group of output features is summed.  Here: the constants (epilogues, weight kinds), the operand block, the norm-on-load pieces, the
 // epilogue (one place where the roundings of the four epilogues live) and the host-side checks and fill of the operand block.
 #pragma once
 #include "common.h"
@@ -11,9 +12,12 @@
 // epilogue 0: out [M, N] | 1: + res [M, N] | 2 (q|k|v): rows [0, n_q) RoPE -> out [M, n_q]; [n_q, n_q + n_k) RoPE -> k cache; rest ->
 // v cache | 3 (gate|up = W0|W1, N = 2 n_0): out [M, N/2] = silu(gate) * up
 enum { GV_NONE = 0, GV_RESIDUAL = 1, GV_QKV = 2, GV_SWIGLU = 3 };
+// weight kind: bf16 | int8 rows x bf16 activations (weight-only) | int8 rows x int8 activations quantised in the prologue (dynamic)
+enum { WK_BF16 = 0, WK_I8W = 1, WK_I8D = 2 };
 
 struct StreamArgs {
   const bf16_t* W[3]; int64_t ldw[3]; int seg_end[3];  // output rows [seg_end[s-1], seg_end[s]) come from W[s] (row-major [rows, K])
+  const bf16_t* wscale[3];                              // int8 kinds: per-row scales of W[s] (W[s] then points at int8 rows, ldw in bytes)
   const bf16_t* x; int64_t ldx;                         // [M, K]
   const bf16_t* norm_w; float eps;                      // NORM: x <- rmsnorm(x) * norm_w, rounded to bf16 (nn.RMSNorm, single rounding)
   int M, N, K;
@@ -126,5 +130,14 @@ static inline int stream_check_fill(const char* fn, StreamArgs& a, int m_lo, int
   a.out = (bf16_t*)out; a.ldo = ldo; a.res = (const bf16_t*)res; a.ldr = ldr;
   a.rope = rope; a.n_q = (int)n_q; a.n_k = (int)n_k; a.kc = (bf16_t*)k_cache; a.vc = (bf16_t*)v_cache;
   a.c_sh = c_sh; a.c_ss = c_ss; a.pos = pos;
+  a.wscale[0] = a.wscale[1] = a.wscale[2] = nullptr;
+  return LLX_OK;
+}
+
+// ---- host: the per-row scales of int8 weights (bf16 [n_s]), after stream_check_fill; scales of absent segments repeat segment 0
+static inline int stream_check_fill_scales(const char* fn, StreamArgs& a, const void* ws0, const void* ws1, const void* ws2, int64_t n1, int64_t n2) {
+  LLX_REQUIRE(ws0 && (ws1 || n1 == 0) && (ws2 || n2 == 0), "%s: null scale (every int8 weight needs its per-row scales)", fn);
+  LLX_REQUIRE(((uintptr_t)ws0 | (uintptr_t)ws1 | (uintptr_t)ws2) % 2 == 0, "%s: scale pointers must be 2-byte aligned", fn);
+  a.wscale[0] = (const bf16_t*)ws0; a.wscale[1] = (const bf16_t*)(ws1 ? ws1 : ws0); a.wscale[2] = (const bf16_t*)(ws2 ? ws2 : ws0);
   return LLX_OK;
 }

@@ -6,9 +6,11 @@ stays for every call this path does not take (more than 4 tokens, more than 16 q
 Int8LinearWeight linears (weight-only or dynamic, subclasses/int8.py:106-121) stream their int8 rows (llx_gemv_i8): no bf16 image of
 the matrix is built or read.
 
-A batch of 2 <= B <= 16 sequences with one token each (x [B, 1, D], a cache of batch B, bf16 linears without adapters) takes the same
-steps per layer with the MFMA weight stream (llx_gemm_rows16_bf16) in place of the GEMV: the weights are read once for all B rows (a
-product whose K is split adds a small combine launch).  int8 and LoRA / DoRA linears and B > 16 stay on the generic path at B > 1.
+A batch of 2 <= B <= 16 sequences with one token each (x [B, 1, D], a cache of batch B, linears without adapters) takes the same
+steps per layer with the MFMA weight stream in place of the GEMV: the weights are read once for all B rows (a product whose K is
+split adds a small combine launch).  Every fused group is bf16 (llx_gemm_rows16_bf16) or dynamic int8 (llx_gemm_rows16_i8: the rows
+quantised in the prologue, int8 MFMA); groups of different kinds may sit next to each other in a layer, as at batch 1.  Weight-only
+int8 and LoRA / DoRA linears and B > 16 stay on the generic path at B > 1.
 
 Per layer (M <= 4 tokens at batch 1):
     q            = gemv([wq; wk; wv], rmsnorm(x))  + RoPE on q, k + k, v scattered into the caches        1 launch
@@ -65,12 +67,14 @@ def _batched(x: Tensor) -> bool:
     return x.dim() == 3 and 2 <= x.shape[0] <= MAX_BATCH and x.shape[1] == 1 and BATCHED
 
 
-def _bf16_plain(mods) -> bool:
-    return all(_plain(m) == KIND_BF16 and int(getattr(m, "rank", 0) or 0) == 0 for m in mods)
+def _batch_group(mods) -> bool:
+    """A fused group the batched stream takes: all members bf16, or all dynamic int8, none with an adapter."""
+    return ({_plain(m) for m in mods} in ({KIND_BF16}, {KIND_I8D})) and all(int(getattr(m, "rank", 0) or 0) == 0 for m in mods)
 
 
 def layer_ok(layer, x: Tensor, mask: Optional[Tensor]) -> bool:
-    """x [1, M <= 4, D], or x [B, 1, D] with 2 <= B <= 16: a cache of batch B, a bool mask [B | 1, 1, 1, Skv], bf16 linears without adapters."""
+    """x [1, M <= 4, D], or x [B, 1, D] with 2 <= B <= 16: a cache of batch B, a bool mask [B | 1, 1, 1, Skv], every fused group
+    bf16 or dynamic int8 without adapters."""
     att, ff = layer.attention, layer.feed_forward
     if att.kv_cache is None or mask is None or x.dim() != 3 or x.dtype is not BF16 or not x.is_cuda or mask.dtype is not torch.bool:
         return False
@@ -81,7 +85,7 @@ def layer_ok(layer, x: Tensor, mask: Optional[Tensor]) -> bool:
     if _batched(x):
         B, Skv = x.shape[0], att.kv_cache.k_cache.shape[2]
         return (att.kv_cache.k_cache.shape[0] == B and mask.dim() == 4 and mask.shape[0] in (1, B) and tuple(mask.shape[1:]) == (1, 1, Skv)
-                and G <= 16 and _bf16_plain(lins))
+                and G <= 16 and all(_batch_group(g) for g in ((att.wq, att.wk, att.wv), (att.wo,), (ff.w1, ff.w3), (ff.w2,))))
     if x.shape[0] != 1 or x.shape[1] > MAX_TOKENS or x.shape[1] * G > 16 or not all(_plain(m) is not None for m in lins):
         return False
     for grp in ((att.wq, att.wk, att.wv), (ff.w1, ff.w3)):  # one t vector, one scale and one weight kind per fused group
@@ -106,9 +110,13 @@ def mask_extent(mask: Tensor) -> Tensor:
 
 def _lin(batched: bool):
     """lin(mods, x, **kw): the fused product of a group of linears on the rows of x - the GEMV (any streamed kind, adapters) at batch 1,
-    the MFMA weight stream for a batch."""
+    the MFMA weight stream for a batch (per group: bf16 or dynamic int8)."""
     if batched:
-        return lambda mods, x, **kw: K.gemm_rows16([m.weight.detach() for m in mods], x, **kw)
+        def lin(mods, x, **kw):
+            w = _w(mods)
+            w.pop("dynamic", None)  # int8 groups of a batch are of the dynamic kind (layer_ok)
+            return K.gemm_rows16(x=x, **w, **kw)
+        return lin
     return lambda mods, x, norm=None, **kw: K.gemv(x=x, norm=norm, lora=_lora(mods, x, norm), **_w(mods), **kw)
 
 
@@ -138,7 +146,7 @@ def head_ok(model, x: Tensor) -> bool:
     if x.dim() != 3 or not x.is_cuda or x.dtype is not BF16 or x.shape[2] % 8 != 0:
         return False
     if _batched(x):
-        return _bf16_plain((model.output,))
+        return _batch_group((model.output,))
     return x.shape[0] == 1 and x.shape[1] <= MAX_TOKENS and _plain(model.output) is not None
 
 

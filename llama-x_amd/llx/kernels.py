@@ -913,14 +913,34 @@ _ROWS16_WS: dict = {}
 
 
 def gemm_rows16(ws: Sequence[Tensor], x: Tensor, *, norm: Optional[tuple[Tensor, float]] = None, epilogue: int = GV_NONE, out: Optional[Tensor] = None,
-                res: Optional[Tensor] = None, qkv: Optional[tuple] = None) -> Tensor:
+                res: Optional[Tensor] = None, qkv: Optional[tuple] = None, wscale: Optional[Sequence[Tensor]] = None) -> Tensor:
     """gemv's product for 2 <= M = x.shape[0] <= 16 rows - a batch of sequences, one token each - on the matrix pipe (llx_gemm_rows16_bf16):
     the weights stream once whatever M is.  bf16 weights without adapters; norm, res and the GV_* epilogues as gemv, except GV_QKV, which
     is the batched mode: qkv = (rope_table, n_q, n_k, k_cache, v_cache, pos) with caches [B >= M, KVH, Smax, 128] and pos int64 [M]; row m
-    is rotated by table row 0 and its k / v heads go to cache[m] at pos[m]; returns q [M, n_q]."""
-    _chk_bf16(x, *ws)
+    is rotated by table row 0 and its k / v heads go to cache[m] at pos[m]; returns q [M, n_q].
+    int8 ws (the int_data of dynamic Int8LinearWeights, all members of the call) with wscale = their bf16 per-row scales run
+    llx_gemm_rows16_i8: the rows of x quantised on chip, int8 MFMA, the reference's dequantisation (the dynamic kind only: the
+    weight-only kind has no batched stream)."""
+    i8 = [w.dtype is torch.int8 for w in ws]
+    if any(i8):
+        if not all(i8):
+            raise L.LlxError("gemm_rows16: bf16 and int8 weights in one call (all members of a fused group must be of one kind)")
+        if x.shape[1] % 16 != 0:
+            raise L.LlxError(f"gemm_rows16: K={x.shape[1]} must be a multiple of 16 for int8 weights")
+        assert wscale is not None and len(wscale) == len(ws), "int8 weights need their per-row scales"
+        assert all(sc.shape == (w.shape[0],) and sc.is_contiguous() for sc, w in zip(wscale, ws))
+        _chk_bf16(x, *wscale)
+        L.require_cuda(*ws)
+    else:
+        assert wscale is None, "wscale belongs to int8 weights"
+        _chk_bf16(x, *ws)
     args, out, N, kc, pos = _stream_operands(ws, x, norm, epilogue, out, res, qkv, batched=True)
     args += [kc.stride(0), kc.stride(1), kc.stride(2), kc.shape[2]] if kc is not None else [0, 0, 0, 0]
+    if any(i8):
+        wsp = _workspace(_ROWS16_WS, x.device, _lib().llx_gemm_rows16_i8_workspace_bytes(x.shape[0], N, x.shape[1], epilogue), 1 << 20)
+        sp = [L.ptr(sc) for sc in wscale] + [None] * (3 - len(ws))
+        L.check(_lib().llx_gemm_rows16_i8(*args, L.ptr(pos), L.ptr(wsp), wsp.numel(), sp[0], sp[1], sp[2], L.stream()), "llx_gemm_rows16_i8")
+        return out
     wsp = _workspace(_ROWS16_WS, x.device, _lib().llx_gemm_rows16_workspace_bytes(x.shape[0], N, x.shape[1], epilogue), 1 << 20)
     L.check(_lib().llx_gemm_rows16_bf16(*args, L.ptr(pos), L.ptr(wsp), wsp.numel(), L.stream()), "llx_gemm_rows16_bf16")
     return out

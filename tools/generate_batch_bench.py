@@ -13,7 +13,16 @@ The batched and the sequential window alternate, `--rounds` times each after an 
 Kernels: each product is launched alone between device events, the variants (GEMV M = 1; rows16 M = 2, 8, 16) and products interleaved
 so that 1.5 GB of other weights pass between two launches on the same matrix; median of `--kernel-rounds`; GB/s = weight bytes / time.
 
-    python tools/generate_batch_bench.py [--prompt 1024] [--new 64] [--rounds 5] [--layers 32] [--out profiles/generate_batch_bench.json]
+--int8: the layers quantised with quantize_linear_(model.layers, "int8", dynamic_int8_act=True), the head bf16 - the int8 workload of
+bench.py.  The batched step then runs the int8 weight stream (llx_gemm_rows16_i8); a third window, alternating with the other two,
+times the same batched step on the generic inference path (llx.decode.BATCHED = False: MFMA GEMMs at M = B with a row-quantise launch
+per linear - what a dynamic-int8 batch ran before the int8 stream existed); `faster_than_generic` holds by the same spread rule.  A
+fourth window times the batched step of a bf16 model of the same dimensions and seed (llx_gemm_rows16_bf16) against the same caches:
+`bf16_batched_step_ms`.  The
+kernel table then has the five products through gemm_rows16 on int8 rows next to the bf16 rows16 and the int8 GEMV (dynamic) figures.
+
+    python tools/generate_batch_bench.py [--int8] [--prompt 1024] [--new 64] [--rounds 5] [--layers 32] [--out profiles/generate_batch_bench.json]
+(--int8: the default output is profiles/generate_batch_int8_bench.json)
 """
 import argparse
 import json
@@ -73,6 +82,7 @@ def main():
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--kernel-rounds", type=int, default=15)
     ap.add_argument("--kernels-only", action="store_true")
+    ap.add_argument("--int8", action="store_true", help="dynamic-int8 layers (bf16 head): the int8 batched weight stream")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     for p in (ROOT, os.path.join(ROOT, "llama-x_amd")):
@@ -81,6 +91,7 @@ def main():
 
     if not torch.cuda.is_available():
         raise SystemExit("generate_batch_bench: no GPU (there is no CPU path to time)")
+    import llx.decode as DEC
     from llx import kernels as K
     from llx.generate import generate, prefill
 
@@ -92,8 +103,10 @@ def main():
     g = torch.Generator(device=dev)
     g.manual_seed(1)
     prompts = torch.randint(0, cfg.vocab_size, (max(BATCHES), P), device=dev, generator=g)
-    res = {"workload": f"Llama-3.1-8B dimensions ({args.layers} layers), random weights, max_seq_len 8192, prompts of {P} tokens, {n} new tokens, greedy; "
-                       f"medians (min-max) of {args.rounds} alternating rounds"}
+    res = {"workload": f"Llama-3.1-8B dimensions ({args.layers} layers), random weights{', layers dynamic int8 (bf16 head)' if args.int8 else ''}, "
+                       f"max_seq_len 8192, prompts of {P} tokens, {n} new tokens, greedy; medians (min-max) of {args.rounds} alternating rounds"}
+    if args.int8 and args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "generate_batch_int8_bench.json")
 
     def events(fn, reps):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -116,27 +129,46 @@ def main():
     xI = torch.randn(16, I, device=dev, generator=g).bfloat16()
     n1 = (lay.attention_norm.weight.detach(), 1e-5)
     pos16 = torch.arange(16, device=dev)
+    # the weights of layer 0 and the head, by kind: bf16 as built; --int8: also their int8 rows and scales (the head's for this table only)
+    mods = {"wq": att.wq, "wk": att.wk, "wv": att.wv, "wo": att.wo, "w1": ff.w1, "w3": ff.w3, "w2": ff.w2, "output": model.output}
+    bf = {k: m.weight.detach() for k, m in mods.items()}
+    q8 = {}
+    if args.int8:
+        from subclasses import quantize_linear_
+        from subclasses.int8 import quantize_int8_rowwise
+
+        q8 = {k: quantize_int8_rowwise(w) for k, w in bf.items()}
+        quantize_linear_(model.layers, "int8", dynamic_int8_act=True)
+        model_bf16, _ = build(args.layers, 8192, dev)  # the bf16 twin for the bf16 batched-step window
+        model_bf16.build_cache(inference=True)
+        model_bf16 = model_bf16.to(dev)
+
+    def operands(kind, names):
+        return dict(ws=[bf[k] for k in names]) if kind == "bf16" else dict(ws=[q8[k][0] for k in names], wscale=[q8[k][1] for k in names])
+
     products = {
-        "q|k|v (6144 x 4096, norm, RoPE + scatter)": lambda f, M, c: f([att.wq.weight, att.wk.weight, att.wv.weight], xD[:M], norm=n1, epilogue=K.GV_QKV,
-                                                                      qkv=(rope, H * 128, KVH * 128, c[0], c[1], pos16[:M])),
-        "wo (4096 x 4096, + residual)": lambda f, M, c: f([att.wo.weight], xD[:M], epilogue=K.GV_RESIDUAL, res=xD[:M]),
-        "gate|up (28672 x 4096, norm, SwiGLU)": lambda f, M, c: f([ff.w1.weight, ff.w3.weight], xD[:M], norm=n1, epilogue=K.GV_SWIGLU),
-        "w2 (4096 x 14336, + residual)": lambda f, M, c: f([ff.w2.weight], xI[:M], epilogue=K.GV_RESIDUAL, res=xD[:M]),
-        "head (128256 x 4096, norm)": lambda f, M, c: f([model.output.weight], xD[:M], norm=n1),
+        "q|k|v (6144 x 4096, norm, RoPE + scatter)": (("wq", "wk", "wv"), 6144 * 4096, lambda M, c: dict(x=xD[:M], norm=n1, epilogue=K.GV_QKV,
+                                                                                                      qkv=(rope, H * 128, KVH * 128, c[0], c[1], pos16[:M]))),
+        "wo (4096 x 4096, + residual)": (("wo",), 4096 * 4096, lambda M, c: dict(x=xD[:M], epilogue=K.GV_RESIDUAL, res=xD[:M])),
+        "gate|up (28672 x 4096, norm, SwiGLU)": (("w1", "w3"), 28672 * 4096, lambda M, c: dict(x=xD[:M], norm=n1, epilogue=K.GV_SWIGLU)),
+        "w2 (4096 x 14336, + residual)": (("w2",), 4096 * 14336, lambda M, c: dict(x=xI[:M], epilogue=K.GV_RESIDUAL, res=xD[:M])),
+        "head (128256 x 4096, norm)": (("output",), 128256 * 4096, lambda M, c: dict(x=xD[:M], norm=n1)),
     }
-    wbytes = {"q|k|v (6144 x 4096, norm, RoPE + scatter)": 6144 * 4096 * 2, "wo (4096 x 4096, + residual)": 4096 * 4096 * 2,
-              "gate|up (28672 x 4096, norm, SwiGLU)": 28672 * 4096 * 2, "w2 (4096 x 14336, + residual)": 4096 * 14336 * 2,
-              "head (128256 x 4096, norm)": 128256 * 4096 * 2}
-    variants = [("gemv M=1", K.gemv, 1, (kc[:1], vc[:1])), ("rows16 M=2", K.gemm_rows16, 2, (kc, vc)), ("rows16 M=8", K.gemm_rows16, 8, (kc, vc)),
-                ("rows16 M=16", K.gemm_rows16, 16, (kc, vc))]
+    # (name, entry point, rows, caches, weight kind, extra arguments)
+    variants = [("gemv M=1", K.gemv, 1, (kc[:1], vc[:1]), "bf16", {})] if not args.int8 else [("gemv int8 M=1", K.gemv, 1, (kc[:1], vc[:1]), "int8", dict(dynamic=True))]
+    variants += [(f"rows16 M={M}", K.gemm_rows16, M, (kc, vc), "bf16", {}) for M in (2, 8, 16)]
+    if args.int8:
+        variants += [(f"rows16 int8 M={M}", K.gemm_rows16, M, (kc, vc), "int8", {}) for M in (2, 8, 16)]
     times = {(v[0], name): [] for v in variants for name in products}
     for r in range(args.kernel_rounds + 1):
-        for vname, f, M, c in variants:
-            for name, call in products.items():
-                t = events(lambda: call(f, M, c), 1)
+        for vname, f, M, c, kind, extra in variants:
+            for name, (names, _, kw) in products.items():
+                w = operands(kind, names)
+                t = events(lambda: f(**w, **kw(M, c), **extra), 1)
                 if r > 0:  # the first round is untimed
                     times[(vname, name)].append(t * 1e3)
-    res["kernels_us_and_GBps"] = {name: {v[0]: {"us": stats(times[(v[0], name)]), "GBps": round(wbytes[name] / (stats(times[(v[0], name)])["median"] * 1e-6) / 1e9, 1)}
+    res["kernels_us_and_GBps"] = {name: {v[0]: {"us": stats(times[(v[0], name)]),
+                                                "GBps": round(products[name][1] * (2 if v[4] == "bf16" else 1) / (stats(times[(v[0], name)])["median"] * 1e-6) / 1e9, 1)}
                                          for v in variants} for name in products}
 
     # ---- decode steps and whole generate() calls, batched against sequential
@@ -147,7 +179,7 @@ def main():
             many = one if B == 1 else caches_for(model, cfg, B, dev)
             pr = prompts[:B]
 
-            def step_ms(batch):
+            def step_ms(batch, model=model):
                 """ms per decode step of `batch` sequences against the installed cache (prefilled here)."""
                 pb = prompts[:batch]
                 logits = prefill(model, pb)
@@ -179,10 +211,19 @@ def main():
                 return (time.perf_counter() - t0) * 1e3
 
             gen_batched(), gen_sequential()  # untimed pass of both
-            ms = {"batched_step": [], "single_step": [], "batched_generate": [], "sequential_generate": []}
+            ms = {"batched_step": [], "single_step": [], "batched_generate": [], "sequential_generate": [], "generic_step": [], "bf16_batched_step": []}
             for _ in range(args.rounds):
                 install(model, many)
                 ms["batched_step"].append(step_ms(B))
+                if args.int8 and B > 1:  # the same step on the generic inference path
+                    DEC.BATCHED = False
+                    try:
+                        ms["generic_step"].append(step_ms(B))
+                    finally:
+                        DEC.BATCHED = True
+                if args.int8:  # the bf16 model's batched step against the same caches
+                    install(model_bf16, many)
+                    ms["bf16_batched_step"].append(step_ms(B, model_bf16))
                 install(model, one)
                 ms["single_step"].append(step_ms(1))
                 ms["batched_generate"].append(wall(gen_batched))
@@ -195,6 +236,13 @@ def main():
                 "batched_tokens_per_s": round(B * n / (bg["median"] * 1e-3), 1), "sequential_tokens_per_s": round(B * n / (sg["median"] * 1e-3), 1),
                 "batched_faster": ss["median"] - bs["median"] > (bs["max"] - bs["min"]) + (ss["max"] - ss["min"]),
             }
+            if ms["generic_step"]:
+                gs = stats(ms["generic_step"])
+                res["batches"][str(B)].update({"generic_step_ms": gs, "speedup_over_generic": round(gs["median"] / bs["median"], 2),
+                                               "faster_than_generic": gs["median"] - bs["median"] > (bs["max"] - bs["min"]) + (gs["max"] - gs["min"])})
+            if ms["bf16_batched_step"]:
+                fs = stats(ms["bf16_batched_step"])
+                res["batches"][str(B)].update({"bf16_batched_step_ms": fs, "int8_over_bf16_step": round(bs["median"] / fs["median"], 2)})
             if B > 1:
                 del many
                 torch.cuda.empty_cache()
