@@ -28,19 +28,8 @@
 //   dkv kernel: S = Q.K^T, dP = dO.V^T (key on the lane, K/V fragments live in registers), dV^T += dO^T.P,
 //               dK^T += Q^T.dS with P/dS from the accumulator registers and Q^T/dO^T by transposed LDS reads.
 // LDS images read both by rows and transposed use the dual-use swizzle  slot = chunk ^ (((row&3)<<2) | ((row>>2)&3)).
-#include "common.h"
-#include <mutex>
-#include <stdlib.h>
-#include <type_traits>
+#include "attn.h"
 
-#define HD 128
-#define BQ 128
-#define BKV 64
-#define TILE_BYTES (64 * HD * 2)  // a 64-row x 128-col bf16 tile = 16 KiB
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
-typedef __attribute__((address_space(3))) s16x4_t lds_s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8_t;
 
 __device__ __forceinline__ int dual_swz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
@@ -1106,26 +1095,62 @@ extern "C" int64_t llx_attn_bwd_ds_bytes(int64_t B, int64_t S, int64_t H) {
   return B * H * Sp * Sp * 2;
 }
 
-static int attn_bwd_set_attrs() {
-  static std::once_flag once;
-  static bool ok = false;
-  std::call_once(once, [] {
-    hipError_t e = hipSuccess;
-    auto set = [&](const void* f, int bytes) { if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); };
-    set((const void*)attn_bwd_dq_kernel<BWD_CAUSAL>, DQ_LDS_BYTES);
-    set((const void*)attn_bwd_dq_kernel<BWD_RULE>, DQ_LDS_BYTES);
-    set((const void*)attn_bwd_dq2_kernel<false>, DQ2_LDS_BYTES);
-    set((const void*)attn_bwd_dq2_kernel<true>, DQ2_LDS_BYTES);
-    set((const void*)attn_bwd_dkv3_kernel<BWD_RULE, false, false>, DKV3_LDS_BYTES);
-    set((const void*)attn_bwd_dkv3_kernel<BWD_CAUSAL, false, false>, DKV3_LDS_BYTES);
-    set((const void*)attn_bwd_dkv3_kernel<BWD_RULE, false, true>, DKV3_LDS_BYTES);
-    set((const void*)attn_bwd_dkv3_kernel<BWD_CAUSAL, false, true>, DKV3_LDS_BYTES);
-    set((const void*)attn_bwd_dkv3_kernel<BWD_CAUSAL, true, false>, DKV3_LDS_BYTES);
-    set((const void*)attn_bwd_dq_kernel<BWD_MASK>, DQ_LDS_BYTES);
-    set((const void*)attn_bwd_dkv3_kernel<BWD_MASK, false, false>, DKV3_LDS_BYTES);
-    ok = e == hipSuccess;
-  });
-  return ok ? LLX_OK : LLX_ERR_LAUNCH;
+static int attn_bwd_set_attrs() {  // (each static is initialised once, by one thread)
+  static const hipError_t e0 = attn_lds_limit(DQ_LDS_BYTES, attn_bwd_dq_kernel<BWD_CAUSAL>, attn_bwd_dq_kernel<BWD_RULE>, attn_bwd_dq_kernel<BWD_MASK>);
+  static const hipError_t e1 = attn_lds_limit(DQ2_LDS_BYTES, attn_bwd_dq2_kernel<false>, attn_bwd_dq2_kernel<true>);
+  static const hipError_t e2 = attn_lds_limit(DKV3_LDS_BYTES, attn_bwd_dkv3_kernel<BWD_CAUSAL, false, false>, attn_bwd_dkv3_kernel<BWD_RULE, false, false>,
+                                              attn_bwd_dkv3_kernel<BWD_MASK, false, false>, attn_bwd_dkv3_kernel<BWD_CAUSAL, true, false>,
+                                              attn_bwd_dkv3_kernel<BWD_CAUSAL, false, true>, attn_bwd_dkv3_kernel<BWD_RULE, false, true>);
+  return e0 == hipSuccess && e1 == hipSuccess && e2 == hipSuccess ? LLX_OK : LLX_ERR_LAUNCH;
+}
+
+// The backward entries' common operands, checked and filled in; the mask source (rule or mask, flags), the dS buffer and the stamps stay null.
+static int attn_bwd_args(const char* fn, AttnBwdArgs& a, const void* q, int64_t q_sb, int64_t q_ss, const void* k, int64_t k_sb, int64_t k_ss,
+                         const void* v, int64_t v_sb, int64_t v_ss, const void* o, int64_t o_sb, int64_t o_ss, const void* d_o, int64_t do_sb,
+                         int64_t do_ss, const float* lse, float* delta, void* dq, int64_t dq_sb, int64_t dq_ss, void* dk, int64_t dk_sb,
+                         int64_t dk_ss, void* dv, int64_t dv_sb, int64_t dv_ss, const float* rope, int64_t B, int64_t S, int64_t H, int64_t KVH,
+                         int64_t head_dim, float scale) {
+  LLX_REQUIRE(q && k && v && o && d_o && lse && delta && dq && dk && dv, "%s: null pointer", fn);
+  if (int rc = attn_check_shape(fn, B, S, H, KVH, head_dim)) return rc;
+  LLX_REQUIRE(((q_ss | k_ss | v_ss | o_ss | do_ss | q_sb | k_sb | v_sb | o_sb | do_sb) % 8) == 0, "%s: input strides must keep 16-byte alignment", fn);
+  LLX_REQUIRE(((dq_ss | dk_ss | dv_ss | dq_sb | dk_sb | dv_sb) % 4) == 0, "%s: output strides must keep 8-byte alignment", fn);
+  LLX_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)d_o) % 16 == 0, "%s: unaligned input", fn);
+  LLX_REQUIRE(((uintptr_t)dq) % 8 == 0 && ((uintptr_t)dk | (uintptr_t)dv) % 16 == 0 && ((dk_ss | dv_ss | dk_sb | dv_sb) % 8) == 0,
+              "%s: unaligned output", fn);
+  LLX_REQUIRE(!rope || (uintptr_t)rope % 16 == 0, "%s: unaligned rope table", fn);
+  LLX_REQUIRE(S < (1 << 24) && B * H < (1 << 16), "%s: S or B*H too large", fn);
+  a = {};
+  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (const bf16_t*)o; a.d_o = (const bf16_t*)d_o;
+  a.lse = lse; a.delta = delta; a.nlse = delta + B * H * S; a.rope = rope; a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv;
+  a.q_sb = q_sb; a.q_ss = q_ss; a.k_sb = k_sb; a.k_ss = k_ss; a.v_sb = v_sb; a.v_ss = v_ss; a.o_sb = o_sb; a.o_ss = o_ss;
+  a.do_sb = do_sb; a.do_ss = do_ss; a.dq_sb = dq_sb; a.dq_ss = dq_ss; a.dk_sb = dk_sb; a.dk_ss = dk_ss; a.dv_sb = dv_sb; a.dv_ss = dv_ss;
+  a.B = (int)B; a.S = (int)S; a.H = (int)H; a.KVH = (int)KVH;
+  a.scale = scale; a.scale_log2 = scale * 1.4426950408889634f;
+  return LLX_OK;
+}
+
+// Both routes: a build of the dK/dV kernel, then the reduce of its partials (behind delta and -lse in the workspace) into dk, dv.
+static int attn_bwd_dkv(const char* fn, void (*kernel)(const AttnBwdArgs, float*), const AttnBwdArgs& a, hipStream_t stream) {
+  const int64_t B = a.B, S = a.S, H = a.H;
+  float* part = a.nlse + B * H * S;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(cdiv64(S, DKV2_KEYS) * B * H)), dim3(256), DKV3_LDS_BYTES, stream, a, part);
+  LLX_LAUNCH_CHECK(fn);
+  hipLaunchKernelGGL(attn_dkv_reduce_kernel, dim3((unsigned)cdiv64(B * S * a.KVH * HD / 8, 256)), dim3(256), 0, stream, a, (const float*)part);
+  LLX_LAUNCH_CHECK(fn);
+  return LLX_OK;
+}
+
+// Route (b) in one of the modes BWD_*: dQ, dK/dV partials, reduce.  With a.stamps (BWD_CAUSAL only) the dK/dV kernel is its stamping build.
+static int attn_bwd_run(const char* fn, const AttnBwdArgs& a, int mode, hipStream_t stream) {
+  void (*const dq[3])(const AttnBwdArgs) = {attn_bwd_dq_kernel<BWD_CAUSAL>, attn_bwd_dq_kernel<BWD_RULE>, attn_bwd_dq_kernel<BWD_MASK>};
+  void (*const dkv[3])(const AttnBwdArgs, float*) = {attn_bwd_dkv3_kernel<BWD_CAUSAL, false, false>, attn_bwd_dkv3_kernel<BWD_RULE, false, false>,
+                                                     attn_bwd_dkv3_kernel<BWD_MASK, false, false>};
+  if (attn_bwd_set_attrs() != LLX_OK) { llx_set_error("%s: cannot raise LDS limit", fn); return LLX_ERR_LAUNCH; }
+  // dQ first: it also publishes delta = rowsum(dO . O) and the sanitised -lse that the dK/dV kernel stages from global memory
+  hipLaunchKernelGGL(dq[mode], dim3((unsigned)a.H, (unsigned)cdiv64(a.S, BQ), (unsigned)a.B), dim3(256), DQ_LDS_BYTES, stream, a);
+  LLX_LAUNCH_CHECK(fn);
+  // (BWD_MASK: a key block without a live tile runs no tile and still writes its zero partials: the reduce then stores exact zeros)
+  return attn_bwd_dkv(fn, a.stamps ? attn_bwd_dkv3_kernel<BWD_CAUSAL, true, false> : dkv[mode], a, stream);
 }
 
 // delta: fp32 workspace of llx_attn_bwd_workspace_bytes() bytes.  All strides in elements.  flags as in llx_attn_fwd.
@@ -1139,62 +1164,25 @@ extern "C" int llx_attn_bwd(const void* q, int64_t q_sb, int64_t q_ss, const voi
                             int64_t dk_sb, int64_t dk_ss, void* dv, int64_t dv_sb, int64_t dv_ss, const int* doc_ids,
                             const int* prefix_len, const void* flags, const float* rope, void* ds, int64_t B, int64_t S, int64_t H,
                             int64_t KVH, int64_t head_dim, float scale, hipStream_t stream) {
-  LLX_REQUIRE(q && k && v && o && d_o && lse && delta && dq && dk && dv, "llx_attn_bwd: null pointer");
-  LLX_REQUIRE(head_dim == HD, "llx_attn_bwd: head_dim=%lld unsupported (only 128)", (long long)head_dim);
-  LLX_REQUIRE(B > 0 && S > 0 && H > 0 && KVH > 0 && H % KVH == 0, "llx_attn_bwd: bad B/S/H/KVH");
-  LLX_REQUIRE(((q_ss | k_ss | v_ss | o_ss | do_ss | q_sb | k_sb | v_sb | o_sb | do_sb) % 8) == 0, "llx_attn_bwd: input strides must keep 16-byte alignment");
-  LLX_REQUIRE(((dq_ss | dk_ss | dv_ss | dq_sb | dk_sb | dv_sb) % 4) == 0, "llx_attn_bwd: output strides must keep 8-byte alignment");
-  LLX_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)d_o) % 16 == 0, "llx_attn_bwd: unaligned input");
-  LLX_REQUIRE(((uintptr_t)dq) % 8 == 0 && ((uintptr_t)dk | (uintptr_t)dv) % 16 == 0 && ((dk_ss | dv_ss | dk_sb | dv_sb) % 8) == 0,
-              "llx_attn_bwd: unaligned output");
-  LLX_REQUIRE(!(doc_ids || prefix_len) || flags, "llx_attn_bwd: tile flags required with doc_ids/prefix_len");
-  LLX_REQUIRE(!rope || (uintptr_t)rope % 16 == 0, "llx_attn_bwd: unaligned rope table");
-  LLX_REQUIRE(!ds || (uintptr_t)ds % 256 == 0, "llx_attn_bwd: the dS buffer must be 256-byte aligned");
-  LLX_REQUIRE(S < (1 << 24) && B * H < (1 << 16), "llx_attn_bwd: S or B*H too large");
-  if (attn_bwd_set_attrs() != LLX_OK) { llx_set_error("llx_attn_bwd: cannot raise LDS limit"); return LLX_ERR_LAUNCH; }
   AttnBwdArgs a;
-  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (const bf16_t*)o; a.d_o = (const bf16_t*)d_o;
-  a.lse = lse; a.delta = delta; a.nlse = delta + B * H * S; a.stamps = nullptr; a.rope = rope; a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv;
-  a.ds = (bf16_t*)ds; a.Sp = (int)(cdiv64(S, 256) * 256);
-  a.q_sb = q_sb; a.q_ss = q_ss; a.k_sb = k_sb; a.k_ss = k_ss; a.v_sb = v_sb; a.v_ss = v_ss; a.o_sb = o_sb; a.o_ss = o_ss;
-  a.do_sb = do_sb; a.do_ss = do_ss; a.dq_sb = dq_sb; a.dq_ss = dq_ss; a.dk_sb = dk_sb; a.dk_ss = dk_ss; a.dv_sb = dv_sb; a.dv_ss = dv_ss;
+  if (int rc = attn_bwd_args("llx_attn_bwd", a, q, q_sb, q_ss, k, k_sb, k_ss, v, v_sb, v_ss, o, o_sb, o_ss, d_o, do_sb, do_ss, lse, delta, dq, dq_sb, dq_ss, dk,
+                             dk_sb, dk_ss, dv, dv_sb, dv_ss, rope, B, S, H, KVH, head_dim, scale)) return rc;
+  LLX_REQUIRE(!(doc_ids || prefix_len) || flags, "llx_attn_bwd: tile flags required with doc_ids/prefix_len");
+  LLX_REQUIRE(!ds || (uintptr_t)ds % 256 == 0, "llx_attn_bwd: the dS buffer must be 256-byte aligned");
   a.doc_ids = doc_ids; a.prefix_len = prefix_len; a.flags = (doc_ids || prefix_len) ? (const uint8_t*)flags : nullptr;
-  a.B = (int)B; a.S = (int)S; a.H = (int)H; a.KVH = (int)KVH;
-  a.scale = scale; a.scale_log2 = scale * 1.4426950408889634f;
-  a.mask = nullptr; a.m_sb = 0; a.m_sq = 0;
-  const dim3 qgrid((unsigned)H, (unsigned)cdiv64(S, BQ), (unsigned)B);
   // (with tile flags the dQ-from-dS kernel keeps its schedule in two 64-bit masks: up to 128 key tiles = 8192 positions)
-  const bool use_ds = ds != nullptr && !g_bwd_stamps && !((doc_ids || prefix_len) && cdiv64(S, BKV) > 128);
-  if (use_ds) {
-    hipLaunchKernelGGL(attn_bwd_delta_kernel, dim3((unsigned)cdiv64(B * S * H, 16)), dim3(256), 0, stream, a);
-    LLX_LAUNCH_CHECK("llx_attn_bwd(delta)");
-  } else {
-    // dQ first: it also publishes delta = rowsum(dO . O) and the sanitised -lse that the dK/dV kernel stages from global memory
-    if (a.flags) hipLaunchKernelGGL(attn_bwd_dq_kernel<BWD_RULE>, qgrid, dim3(256), DQ_LDS_BYTES, stream, a);
-    else hipLaunchKernelGGL(attn_bwd_dq_kernel<BWD_CAUSAL>, qgrid, dim3(256), DQ_LDS_BYTES, stream, a);
-    LLX_LAUNCH_CHECK("llx_attn_bwd(dq)");
+  if (!ds || g_bwd_stamps || (a.flags && cdiv64(S, BKV) > 128)) {
+    if (!a.flags) a.stamps = g_bwd_stamps;
+    return attn_bwd_run("llx_attn_bwd", a, a.flags ? BWD_RULE : BWD_CAUSAL, stream);
   }
-  float* part = delta + 2 * B * H * S;
-  const int64_t nkb = cdiv64(S, DKV2_KEYS);
-  const dim3 kgrid((unsigned)(nkb * B * H));
-  if (use_ds) {
-    if (a.flags) hipLaunchKernelGGL((attn_bwd_dkv3_kernel<BWD_RULE, false, true>), kgrid, dim3(256), DKV3_LDS_BYTES, stream, a, part);
-    else hipLaunchKernelGGL((attn_bwd_dkv3_kernel<BWD_CAUSAL, false, true>), kgrid, dim3(256), DKV3_LDS_BYTES, stream, a, part);
-  } else if (g_bwd_stamps && !a.flags) {
-    a.stamps = g_bwd_stamps;
-    hipLaunchKernelGGL((attn_bwd_dkv3_kernel<BWD_CAUSAL, true, false>), kgrid, dim3(256), DKV3_LDS_BYTES, stream, a, part);
-  } else if (a.flags) hipLaunchKernelGGL((attn_bwd_dkv3_kernel<BWD_RULE, false, false>), kgrid, dim3(256), DKV3_LDS_BYTES, stream, a, part);
-  else hipLaunchKernelGGL((attn_bwd_dkv3_kernel<BWD_CAUSAL, false, false>), kgrid, dim3(256), DKV3_LDS_BYTES, stream, a, part);
-  LLX_LAUNCH_CHECK("llx_attn_bwd(dkv)");
-  const int64_t plane = B * S * KVH * HD;
-  hipLaunchKernelGGL(attn_dkv_reduce_kernel, dim3((unsigned)cdiv64(plane / 8, 256)), dim3(256), 0, stream, a, (const float*)part);
-  LLX_LAUNCH_CHECK("llx_attn_bwd(dkv reduce)");
-  if (use_ds) {
-    const dim3 q2grid((unsigned)H, (unsigned)cdiv64(S, DQ2_BQ), (unsigned)B);
-    if (a.flags) hipLaunchKernelGGL(attn_bwd_dq2_kernel<true>, q2grid, dim3(512), DQ2_LDS_BYTES, stream, a);
-    else hipLaunchKernelGGL(attn_bwd_dq2_kernel<false>, q2grid, dim3(512), DQ2_LDS_BYTES, stream, a);
-    LLX_LAUNCH_CHECK("llx_attn_bwd(dq from dS)");
-  }
+  if (attn_bwd_set_attrs() != LLX_OK) { llx_set_error("llx_attn_bwd: cannot raise LDS limit"); return LLX_ERR_LAUNCH; }
+  a.ds = (bf16_t*)ds; a.Sp = (int)(cdiv64(S, 256) * 256);
+  hipLaunchKernelGGL(attn_bwd_delta_kernel, dim3((unsigned)cdiv64(B * S * H, 16)), dim3(256), 0, stream, a);
+  LLX_LAUNCH_CHECK("llx_attn_bwd(delta)");
+  if (int rc = attn_bwd_dkv("llx_attn_bwd", a.flags ? attn_bwd_dkv3_kernel<BWD_RULE, false, true> : attn_bwd_dkv3_kernel<BWD_CAUSAL, false, true>, a, stream)) return rc;
+  hipLaunchKernelGGL(a.flags ? attn_bwd_dq2_kernel<true> : attn_bwd_dq2_kernel<false>, dim3((unsigned)H, (unsigned)cdiv64(S, DQ2_BQ), (unsigned)B), dim3(512),
+                     DQ2_LDS_BYTES, stream, a);
+  LLX_LAUNCH_CHECK("llx_attn_bwd(dq from dS)");
   return LLX_OK;
 }
 
@@ -1212,39 +1200,12 @@ extern "C" int llx_attn_mask_bwd(const void* q, int64_t q_sb, int64_t q_ss, cons
                                  int64_t dk_sb, int64_t dk_ss, void* dv, int64_t dv_sb, int64_t dv_ss, const void* mask, int64_t m_sb,
                                  int64_t m_sq, const void* flags, const float* rope, int64_t B, int64_t S, int64_t H, int64_t KVH,
                                  int64_t head_dim, float scale, hipStream_t stream) {
-  LLX_REQUIRE(q && k && v && o && d_o && lse && delta && dq && dk && dv && mask && flags, "llx_attn_mask_bwd: null pointer");
-  LLX_REQUIRE(head_dim == HD, "llx_attn_mask_bwd: head_dim=%lld unsupported (only 128)", (long long)head_dim);
-  LLX_REQUIRE(B > 0 && S > 0 && H > 0 && KVH > 0 && H % KVH == 0, "llx_attn_mask_bwd: bad B/S/H/KVH");
-  LLX_REQUIRE(S >= 4, "llx_attn_mask_bwd: S=%lld (>= 4: the mask is read 4 bytes at a time)", (long long)S);
-  LLX_REQUIRE(((q_ss | k_ss | v_ss | o_ss | do_ss | q_sb | k_sb | v_sb | o_sb | do_sb) % 8) == 0, "llx_attn_mask_bwd: input strides must keep 16-byte alignment");
-  LLX_REQUIRE(((dq_ss | dk_ss | dv_ss | dq_sb | dk_sb | dv_sb) % 4) == 0, "llx_attn_mask_bwd: output strides must keep 8-byte alignment");
-  LLX_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)d_o) % 16 == 0, "llx_attn_mask_bwd: unaligned input");
-  LLX_REQUIRE(((uintptr_t)dq) % 8 == 0 && ((uintptr_t)dk | (uintptr_t)dv) % 16 == 0 && ((dk_ss | dv_ss | dk_sb | dv_sb) % 8) == 0,
-              "llx_attn_mask_bwd: unaligned output");
-  LLX_REQUIRE(!rope || (uintptr_t)rope % 16 == 0, "llx_attn_mask_bwd: unaligned rope table");
-  LLX_REQUIRE(S < (1 << 24) && B * H < (1 << 16), "llx_attn_mask_bwd: S or B*H too large");
-  LLX_REQUIRE(m_sq >= S && m_sb >= 0, "llx_attn_mask_bwd: mask rows overlap");
-  if (attn_bwd_set_attrs() != LLX_OK) { llx_set_error("llx_attn_mask_bwd: cannot raise LDS limit"); return LLX_ERR_LAUNCH; }
   AttnBwdArgs a;
-  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (const bf16_t*)o; a.d_o = (const bf16_t*)d_o;
-  a.lse = lse; a.delta = delta; a.nlse = delta + B * H * S; a.stamps = nullptr; a.rope = rope; a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv;
-  a.ds = nullptr; a.Sp = 0;
-  a.q_sb = q_sb; a.q_ss = q_ss; a.k_sb = k_sb; a.k_ss = k_ss; a.v_sb = v_sb; a.v_ss = v_ss; a.o_sb = o_sb; a.o_ss = o_ss;
-  a.do_sb = do_sb; a.do_ss = do_ss; a.dq_sb = dq_sb; a.dq_ss = dq_ss; a.dk_sb = dk_sb; a.dk_ss = dk_ss; a.dv_sb = dv_sb; a.dv_ss = dv_ss;
-  a.doc_ids = nullptr; a.prefix_len = nullptr; a.flags = (const uint8_t*)flags;
-  a.B = (int)B; a.S = (int)S; a.H = (int)H; a.KVH = (int)KVH;
-  a.scale = scale; a.scale_log2 = scale * 1.4426950408889634f;
-  a.mask = (const uint8_t*)mask; a.m_sb = m_sb; a.m_sq = m_sq;
-  // dQ first: it also publishes delta = rowsum(dO . O) and the sanitised -lse that the dK/dV kernel stages from global memory
-  hipLaunchKernelGGL(attn_bwd_dq_kernel<BWD_MASK>, dim3((unsigned)H, (unsigned)cdiv64(S, BQ), (unsigned)B), dim3(256), DQ_LDS_BYTES, stream, a);
-  LLX_LAUNCH_CHECK("llx_attn_mask_bwd(dq)");
-  float* part = delta + 2 * B * H * S;
-  // (a key block without a live tile runs no tile and still writes its zero partials: the reduce then stores exact zeros)
-  hipLaunchKernelGGL((attn_bwd_dkv3_kernel<BWD_MASK, false, false>), dim3((unsigned)(cdiv64(S, DKV2_KEYS) * B * H)), dim3(256), DKV3_LDS_BYTES,
-                     stream, a, part);
-  LLX_LAUNCH_CHECK("llx_attn_mask_bwd(dkv)");
-  const int64_t plane = B * S * KVH * HD;
-  hipLaunchKernelGGL(attn_dkv_reduce_kernel, dim3((unsigned)cdiv64(plane / 8, 256)), dim3(256), 0, stream, a, (const float*)part);
-  LLX_LAUNCH_CHECK("llx_attn_mask_bwd(dkv reduce)");
-  return LLX_OK;
+  if (int rc = attn_bwd_args("llx_attn_mask_bwd", a, q, q_sb, q_ss, k, k_sb, k_ss, v, v_sb, v_ss, o, o_sb, o_ss, d_o, do_sb, do_ss, lse, delta, dq, dq_sb, dq_ss, dk,
+                             dk_sb, dk_ss, dv, dv_sb, dv_ss, rope, B, S, H, KVH, head_dim, scale)) return rc;
+  LLX_REQUIRE(S >= 4, "llx_attn_mask_bwd: S=%lld (>= 4: the mask is read 4 bytes at a time)", (long long)S);
+  LLX_REQUIRE(mask && flags, "llx_attn_mask_bwd: null pointer");
+  LLX_REQUIRE(m_sq >= S && m_sb >= 0, "llx_attn_mask_bwd: mask rows overlap");
+  a.flags = (const uint8_t*)flags; a.mask = (const uint8_t*)mask; a.m_sb = m_sb; a.m_sq = m_sq;
+  return attn_bwd_run("llx_attn_mask_bwd", a, BWD_MASK, stream);
 }

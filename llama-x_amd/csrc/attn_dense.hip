@@ -3,9 +3,7 @@
 // Query length is small there (1 for decode), keys are the whole cache, so this is a bandwidth-bound sweep over K/V:
 // one wave per (batch, head, query row); lane j scores key 64c+j, the wave reduces the online-softmax statistics, then
 // each lane accumulates its two output dims over the 64 keys of the chunk.  Forward only.
-#include "common.h"
-
-#define HD 128
+#include "attn.h"
 
 struct DenseArgs {
   const bf16_t* q; const bf16_t* k; const bf16_t* v; bf16_t* o; const uint8_t* mask;
@@ -73,8 +71,8 @@ extern "C" int llx_attn_dense_fwd(const void* q, int64_t q_sb, int64_t q_sh, int
                                   int64_t o_ss, const void* mask, int64_t m_sb, int64_t m_sh, int64_t m_sq, int64_t B, int64_t H, int64_t KVH,
                                   int64_t Sq, int64_t Skv, int64_t head_dim, float scale, hipStream_t stream) {
   LLX_REQUIRE(q && k && v && o && mask, "llx_attn_dense_fwd: null pointer");
-  LLX_REQUIRE(head_dim == HD, "llx_attn_dense_fwd: head_dim=%lld unsupported (only 128)", (long long)head_dim);
-  LLX_REQUIRE(B > 0 && H > 0 && KVH > 0 && H % KVH == 0 && Sq > 0 && Skv > 0, "llx_attn_dense_fwd: bad sizes");
+  if (int rc = attn_check_shape("llx_attn_dense_fwd", B, Sq, H, KVH, head_dim)) return rc;
+  LLX_REQUIRE(Skv > 0, "llx_attn_dense_fwd: bad sizes");
   LLX_REQUIRE(((k_sb | k_sh | k_ss) % 8) == 0 && (uintptr_t)k % 16 == 0, "llx_attn_dense_fwd: K rows must be 16-byte aligned");
   LLX_REQUIRE(((v_sb | v_sh | v_ss | o_sb | o_sh | o_ss) % 2) == 0, "llx_attn_dense_fwd: V/O strides must be even");
   DenseArgs a;

@@ -14,20 +14,11 @@
 //   O^T += V^T.P^T (P^T taken straight from the S^T accumulator registers as the MFMA B operand; V^T fragments
 //                   come from the row-major LDS tile through ds_read_b64_tr_b16)
 // K/V tiles are double-buffered in LDS by global_load_lds with the bank swizzle applied on the source address.
-#include "common.h"
-#include <mutex>
-#include <type_traits>
+#include "attn.h"
 
-#define HD 128
-#define BQ 128
-#define BKV 64
-#define KV_TILE_BYTES (BKV * HD * 2)        // 16 KiB
+#define KV_TILE_BYTES TILE_BYTES
 #define ATT_STAGE_BYTES (2 * KV_TILE_BYTES)  // K + V
 #define ATT_LDS_BYTES (2 * ATT_STAGE_BYTES)  // 64 KiB
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
-typedef __attribute__((address_space(3))) s16x4_t lds_s16x4;
 
 struct AttnFwdArgs {
   const bf16_t* q; const bf16_t* k; const bf16_t* v; bf16_t* o; float* lse;
@@ -90,7 +81,6 @@ __global__ void attn_tile_flags_kernel(const int* __restrict__ doc_ids, const in
   if (threadIdx.x == 0) flags[((int64_t)b * nqb + qb) * nkt + kt] = s_any ? (s_all ? 2 : 1) : 0;
 }
 
-
 extern "C" int64_t llx_attn_flags_bytes(int64_t B, int64_t S) { return B * cdiv64(S, BQ) * cdiv64(S, BKV); }
 
 // flags: llx_attn_flags_bytes(B,S) bytes (device), filled here. Needed only when doc_ids or prefix_len is used.
@@ -103,39 +93,43 @@ extern "C" int llx_attn_tile_flags(const int* doc_ids, const int* prefix_len, vo
   return LLX_OK;
 }
 
+// The forward entries' common operands (S = query rows), checked and filled in; the fields of rule, mask and stamps stay zero.
+static int attn_fwd_args(const char* fn, AttnFwdArgs& a, const void* q, int64_t q_sb, int64_t q_ss, const void* k, int64_t k_sb, int64_t k_ss,
+                         const void* v, int64_t v_sb, int64_t v_ss, void* o, int64_t o_sb, int64_t o_ss, float* lse, int64_t B, int64_t S,
+                         int64_t H, int64_t KVH, int64_t head_dim, float scale) {
+  LLX_REQUIRE(q && k && v && o, "%s: null pointer", fn);
+  if (int rc = attn_check_shape(fn, B, S, H, KVH, head_dim)) return rc;
+  LLX_REQUIRE((q_ss % 8 | k_ss % 8 | v_ss % 8 | o_ss % 4 | q_sb % 8 | k_sb % 8 | v_sb % 8 | o_sb % 4) == 0, "%s: strides must keep 16-byte alignment", fn);
+  LLX_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 == 0 && (uintptr_t)o % 8 == 0, "%s: unaligned pointer", fn);
+  a = {};
+  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (bf16_t*)o; a.lse = lse;
+  a.q_sb = q_sb; a.q_ss = q_ss; a.k_sb = k_sb; a.k_ss = k_ss; a.v_sb = v_sb; a.v_ss = v_ss; a.o_sb = o_sb; a.o_ss = o_ss;
+  a.B = (int)B; a.S = (int)S; a.H = (int)H; a.KVH = (int)KVH;
+  a.scale_log2 = scale * 1.4426950408889634f;
+  return LLX_OK;
+}
+
+// Any forward instance: 8 waves per 256 query rows of a (head, batch).  The static is initialised once, by one thread (checkpointing enters from several).
+static int attn_fwd_launch(const char* fn, void (*kernel)(const AttnFwdArgs), const AttnFwdArgs& a, hipStream_t stream) {
+  static const hipError_t err = attn_lds_limit(ATT_LDS_BYTES, attn_fwd_kernel<false, false, 8>, attn_fwd_kernel<true, false, 8>,
+                                               attn_fwd_kernel<false, true, 8>, attn_mask_fwd_kernel);
+  if (err != hipSuccess) { llx_set_error("%s: %s", fn, hipGetErrorString(err)); return LLX_ERR_LAUNCH; }
+  hipLaunchKernelGGL(kernel, dim3((unsigned)a.H, (unsigned)cdiv64(a.S, 256), (unsigned)a.B), dim3(512), ATT_LDS_BYTES, stream, a);
+  LLX_LAUNCH_CHECK(fn);
+  return LLX_OK;
+}
+
 // strides are in elements: *_sb per batch, *_ss per sequence position; head h starts at element h*128 of a row.
 extern "C" int llx_attn_fwd(const void* q, int64_t q_sb, int64_t q_ss, const void* k, int64_t k_sb, int64_t k_ss, const void* v,
                             int64_t v_sb, int64_t v_ss, void* o, int64_t o_sb, int64_t o_ss, float* lse, const int* doc_ids,
                             const int* prefix_len, const void* flags, int64_t B, int64_t S, int64_t H, int64_t KVH, int64_t head_dim,
                             float scale, hipStream_t stream) {
-  LLX_REQUIRE(q && k && v && o, "llx_attn_fwd: null pointer");
-  LLX_REQUIRE(head_dim == HD, "llx_attn_fwd: head_dim=%lld unsupported (only 128)", (long long)head_dim);
-  LLX_REQUIRE(B > 0 && S > 0 && H > 0 && KVH > 0 && H % KVH == 0, "llx_attn_fwd: bad B/S/H/KVH");
-  LLX_REQUIRE((q_ss % 8 | k_ss % 8 | v_ss % 8 | o_ss % 4 | q_sb % 8 | k_sb % 8 | v_sb % 8 | o_sb % 4) == 0, "llx_attn_fwd: strides must keep 16-byte alignment");
-  LLX_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 == 0 && (uintptr_t)o % 8 == 0, "llx_attn_fwd: unaligned pointer");
+  AttnFwdArgs a;
+  if (int rc = attn_fwd_args("llx_attn_fwd", a, q, q_sb, q_ss, k, k_sb, k_ss, v, v_sb, v_ss, o, o_sb, o_ss, lse, B, S, H, KVH, head_dim, scale)) return rc;
   LLX_REQUIRE(!(doc_ids || prefix_len) || flags, "llx_attn_fwd: tile flags required with doc_ids/prefix_len");
-  LLX_REQUIRE(S < (1 << 24), "llx_attn_fwd: S too large");
-  {
-    static std::once_flag once;  // forward may be entered from several host threads (activation checkpointing recomputes it in backward)
-    static hipError_t err = hipSuccess;
-    std::call_once(once, [] {
-      const void* fns[2] = {(const void*)attn_fwd_kernel<false, false, 8>, (const void*)attn_fwd_kernel<true, false, 8>};
-      for (int i = 0; i < 2 && err == hipSuccess; ++i) err = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, ATT_LDS_BYTES);
-    });
-    if (err != hipSuccess) { llx_set_error("llx_attn_fwd: %s", hipGetErrorString(err)); return LLX_ERR_LAUNCH; }
-  }
-  AttnFwdArgs a = {};
-  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (bf16_t*)o; a.lse = lse;
-  a.q_sb = q_sb; a.q_ss = q_ss; a.k_sb = k_sb; a.k_ss = k_ss; a.v_sb = v_sb; a.v_ss = v_ss; a.o_sb = o_sb; a.o_ss = o_ss;
   a.doc_ids = doc_ids; a.prefix_len = prefix_len; a.flags = (doc_ids || prefix_len) ? (const uint8_t*)flags : nullptr;
-  a.B = (int)B; a.S = (int)S; a.H = (int)H; a.KVH = (int)KVH;
-  a.scale_log2 = scale * 1.4426950408889634f;
-  a.stamps = nullptr;
-  const dim3 grid((unsigned)H, (unsigned)cdiv64(S, 256), (unsigned)B), block(512);
-  if (a.flags) hipLaunchKernelGGL((attn_fwd_kernel<true, false, 8>), grid, block, ATT_LDS_BYTES, stream, a);
-  else hipLaunchKernelGGL((attn_fwd_kernel<false, false, 8>), grid, block, ATT_LDS_BYTES, stream, a);
-  LLX_LAUNCH_CHECK("llx_attn_fwd");
-  return LLX_OK;
+  LLX_REQUIRE(S < (1 << 24), "llx_attn_fwd: S too large");
+  return attn_fwd_launch("llx_attn_fwd", a.flags ? attn_fwd_kernel<true, false, 8> : attn_fwd_kernel<false, false, 8>, a, stream);
 }
 
 // Tile classes of a dense bool mask [B | 1, Sq, Skv] (row stride m_sq, batch stride m_sb, bytes): the layout llx_attn_tile_flags writes,
@@ -192,32 +186,16 @@ extern "C" int llx_attn_mask_fwd(const void* q, int64_t q_sb, int64_t q_ss, cons
                                  const void* v, int64_t v_sb, int64_t v_sh, int64_t v_ss, void* o, int64_t o_sb, int64_t o_ss, float* lse,
                                  const void* mask, int64_t m_sb, int64_t m_sq, const void* flags, int64_t B, int64_t Sq, int64_t Skv,
                                  int64_t H, int64_t KVH, int64_t head_dim, float scale, hipStream_t stream) {
-  LLX_REQUIRE(q && k && v && o && mask && flags, "llx_attn_mask_fwd: null pointer");
-  LLX_REQUIRE(head_dim == HD, "llx_attn_mask_fwd: head_dim=%lld unsupported (only 128)", (long long)head_dim);
-  LLX_REQUIRE(B > 0 && Sq > 0 && H > 0 && KVH > 0 && H % KVH == 0 && B < 65536, "llx_attn_mask_fwd: bad B/Sq/H/KVH");
+  AttnFwdArgs a;
+  if (int rc = attn_fwd_args("llx_attn_mask_fwd", a, q, q_sb, q_ss, k, k_sb, k_ss, v, v_sb, v_ss, o, o_sb, o_ss, lse, B, Sq, H, KVH, head_dim, scale)) return rc;
+  LLX_REQUIRE(B < 65536, "llx_attn_mask_fwd: bad B/Sq/H/KVH");
   LLX_REQUIRE(Skv >= 4 && Skv < (1 << 24) && Sq < (1 << 24), "llx_attn_mask_fwd: Skv=%lld (>= 4) / Sq=%lld out of range", (long long)Skv, (long long)Sq);
-  LLX_REQUIRE((q_ss % 8 | k_ss % 8 | v_ss % 8 | o_ss % 4 | q_sb % 8 | k_sb % 8 | v_sb % 8 | o_sb % 4 | k_sh % 8 | v_sh % 8) == 0,
-              "llx_attn_mask_fwd: strides must keep 16-byte alignment");
+  LLX_REQUIRE((k_sh % 8 | v_sh % 8) == 0, "llx_attn_mask_fwd: strides must keep 16-byte alignment");
   LLX_REQUIRE(k_ss >= 0 && v_ss >= 0 && k_ss < (1 << 24) && v_ss < (1 << 24), "llx_attn_mask_fwd: K/V position stride out of range");
-  LLX_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 == 0 && (uintptr_t)o % 8 == 0, "llx_attn_mask_fwd: unaligned pointer");
+  LLX_REQUIRE(mask && flags, "llx_attn_mask_fwd: null pointer");
   LLX_REQUIRE(m_sq >= Skv && m_sb >= 0, "llx_attn_mask_fwd: mask rows overlap");
-  {
-    static std::once_flag once;
-    static hipError_t err = hipSuccess;
-    std::call_once(once, [] { err = hipFuncSetAttribute((const void*)attn_mask_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ATT_LDS_BYTES); });
-    if (err != hipSuccess) { llx_set_error("llx_attn_mask_fwd: %s", hipGetErrorString(err)); return LLX_ERR_LAUNCH; }
-  }
-  AttnFwdArgs a = {};
-  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (bf16_t*)o; a.lse = lse;
-  a.q_sb = q_sb; a.q_ss = q_ss; a.k_sb = k_sb; a.k_ss = k_ss; a.v_sb = v_sb; a.v_ss = v_ss; a.o_sb = o_sb; a.o_ss = o_ss;
-  a.doc_ids = nullptr; a.prefix_len = nullptr; a.flags = (const uint8_t*)flags;
-  a.B = (int)B; a.S = (int)Sq; a.H = (int)H; a.KVH = (int)KVH;
-  a.scale_log2 = scale * 1.4426950408889634f;
-  a.stamps = nullptr;
-  a.Skv = (int)Skv; a.k_sh = k_sh; a.v_sh = v_sh; a.mask = (const uint8_t*)mask; a.m_sb = m_sb; a.m_sq = m_sq;
-  hipLaunchKernelGGL(attn_mask_fwd_kernel, dim3((unsigned)H, (unsigned)cdiv64(Sq, 256), (unsigned)B), dim3(512), ATT_LDS_BYTES, stream, a);
-  LLX_LAUNCH_CHECK("llx_attn_mask_fwd");
-  return LLX_OK;
+  a.flags = (const uint8_t*)flags; a.Skv = (int)Skv; a.k_sh = k_sh; a.v_sh = v_sh; a.mask = (const uint8_t*)mask; a.m_sb = m_sb; a.m_sq = m_sq;
+  return attn_fwd_launch("llx_attn_mask_fwd", attn_mask_fwd_kernel, a, stream);
 }
 
 // Diagnostic: resident workgroups per CU the runtime grants the forward kernel (occupancy API; advisory).
@@ -232,13 +210,9 @@ extern "C" int llx_debug_attn_fwd_occupancy(void) {
 // Diagnostic build of the forward kernel with in-kernel s_memtime stamps (5 per key tile) for one wave; timing only.
 extern "C" int llx_debug_attn_fwd_stamps(const void* q, const void* k, const void* v, void* o, int64_t S, int64_t H, int64_t KVH,
                                          unsigned long long* stamps, hipStream_t stream) {
-  AttnFwdArgs a = {};
-  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (bf16_t*)o; a.lse = nullptr;
-  a.q_ss = H * HD; a.q_sb = S * a.q_ss; a.k_ss = KVH * HD; a.k_sb = S * a.k_ss; a.v_ss = a.k_ss; a.v_sb = a.k_sb; a.o_ss = a.q_ss; a.o_sb = a.q_sb;
-  a.doc_ids = nullptr; a.prefix_len = nullptr; a.flags = nullptr; a.B = 1; a.S = (int)S; a.H = (int)H; a.KVH = (int)KVH;
-  a.scale_log2 = 0.08838834764f * 1.4426950408889634f; a.stamps = stamps;
-  hipFuncSetAttribute((const void*)attn_fwd_kernel<false, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT_LDS_BYTES);
-  hipLaunchKernelGGL((attn_fwd_kernel<false, true, 8>), dim3((unsigned)H, (unsigned)cdiv64(S, 256), 1), dim3(512), ATT_LDS_BYTES, stream, a);
-  LLX_LAUNCH_CHECK("llx_debug_attn_fwd_stamps");
-  return LLX_OK;
+  AttnFwdArgs a;
+  if (int rc = attn_fwd_args("llx_debug_attn_fwd_stamps", a, q, S * H * HD, H * HD, k, S * KVH * HD, KVH * HD, v, S * KVH * HD, KVH * HD, o,
+                             S * H * HD, H * HD, nullptr, 1, S, H, KVH, HD, 0.08838834764f)) return rc;
+  a.stamps = stamps;
+  return attn_fwd_launch("llx_debug_attn_fwd_stamps", attn_fwd_kernel<false, true, 8>, a, stream);
 }

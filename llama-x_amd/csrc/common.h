@@ -42,6 +42,7 @@ typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2_t;
 
 #define LLX_WAVE 64
+#define HD 128  // head dim of every attention kernel and of the q|k|v epilogue of the decode weight streams
 
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
 // round-to-nearest-even, NaN preserving (hipcc emits v_cvt_pk_bf16_f32)

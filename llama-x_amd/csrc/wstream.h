@@ -5,9 +5,7 @@
 // and differ only in how a group of output features is summed.  Here: the constants (epilogues, weight kinds), the operand block, the norm-on-load pieces, the
 // epilogue (one place where the roundings of the four epilogues live) and the host-side checks and fill of the operand block.
 #pragma once
-#include "common.h"
-
-#define HD 128
+#include "common.h"  // HD
 
 // epilogue 0: out [M, N] | 1: + res [M, N] | 2 (q|k|v): rows [0, n_q) RoPE -> out [M, n_q]; [n_q, n_q + n_k) RoPE -> k cache; rest ->
 // v cache | 3 (gate|up = W0|W1, N = 2 n_0): out [M, N/2] = silu(gate) * up

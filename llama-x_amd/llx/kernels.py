@@ -28,6 +28,23 @@ GEMM_TRACE = None
 ATTN_TRACE = None
 
 
+def _trace_begin(trace):
+    """Start of one GEMM_TRACE / ATTN_TRACE entry; None while tracing is off.  `trace` is the module global as the caller reads it at the
+    call (bench.py rebinds the globals to fresh lists)."""
+    if trace is None:
+        return None
+    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+    ev[0].record()
+    return ev
+
+
+def _trace_end(trace, ev, *info):
+    """End of the entry _trace_begin started: (start_event, end_event, *info) joins the trace."""
+    if ev is not None:
+        ev[1].record()
+        trace.append((ev[0], ev[1], *info))
+
+
 def _lib():
     return L.load()
 
@@ -154,10 +171,7 @@ def gemm_nt(a: Tensor, b: Tensor, *, out: Optional[Tensor] = None, a2: Optional[
         lde = e.stride(0)
     elif epilogue != EPI_NONE:
         assert e is not None and e.shape == (N,) and e.is_contiguous()
-    ev = None
-    if GEMM_TRACE is not None:
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
+    ev = _trace_begin(GEMM_TRACE)
     if rope is not None:
         table, rs, rc = rope
         assert epilogue == EPI_NONE and table.dtype is torch.float32 and table.is_contiguous() and table.shape[0] >= rs and table.shape[1:] == (64, 2)
@@ -174,11 +188,10 @@ def gemm_nt(a: Tensor, b: Tensor, *, out: Optional[Tensor] = None, a2: Optional[
                                         L.ptr(a2), a2.stride(0) if a2 is not None else 0, L.ptr(b2), b2.stride(0) if b2 is not None else 0, K2,
                                         epilogue, L.ptr(e), lde, L.stream()), "llx_gemm_nt_bf16")
     if ev is not None:
-        ev[1].record()
         kk = K + (K2 if k2_eff is None else min(float(k2_eff), K2))
         Mw = M if m_expect is None else float(m_expect)  # rows actually wanted (row-limited launches: the labelled rows)
-        GEMM_TRACE.append((ev[0], ev[1], 2.0 * Mw * N * kk, 2.0 * (Mw * kk + N * kk + Mw * N * (2 if epilogue == EPI_RESIDUAL else 1)), "bf16",
-                           gemm_kernel_launches(M, N, 8 if rope is not None else epilogue)))
+        _trace_end(GEMM_TRACE, ev, 2.0 * Mw * N * kk, 2.0 * (Mw * kk + N * kk + Mw * N * (2 if epilogue == EPI_RESIDUAL else 1)), "bf16",
+                   gemm_kernel_launches(M, N, 8 if rope is not None else epilogue))
     return out
 
 
@@ -192,16 +205,12 @@ def gemm_nt_splitk(a: Tensor, b: Tensor, splits: int, *, m_valid: Optional[Tenso
     M, K = a.shape
     N = b.shape[0]
     part = torch.empty(splits, M, N, device=a.device, dtype=torch.float32)
-    ev = None
-    if GEMM_TRACE is not None:
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
+    ev = _trace_begin(GEMM_TRACE)
     L.check(_lib().llx_gemm_nt_bf16_splitk(L.ptr(a), a.stride(0), L.ptr(b), b.stride(0), L.ptr(part), M, N, K, splits, L.ptr(m_valid), L.stream()),
             "llx_gemm_nt_bf16_splitk")
     if ev is not None:
-        ev[1].record()
         Mw = M if m_expect is None else float(m_expect)
-        GEMM_TRACE.append((ev[0], ev[1], 2.0 * Mw * N * K, 2.0 * (Mw * K + N * K) + 4.0 * splits * Mw * N, "bf16", 1))
+        _trace_end(GEMM_TRACE, ev, 2.0 * Mw * N * K, 2.0 * (Mw * K + N * K) + 4.0 * splits * Mw * N, "bf16", 1)
     out = torch.empty(M, N, device=a.device, dtype=BF16)
     assert inv is None or (inv.dtype is torch.int32 and inv.numel() == M)
     assert dev_scalar is None or (dev_scalar.dtype is torch.float32 and dev_scalar.numel() == 1)
@@ -319,18 +328,14 @@ def gemm_tn(a: Tensor, b: Tensor, m_valid: Optional[Tensor] = None, m_expect: Op
             raise L.LlxError("gemm_tn: a device-side row count needs the TN kernel's shapes (dimensions multiples of 8, 16-byte aligned rows)")
         return gemm_nt(transpose(a, 64), transpose(b, 64))
     out = torch.empty(N1, N2, device=a.device, dtype=BF16)
-    ev = None
-    if GEMM_TRACE is not None:
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
+    ev = _trace_begin(GEMM_TRACE)
     if m_valid is not None:
         assert m_valid.dtype is torch.int32 and m_valid.is_cuda and m_valid.numel() == 1
     L.check(_lib().llx_gemm_tn_bf16_rows(L.ptr(a), a.stride(0), L.ptr(b), b.stride(0), L.ptr(out), out.stride(0), M, N1, N2,
                                          L.ptr(m_valid) if m_valid is not None else None, L.stream()), "llx_gemm_tn_bf16")
     if ev is not None:
-        ev[1].record()
         Me = M if m_expect is None else m_expect
-        GEMM_TRACE.append((ev[0], ev[1], 2.0 * Me * N1 * N2, 2.0 * (Me * N1 + Me * N2 + N1 * N2), "bf16_tn", 1))
+        _trace_end(GEMM_TRACE, ev, 2.0 * Me * N1 * N2, 2.0 * (Me * N1 + Me * N2 + N1 * N2), "bf16_tn", 1)
     return out
 
 
@@ -551,20 +556,13 @@ class MaskSpec:
         if self._key == key:
             return self
         if self.dense is not None:
-            m = self.dense
-            while m.dim() < 4:
-                m = m.unsqueeze(0)
-            if m.shape[0] not in (1, B) or m.shape[2:] != (S, S):
+            norm = _mask_norm(self.dense.to(device), B, S, S)
+            if norm is None:
                 raise L.LlxError(f"MaskSpec: dense mask of shape {tuple(self.dense.shape)} does not fit batch {B}, sequence {S}")
             if S < 4:
                 raise L.LlxError("MaskSpec: a dense mask needs S >= 4 (the kernels read it 4 bytes at a time)")
-            from . import ops  # (ops imports this module)
-
-            m = m.to(device)
-            if m.stride(3) != 1 or m.stride(2) < S:
-                m = m.contiguous()
-            self._rows = m  # [B | 1, 1, S, S], last dim dense: the tensor attn_mask_fwd / attn_mask_bwd are called with
-            self._flags = ops._cached(m, f"maskflags{B}", lambda: attn_mask_flags(m, B))  # (the cache those two look into)
+            self._rows = norm[0]  # [B | 1, 1, S, S], last dim dense: the tensor attn_mask_fwd / attn_mask_bwd are called with
+            self._flags = _mask_flags(self._rows, B)  # (the cache those two look into)
             self._key = key
             return self
         d = self.doc_ids
@@ -598,14 +596,10 @@ def maskspec_from_dense(mask: Tensor, B: int, S: int) -> Optional[MaskSpec]:
     sub-diagonal (q-1 and q share a document iff mask[q, q-1]), the prefix off the part above the diagonal (its last visible column);
     the rule is then evaluated densely and compared bit for bit - any other mask (per-head masks, non-contiguous document ids,
     arbitrary patterns) gives None.  One host synchronisation (the comparison) per distinct mask tensor; cached on the tensor."""
-    if mask.dtype is not torch.bool or mask.shape[-2:] != (S, S):
+    norm = _mask_norm(mask, B, S, S) if mask.dtype is torch.bool else None
+    if norm is None:
         return None
-    m = mask
-    while m.dim() < 4:
-        m = m.unsqueeze(0)
-    if m.dim() != 4 or m.shape[1] != 1 or m.shape[0] not in (1, B):
-        return None
-    m = m[:, 0].expand(B, S, S)
+    m = norm[0][:, 0].expand(B, S, S)
     idx = torch.arange(S, device=m.device)
     upper = m & (idx[None, :, None] < idx[None, None, :])            # allowed pairs with k > q: only the prefix term can make them
     seen = upper.any(dim=1)                                           # [B, S]: column k visible from some earlier row
@@ -646,38 +640,41 @@ def attn_fwd(q: Tensor, k: Tensor, v: Tensor, mask: Optional[MaskSpec] = None) -
     return o, lse
 
 
-def _trace_begin(trace):
-    if trace is None:
-        return None
-    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-    ev[0].record()
-    return ev
-
-
-def _trace_end(trace, ev, *info):
-    if ev is not None:
-        ev[1].record()
-        trace.append((ev[0], ev[1], *info))
-
-
 _ATTN_BWD_DS = os.environ.get("LLX_ATTN_BWD_DS", "0") == "1"
 _ATTN_BWD_DS_MAX = int(float(os.environ.get("LLX_ATTN_BWD_DS_MAX_GB", "16")) * 2**30)
+
+
+def _attn_bwd_operands(q: Tensor, k: Tensor, v: Tensor, o: Tensor, do: Tensor, lse: Tensor, dq: Tensor, dk: Tensor, dv: Tensor,
+                       rope: Optional[Tensor]):
+    """What attn_bwd and attn_mask_bwd share: the checks on q .. dv, lse and rope, the fp32 workspace (delta + dK/dV partials) and the
+    leading (q .. dv) and trailing (B .. stream) arguments of the C entry points.  Returns (leading, trailing, workspace): the caller
+    holds the workspace until its launch is issued."""
+    _chk_bf16(q, k, v, o, do, dq, dk, dv)
+    B, S, H, hd = q.shape
+    KVH = k.shape[2]
+    if rope is not None:
+        assert rope.dtype is torch.float32 and rope.is_contiguous() and rope.shape[0] >= S and rope.shape[1:] == (64, 2)
+    for t in (q, k, v, o, do, dq, dk, dv):
+        assert t.stride(3) == 1 and t.stride(2) == hd
+    assert lse.shape == (B, H, S) and lse.dtype is torch.float32 and lse.is_contiguous()
+    delta = torch.empty(_lib().llx_attn_bwd_workspace_bytes(B, S, H, KVH) // 4, device=q.device, dtype=torch.float32)
+    lead = [L.ptr(q), q.stride(0), q.stride(1), L.ptr(k), k.stride(0), k.stride(1), L.ptr(v), v.stride(0), v.stride(1), L.ptr(o), o.stride(0),
+            o.stride(1), L.ptr(do), do.stride(0), do.stride(1), L.ptr(lse), L.ptr(delta), L.ptr(dq), dq.stride(0), dq.stride(1), L.ptr(dk),
+            dk.stride(0), dk.stride(1), L.ptr(dv), dv.stride(0), dv.stride(1)]
+    return lead, [B, S, H, KVH, hd, 1.0 / math.sqrt(hd), L.stream()], delta
 
 
 def attn_bwd(q: Tensor, k: Tensor, v: Tensor, o: Tensor, do: Tensor, lse: Tensor, dq: Tensor, dk: Tensor, dv: Tensor,
              mask: Optional[MaskSpec] = None, rope: Optional[Tensor] = None) -> None:
     """rope (fp32 table [>= S, 64, 2]): q, k are the rotated projections; dq, dk come out as gradients of the un-rotated ones."""
-    _chk_bf16(q, k, v, o, do, dq, dk, dv)
-    if rope is not None:
-        assert rope.dtype is torch.float32 and rope.is_contiguous() and rope.shape[0] >= q.shape[1] and rope.shape[1:] == (64, 2)
-    B, S, H, hd = q.shape
-    KVH = k.shape[2]
-    for t in (q, k, v, o, do, dq, dk, dv):
-        assert t.stride(3) == 1 and t.stride(2) == hd
-    if mask is not None and mask.dense is not None:
+    B, S, H = q.shape[:3]
+    d = p = fl = None
+    if mask is not None:
         mask = mask.prepared(B, S, q.device)
-        return attn_mask_bwd(q, k, v, o, do, lse, dq, dk, dv, mask._rows, rope=rope)
-    delta = torch.empty(_lib().llx_attn_bwd_workspace_bytes(B, S, H, KVH) // 4, device=q.device, dtype=torch.float32)  # delta + dK/dV partials
+        if mask.dense is not None:
+            return attn_mask_bwd(q, k, v, o, do, lse, dq, dk, dv, mask._rows, rope=rope)
+        d, p, fl = mask.doc_ids, mask.prefix_len, mask._flags
+    lead, trail, ws = _attn_bwd_operands(q, k, v, o, do, lse, dq, dk, dv, rope)
     # LLX_ATTN_BWD_DS=1: dS^T scratch (bf16 [B, H, Sp, Sp], 1.07 GB at S = 4096; capped by LLX_ATTN_BWD_DS_MAX_GB, default 16): with it every
     # product of the backward is computed once and dQ becomes a tiled product over the stored dS^T.  Measured at S = 4096 (DESIGN.md): the
     # two routes take the same time (the dS^T round trip is bound by the CUs' fill rate), so the default is the route without scratch,
@@ -686,18 +683,32 @@ def attn_bwd(q: Tensor, k: Tensor, v: Tensor, o: Tensor, do: Tensor, lse: Tensor
     ds_bytes = _lib().llx_attn_bwd_ds_bytes(B, S, H)
     if _ATTN_BWD_DS and ds_bytes <= _ATTN_BWD_DS_MAX:
         ds = torch.empty(ds_bytes // 2, device=q.device, dtype=BF16)
-    d = p = fl = None
-    if mask is not None:
-        mask = mask.prepared(B, S, q.device)
-        d, p, fl = mask.doc_ids, mask.prefix_len, mask._flags
     ev = _trace_begin(ATTN_TRACE)
-    L.check(_lib().llx_attn_bwd(L.ptr(q), q.stride(0), q.stride(1), L.ptr(k), k.stride(0), k.stride(1), L.ptr(v), v.stride(0), v.stride(1),
-                                L.ptr(o), o.stride(0), o.stride(1), L.ptr(do), do.stride(0), do.stride(1), L.ptr(lse), L.ptr(delta),
-                                L.ptr(dq), dq.stride(0), dq.stride(1), L.ptr(dk), dk.stride(0), dk.stride(1), L.ptr(dv), dv.stride(0),
-                                dv.stride(1), L.ptr(d), L.ptr(p), L.ptr(fl), L.ptr(rope), L.ptr(ds), B, S, H, KVH, hd, 1.0 / math.sqrt(hd),
-                                L.stream()),
-            "llx_attn_bwd")
+    L.check(_lib().llx_attn_bwd(*lead, L.ptr(d), L.ptr(p), L.ptr(fl), L.ptr(rope), L.ptr(ds), *trail), "llx_attn_bwd")
     _trace_end(ATTN_TRACE, ev, "bwd", B, S, H)
+
+
+def _mask_norm(mask: Tensor, B: int, Sq: int, Skv: int, H: Optional[int] = None) -> Optional[tuple[Tensor, int, int]]:
+    """The one reading of a bool attention mask [Sq, Skv], [B | 1, Sq, Skv] or [B | 1, H | 1, Sq, Skv]: (m, m_sb, m_sh) with m the 4-d
+    view, last dim dense, and the batch / head strides the kernels take (0 = broadcast) - or None if the mask does not fit.  With H the
+    mask may be per head (attn_dense_fwd, attn_decode).  Without H it must be broadcast over heads and is bound for the MFMA tile loops
+    (attn_mask_fwd / attn_mask_bwd and their tile flags), which read a row 4 bytes at a time: there a row stride below Skv
+    (overlapping rows) is copied too.  No other copy is made: a dense last dim goes to the kernels as it lies."""
+    m = mask
+    while m.dim() < 4:
+        m = m.unsqueeze(0)
+    if m.dim() != 4 or m.shape[2:] != (Sq, Skv) or m.shape[0] not in (1, B) or m.shape[1] not in ((1,) if H is None else (1, H)):
+        return None
+    if m.stride(3) != 1 or (H is None and m.stride(2) < Skv):
+        m = m.contiguous()
+    return m, (m.stride(0) if m.shape[0] != 1 else 0), (m.stride(1) if m.shape[1] != 1 else 0)
+
+
+def _mask_flags(mask: Tensor, B: int) -> Tensor:
+    """The tile classes of a mask tensor, computed once per tensor (cached on it: every layer and both directions of a step share them)."""
+    from . import ops  # (ops imports this module)
+
+    return ops._cached(mask, f"maskflags{B}", lambda: attn_mask_flags(mask, B))
 
 
 def attn_dense_fwd(q: Tensor, k: Tensor, v: Tensor, mask: Tensor) -> Tensor:
@@ -707,17 +718,11 @@ def attn_dense_fwd(q: Tensor, k: Tensor, v: Tensor, mask: Tensor) -> Tensor:
     L.require_cuda(mask)
     B, H, Sq, hd = q.shape
     KVH, Skv = k.shape[1], k.shape[2]
-    assert mask.dtype is torch.bool and mask.shape[-2:] == (Sq, Skv)
+    norm = _mask_norm(mask, B, Sq, Skv, H)
+    assert mask.dtype is torch.bool and norm is not None, "mask must be bool and broadcastable to [B, H, Sq, Skv]"
+    m, m_sb, m_sh = norm
     for t in (q, k, v):
         assert t.stride(3) == 1
-    m = mask
-    while m.dim() < 4:
-        m = m.unsqueeze(0)
-    m = m.expand(B if m.shape[0] != 1 else 1, H if m.shape[1] != 1 else 1, Sq, Skv)
-    if m.stride(3) != 1:
-        m = m.contiguous()
-    m_sb = m.stride(0) if m.shape[0] != 1 else 0
-    m_sh = m.stride(1) if m.shape[1] != 1 else 0
     o = torch.empty(B, H, Sq, hd, device=q.device, dtype=BF16)
     L.check(_lib().llx_attn_dense_fwd(L.ptr(q), q.stride(0), q.stride(1), q.stride(2), L.ptr(k), k.stride(0), k.stride(1), k.stride(2),
                                       L.ptr(v), v.stride(0), v.stride(1), v.stride(2), L.ptr(o), o.stride(0), o.stride(1), o.stride(2),
@@ -726,26 +731,18 @@ def attn_dense_fwd(q: Tensor, k: Tensor, v: Tensor, mask: Tensor) -> Tensor:
     return o
 
 
-def _mask_4d(mask: Tensor, B: int, Sq: int, Skv: int) -> Optional[Tensor]:
-    """The mask as [B | 1, 1, Sq, Skv] if it is broadcast over heads, else None (per-head masks)."""
-    m = mask
-    while m.dim() < 4:
-        m = m.unsqueeze(0)
-    return m if m.dim() == 4 and m.shape[1] == 1 and m.shape[0] in (1, B) and m.shape[2:] == (Sq, Skv) else None
-
-
-def _mask_rows(mask: Tensor, B: int, Sq: int, Skv: int) -> Optional[Tensor]:
-    """The bool mask as [B | 1, Sq, Skv] with a dense last dim if it is broadcast over heads, else None."""
-    m = _mask_4d(mask, B, Sq, Skv)
-    if m is None:
-        return None
-    m = m[:, 0]
-    return m if m.stride(2) == 1 and m.stride(1) >= Skv else m.contiguous()
+def _mask_rows(mask: Tensor, B: int, Sq: int, Skv: int) -> tuple[Tensor, int]:
+    """(m, m_sb) of a bool mask broadcast over heads, as the MFMA tile loops take it (m.stride(2) is their row stride)."""
+    norm = _mask_norm(mask, B, Sq, Skv)
+    if mask.dtype is not torch.bool or norm is None:
+        raise L.LlxError(f"the mask must be bool and broadcast over heads ([B | 1, 1, Sq, Skv]), got {mask.dtype} {tuple(mask.shape)}; "
+                         "per-head masks run on attn_dense_fwd")
+    return norm[:2]
 
 
 def attn_mask_routable(mask: Tensor, B: int, Sq: int, Skv: int) -> bool:
     """Whether attn_mask_fwd takes this mask: bool, broadcast over heads, at least 4 keys (its mask reads are 4 bytes wide)."""
-    return mask.dtype is torch.bool and Skv >= 4 and _mask_4d(mask, B, Sq, Skv) is not None
+    return mask.dtype is torch.bool and Skv >= 4 and _mask_norm(mask, B, Sq, Skv) is not None
 
 
 def attn_mask_flags(mask: Tensor, B: int) -> Tensor:
@@ -753,11 +750,9 @@ def attn_mask_flags(mask: Tensor, B: int) -> Tensor:
     [B, 1, Sq, Skv]: one pass over the mask bytes."""
     L.require_cuda(mask)
     Sq, Skv = mask.shape[-2:]
-    m = _mask_rows(mask, B, Sq, Skv)
-    assert m is not None and mask.dtype is torch.bool, "mask must be bool and broadcast over heads"
+    m, m_sb = _mask_rows(mask, B, Sq, Skv)
     fl = torch.empty(_lib().llx_attn_mask_flags_bytes(B, Sq, Skv), device=mask.device, dtype=torch.uint8)
-    L.check(_lib().llx_attn_mask_tile_flags(L.ptr(m), m.stride(0) if m.shape[0] != 1 else 0, m.stride(1), L.ptr(fl), B, Sq, Skv, L.stream()),
-            "llx_attn_mask_tile_flags")
+    L.check(_lib().llx_attn_mask_tile_flags(L.ptr(m), m_sb, m.stride(2), L.ptr(fl), B, Sq, Skv, L.stream()), "llx_attn_mask_tile_flags")
     return fl
 
 
@@ -767,29 +762,24 @@ def attn_mask_fwd(q: Tensor, k: Tensor, v: Tensor, mask: Tensor, out: Optional[T
     [B,KVH,Skv,128] with any head / position strides (the caches, or views of the q|k|v rows), mask broadcastable to [B,1,Sq,Skv]
     -> o [B,Sq,H*128], the rows `wo` reads; with ``lse=True`` -> (o, lse), lse fp32 [B,H,Sq] in log2 units (what attn_mask_bwd takes).
     The tile classes are computed once per mask tensor (cached on it: every layer of a call shares them).  No host synchronisation."""
-    from . import ops  # (ops imports this module)
-
     _chk_bf16(q, k, v)
     L.require_cuda(mask)
     B, H, Sq, hd = q.shape
     KVH, Skv = k.shape[1], k.shape[2]
-    assert mask.dtype is torch.bool and mask.shape[-2:] == (Sq, Skv) and v.shape == k.shape
+    assert v.shape == k.shape
     for t in (q, k, v):
         assert t.stride(3) == 1
     if q.stride(1) != hd:  # heads must sit side by side in a row
         q = q.transpose(1, 2).contiguous().transpose(1, 2)
-    m = _mask_rows(mask, B, Sq, Skv)
-    if m is None:
-        raise L.LlxError("attn_mask_fwd: the mask must be broadcast over heads ([B | 1, 1, Sq, Skv]); per-head masks run on attn_dense_fwd")
-    fl = ops._cached(mask, f"maskflags{B}", lambda: attn_mask_flags(mask, B))
+    m, m_sb = _mask_rows(mask, B, Sq, Skv)
+    fl = _mask_flags(mask, B)
     if out is None:
         out = torch.empty(B, Sq, H * hd, device=q.device, dtype=BF16)
     assert out.shape == (B, Sq, H * hd) and out.dtype is BF16 and out.stride(2) == 1
     lse_t = torch.empty(B, H, Sq, device=q.device, dtype=torch.float32) if lse else None
     L.check(_lib().llx_attn_mask_fwd(L.ptr(q), q.stride(0), q.stride(2), L.ptr(k), k.stride(0), k.stride(1), k.stride(2), L.ptr(v), v.stride(0),
-                                     v.stride(1), v.stride(2), L.ptr(out), out.stride(0), out.stride(1), L.ptr(lse_t), L.ptr(m),
-                                     m.stride(0) if m.shape[0] != 1 else 0, m.stride(1), L.ptr(fl), B, Sq, Skv, H, KVH, hd, 1.0 / math.sqrt(hd),
-                                     L.stream()), "llx_attn_mask_fwd")
+                                     v.stride(1), v.stride(2), L.ptr(out), out.stride(0), out.stride(1), L.ptr(lse_t), L.ptr(m), m_sb, m.stride(2),
+                                     L.ptr(fl), B, Sq, Skv, H, KVH, hd, 1.0 / math.sqrt(hd), L.stream()), "llx_attn_mask_fwd")
     return (out, lse_t) if lse else out
 
 
@@ -799,29 +789,13 @@ def attn_mask_bwd(q: Tensor, k: Tensor, v: Tensor, o: Tensor, do: Tensor, lse: T
     batch / sequence strides free: views of fused q|k|v rows work), lse [B,H,S] from attn_mask_fwd(..., lse=True), mask bool
     broadcastable to [B,1,S,S].  rope as in attn_bwd.  A key that no row attends to gets exact zeros in dk / dv.  The tile classes are
     the ones attn_mask_fwd cached on the mask tensor.  No host synchronisation."""
-    from . import ops  # (ops imports this module)
-
-    _chk_bf16(q, k, v, o, do, dq, dk, dv)
     L.require_cuda(mask)
-    if rope is not None:
-        assert rope.dtype is torch.float32 and rope.is_contiguous() and rope.shape[0] >= q.shape[1] and rope.shape[1:] == (64, 2)
-    B, S, H, hd = q.shape
-    KVH = k.shape[2]
-    for t in (q, k, v, o, do, dq, dk, dv):
-        assert t.stride(3) == 1 and t.stride(2) == hd
-    assert mask.dtype is torch.bool and mask.shape[-2:] == (S, S) and lse.shape == (B, H, S) and lse.dtype is torch.float32 and lse.is_contiguous()
-    m = _mask_rows(mask, B, S, S)
-    if m is None:
-        raise L.LlxError("attn_mask_bwd: the mask must be broadcast over heads ([B | 1, 1, S, S])")
-    fl = ops._cached(mask, f"maskflags{B}", lambda: attn_mask_flags(mask, B))
-    delta = torch.empty(_lib().llx_attn_bwd_workspace_bytes(B, S, H, KVH) // 4, device=q.device, dtype=torch.float32)  # delta + dK/dV partials
+    B, S, H = q.shape[:3]
+    m, m_sb = _mask_rows(mask, B, S, S)
+    fl = _mask_flags(mask, B)
+    lead, trail, ws = _attn_bwd_operands(q, k, v, o, do, lse, dq, dk, dv, rope)
     ev = _trace_begin(ATTN_TRACE)
-    L.check(_lib().llx_attn_mask_bwd(L.ptr(q), q.stride(0), q.stride(1), L.ptr(k), k.stride(0), k.stride(1), L.ptr(v), v.stride(0), v.stride(1),
-                                     L.ptr(o), o.stride(0), o.stride(1), L.ptr(do), do.stride(0), do.stride(1), L.ptr(lse), L.ptr(delta),
-                                     L.ptr(dq), dq.stride(0), dq.stride(1), L.ptr(dk), dk.stride(0), dk.stride(1), L.ptr(dv), dv.stride(0),
-                                     dv.stride(1), L.ptr(m), m.stride(0) if m.shape[0] != 1 else 0, m.stride(1), L.ptr(fl), L.ptr(rope),
-                                     B, S, H, KVH, hd, 1.0 / math.sqrt(hd), L.stream()),
-            "llx_attn_mask_bwd")
+    L.check(_lib().llx_attn_mask_bwd(*lead, L.ptr(m), m_sb, m.stride(2), L.ptr(fl), L.ptr(rope), *trail), "llx_attn_mask_bwd")
     _trace_end(ATTN_TRACE, ev, "bwd", B, S, H)
 
 
@@ -987,14 +961,9 @@ def attn_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, mask: Tensor, exten
     L.require_cuda(mask)
     B, H, M, hd = q.shape
     KVH, Skv = k_cache.shape[1], k_cache.shape[2]
-    assert mask.dtype is torch.bool and mask.shape[-2:] == (M, Skv) and k_cache.stride() == v_cache.stride()
-    m = mask
-    while m.dim() < 4:
-        m = m.unsqueeze(0)
-    if m.stride(3) != 1:
-        m = m.contiguous()
-    m_sb = m.stride(0) if m.shape[0] != 1 else 0
-    m_sh = m.stride(1) if m.shape[1] != 1 else 0
+    norm = _mask_norm(mask, B, M, Skv, H)
+    assert mask.dtype is torch.bool and norm is not None and k_cache.stride() == v_cache.stride()
+    m, m_sb, m_sh = norm
     nsplit = max(1, min(-(-Skv // 32), -(-_DECODE_WGS // (B * KVH)), 128))  # workgroups = nsplit * B * KVH: two or more per CU keep more rows in flight
     nbytes = _lib().llx_attn_decode_workspace_bytes(B, H, M, nsplit)
     ws = _workspace(_DECODE_WS, q.device, nbytes)

@@ -39,17 +39,13 @@ def _launch(A: Tensor, Bt: Tensor, a_scale: Tensor, b_scale: Tensor, out: Tensor
             b2: Tensor | None = None, epilogue: int = 0, e: Tensor | None = None, rope: tuple | None = None) -> Tensor:
     from llx import kernels as K
 
-    if K.GEMM_TRACE is None:
-        return _launch_impl(A, Bt, a_scale, b_scale, out, a2, b2, epilogue, e, rope)
-    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-    ev[0].record()
+    ev = K._trace_begin(K.GEMM_TRACE)
     res = _launch_impl(A, Bt, a_scale, b_scale, out, a2, b2, epilogue, e, rope)
-    ev[1].record()
-    M, Kd = A.shape
-    N = Bt.shape[0]
-    # algorithmic work of the i8 kernel: the int8 product only (the bf16 LoRA extension riding in the same launch is not counted)
-    K.GEMM_TRACE.append((ev[0], ev[1], 2.0 * M * N * Kd, 1.0 * (M * Kd + N * Kd) + 2.0 * M * N * (2 if epilogue == 1 else 1), "i8",
-                         K.gemm_kernel_launches(M, N, epilogue)))
+    if ev is not None:
+        (M, Kd), N = A.shape, Bt.shape[0]
+        # algorithmic work of the i8 kernel: the int8 product only (the bf16 LoRA extension riding in the same launch is not counted)
+        K._trace_end(K.GEMM_TRACE, ev, 2.0 * M * N * Kd, 1.0 * (M * Kd + N * Kd) + 2.0 * M * N * (2 if epilogue == 1 else 1), "i8",
+                     K.gemm_kernel_launches(M, N, epilogue))
     return res
 
 

@@ -431,3 +431,77 @@ def test_cached_is_keyed_by_version_and_device_of_every_source():
     assert _cached_multi([a, b], "cat", build("ab")) == "ab" and _cached_multi([a, b], "cat", build("ab2")) == "ab" and len(calls) == n + 1
     b.mul_(2)
     assert _cached_multi([a, b], "cat", build("ab3")) == "ab3" and _cached_multi([a, b], "cat", build("ab4")) == "ab3"
+
+
+# ---------------------------------------------------------------------------------------------- the attention mask normaliser
+def _mask_forms(B, H, Sq, Skv):
+    """name -> (mask, H argument, shape, (m_sb, m_sh), copied): every form the attention wrappers are handed."""
+    g = torch.Generator().manual_seed(5)
+    r = lambda *shape: torch.rand(*shape, generator=g) < 0.5
+    m2, mb, mbh = r(Sq, Skv), r(B, Sq, Skv), r(B, H, Sq, Skv)
+    wide = r(Sq, Skv + 3)
+    flat = r(Skv + 2 * Sq)
+    return {
+        "[Sq,Skv]": (m2, None, (1, 1, Sq, Skv), (0, 0), False),
+        "[1,Sq,Skv]": (m2[None], None, (1, 1, Sq, Skv), (0, 0), False),
+        "[B,Sq,Skv]": (mb, None, (1, B, Sq, Skv), None, False),  # 3-d is [H | 1, Sq, Skv] to SDPA's broadcast: B must equal 1 or H
+        "[1,1,Sq,Skv]": (m2[None, None], None, (1, 1, Sq, Skv), (0, 0), False),
+        "[B,1,Sq,Skv]": (mb[:, None], None, (B, 1, Sq, Skv), (Sq * Skv, 0), False),
+        "[B,H,Sq,Skv] per head": (mbh, H, (B, H, Sq, Skv), (H * Sq * Skv, Sq * Skv), False),
+        "[1,H,Sq,Skv] per head": (mbh[:1], H, (1, H, Sq, Skv), (0, Sq * Skv), False),
+        "[H,Sq,Skv] per head": (mbh[0], H, (1, H, Sq, Skv), (0, Sq * Skv), False),  # 3-d reads as [H | 1, Sq, Skv], as SDPA broadcasts it
+        "[H,Sq,Skv] without H": (mbh[0], None, (1, H, Sq, Skv), None, False),
+        "expanded batch": (m2[None, None].expand(B, 1, Sq, Skv), None, (B, 1, Sq, Skv), (0, 0), False),
+        "row stride > Skv": (wide[:, :Skv], None, (1, 1, Sq, Skv), (0, 0), False),
+        "transposed last dim": (r(Skv, Sq).t(), None, (1, 1, Sq, Skv), (0, 0), True),
+        "transposed last dim per head": (r(B, H, Skv, Sq).transpose(2, 3), H, (B, H, Sq, Skv), (H * Sq * Skv, Sq * Skv), True),
+        "overlapping rows": (flat.as_strided((Sq, Skv), (2, 1)), None, (1, 1, Sq, Skv), (0, 0), True),
+        "overlapping rows per head": (flat.as_strided((Sq, Skv), (2, 1)), H, (1, 1, Sq, Skv), (0, 0), False),  # the row-wise kernels take them
+    }
+
+
+def test_mask_normaliser_forms_strides_and_copies():
+    from llx import kernels as K
+
+    B, H, Sq, Skv = 3, 4, 5, 9
+    for name, (mask, h, shape, strides, copied) in _mask_forms(B, H, Sq, Skv).items():
+        got = K._mask_norm(mask, B, Sq, Skv, h)
+        if strides is None:
+            assert got is None, name
+            continue
+        m, m_sb, m_sh = got
+        assert tuple(m.shape) == shape and m.stride(3) == 1, name
+        assert (m_sb, m_sh) == strides, (name, m_sb, m_sh)
+        assert (m.data_ptr() != mask.data_ptr()) == copied, name
+        if h is None:
+            assert m.stride(2) >= Skv, name
+        assert torch.equal(m.expand(B, H, Sq, Skv), mask.expand(B, H, Sq, Skv)), name
+        # the addresses the kernels form from the strides see the same values
+        flat = torch.as_strided(m, (B, H, Sq, Skv), (m_sb, m_sh, m.stride(2), 1))
+        assert torch.equal(flat, mask.expand(B, H, Sq, Skv)), name
+
+
+def test_mask_normaliser_rejections():
+    from llx import kernels as K
+    from llx._lib import LlxError
+
+    B, H, Sq, Skv = 3, 4, 5, 9
+    ok = torch.ones(Sq, Skv, dtype=torch.bool)
+    for bad in (torch.ones(Sq, Skv + 1, dtype=torch.bool), torch.ones(Sq + 1, Skv, dtype=torch.bool), torch.ones(Skv, Sq, dtype=torch.bool),
+                torch.ones(2, 1, Sq, Skv, dtype=torch.bool), torch.ones(B + 1, 1, Sq, Skv, dtype=torch.bool),
+                torch.ones(1, 1, 1, Sq, Skv, dtype=torch.bool)):
+        assert K._mask_norm(bad, B, Sq, Skv) is None and K._mask_norm(bad, B, Sq, Skv, H) is None, tuple(bad.shape)
+        assert not K.attn_mask_routable(bad, B, Sq, Skv)
+        with pytest.raises(LlxError, match="broadcast over heads"):
+            K._mask_rows(bad, B, Sq, Skv)
+    per_head = torch.ones(B, H, Sq, Skv, dtype=torch.bool)
+    assert K._mask_norm(per_head, B, Sq, Skv) is None and K._mask_norm(per_head, B, Sq, Skv, H) is not None
+    assert K._mask_norm(torch.ones(B, 2, Sq, Skv, dtype=torch.bool), B, Sq, Skv, H) is None  # heads not in (1, H)
+    assert not K.attn_mask_routable(per_head, B, Sq, Skv) and K.attn_mask_routable(ok, B, Sq, Skv)
+    assert not K.attn_mask_routable(ok.to(torch.uint8), B, Sq, Skv) and not K.attn_mask_routable(ok[:, :3], B, Sq, 3)  # bool, Skv >= 4
+    with pytest.raises(LlxError, match="bool"):
+        K._mask_rows(ok.to(torch.uint8), B, Sq, Skv)
+    with pytest.raises(LlxError, match="does not fit"):
+        K.MaskSpec(dense=torch.ones(2, 8, 8, dtype=torch.bool)).prepared(B, 8, "cpu")
+    with pytest.raises(LlxError, match="does not fit"):
+        K.MaskSpec(dense=torch.ones(8, 8, dtype=torch.bool)).prepared(B, 16, "cpu")
