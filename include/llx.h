@@ -128,6 +128,27 @@ int llx_attn_bwd(const void* q, int64_t q_sb, int64_t q_ss, const void* k, int64
                              (S, dP, dV, dK, dQ) is computed once; without it the dQ kernel recomputes S and dP */,
                  int64_t B, int64_t S, int64_t H, int64_t KVH, int64_t head_dim, float scale, llx_stream_t s);
 
+/* ---- attention dropout in training: F.scaled_dot_product_attention(..., dropout_p) at modelling/llama.py:135-137.  The two entries
+ *      above with three more operands in front of the stream: threshold = t = round(p * 65536), 0 < t < 65536 (an element is dropped with
+ *      probability t / 65536, a kept one is scaled by 65536 / (65536 - t)); rng = device pointer to two int64 (seed, counter), read by
+ *      the kernels - the backward must see the values the forward saw, so callers hand both a per-step copy (the ticket) of their live
+ *      state; stream_id = one value per attention module.  keep(b, h, q, k) is a counter-based integer hash of (seed, counter, stream_id,
+ *      b, h, q, k) (csrc/attn_dropout.h), independent per QUERY head.  The softmax statistics and lse are those of the undropped rows;
+ *      O = sum_k (P keep c) V, dV = (P keep c)^T dO, dP = keep c (dO V^T), dS = P (dP - delta).  llx_attn_bwd_dropout takes ds = null
+ *      only (the dS scratch route has no dropout build).  llx_attn_dropout_keep writes the keep bytes [B, H, Sq, Skv] (1 = kept). ---- */
+int llx_attn_fwd_dropout(const void* q, int64_t q_sb, int64_t q_ss, const void* k, int64_t k_sb, int64_t k_ss, const void* v, int64_t v_sb,
+                         int64_t v_ss, void* o, int64_t o_sb, int64_t o_ss, float* lse, const int* doc_ids, const int* prefix_len,
+                         const void* flags, int64_t B, int64_t S, int64_t H, int64_t KVH, int64_t head_dim, float scale, int64_t threshold,
+                         const void* rng, int64_t stream_id, llx_stream_t s);
+int llx_attn_bwd_dropout(const void* q, int64_t q_sb, int64_t q_ss, const void* k, int64_t k_sb, int64_t k_ss, const void* v, int64_t v_sb,
+                         int64_t v_ss, const void* o, int64_t o_sb, int64_t o_ss, const void* d_o, int64_t do_sb, int64_t do_ss,
+                         const float* lse, float* delta, void* dq, int64_t dq_sb, int64_t dq_ss, void* dk, int64_t dk_sb, int64_t dk_ss,
+                         void* dv, int64_t dv_sb, int64_t dv_ss, const int* doc_ids, const int* prefix_len, const void* flags,
+                         const float* rope, void* ds, int64_t B, int64_t S, int64_t H, int64_t KVH, int64_t head_dim, float scale,
+                         int64_t threshold, const void* rng, int64_t stream_id, llx_stream_t s);
+int llx_attn_dropout_keep(void* keep, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t threshold, const void* rng, int64_t stream_id,
+                          llx_stream_t s);
+
 /* ---- dense-mask attention forward (inference / KV-cache path): SDPA(q,k,v,mask,is_causal=False,enable_gqa=True) at
  *      modelling/llama.py:126-127,135-137 with mask = causal_mask[None,None,input_pos] (:194,:205).  q [B,H,Sq,128],
  *      k/v [B,KVH,Skv,128] (e.g. the KVCache buffers :79-81), mask bool with broadcast strides; forward only. ------- */

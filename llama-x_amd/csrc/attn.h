@@ -17,6 +17,8 @@ static inline int attn_check_shape(const char* fn, int64_t B, int64_t S, int64_t
   LLX_REQUIRE(B > 0 && S > 0 && H > 0 && KVH > 0 && H % KVH == 0, "%s: bad B/S/H/KVH", fn);
   return LLX_OK;
 }
+// the dropout entries' own operands (attn_fwd.hip): threshold = round(p * 65536), rng = device (seed, counter), stream_id per module
+int attn_dropout_check(const char* fn, int64_t threshold, const void* rng, int64_t stream_id, int64_t B, int64_t H);
 // raises the dynamic-LDS limit of every listed kernel to `bytes`; the first failure is returned
 template <typename... K>
 static inline hipError_t attn_lds_limit(int bytes, K... kernels) {

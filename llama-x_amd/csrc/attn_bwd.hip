@@ -29,6 +29,7 @@
 //               dK^T += Q^T.dS with P/dS from the accumulator registers and Q^T/dO^T by transposed LDS reads.
 // LDS images read both by rows and transposed use the dual-use swizzle  slot = chunk ^ (((row&3)<<2) | ((row>>2)&3)).
 #include "attn.h"
+#include "attn_dropout.h"
 
 typedef __attribute__((ext_vector_type(8))) short s16x8_t;
 
@@ -87,6 +88,9 @@ struct AttnBwdArgs {
   // dense-mask mode only (llx_attn_mask_bwd): [B | 1, S, S] bool / uint8, last dim dense, nonzero = attend; strides in bytes
   // (m_sb = 0: broadcast over the batch); flags are then those of llx_attn_mask_tile_flags with Sq = Skv = S
   const uint8_t* mask; int64_t m_sb, m_sq;
+  // attention dropout only (llx_attn_bwd_dropout; attn_dropout.h): the forward's ticket (seed, counter) on the device, t << 16,
+  // 65536 / (65536 - t), the module's stream id.  dV takes P o keep * c, dP = keep * c o (dO V^T), dS = P o (dP - delta) with the undropped P.
+  const int64_t* rng; uint32_t drop_thr; float drop_c; int stream_id;
 };
 
 // Where the tile schedule and the predicate of a partly masked (class-1) tile come from:
@@ -108,8 +112,9 @@ __device__ __forceinline__ uint32_t mask_nibble(uint32_t w) {
 #define DQ_STAGE_BYTES (2 * TILE_BYTES)
 #define DQ_LDS_BYTES (2 * DQ_STAGE_BYTES)
 
-template <int MODE>
+template <int MODE, bool DROPOUT = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnBwdArgs a) {
+  static_assert(!(DROPOUT && MODE == BWD_MASK), "dropout exists in the causal and the rule mode");
   constexpr bool GENERAL = MODE == BWD_RULE;   // doc_ids / prefix_len
   constexpr bool FLAGS = MODE != BWD_CAUSAL;   // tile classes come from flags
   constexpr bool MASK = MODE == BWD_MASK;
@@ -161,10 +166,26 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnBwdArgs a
     if (t * BKV + BKV <= a.S) {
       const char* kt = (const char*)(kbase + (int64_t)t * BKV * a.k_ss);
       const char* vt = (const char*)(vbase + (int64_t)t * BKV * a.v_ss);
+      if constexpr (DROPOUT) {
+        // (the dropout builds have no registers for the eight loop-invariant offsets: kept across the tile loop they go to scratch and
+        // are reloaded in front of every tile's LDS-DMA; rebuilt per call from a fresh lane id they cost a few vector instructions)
+        uint32_t l0;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l0));
+        const int slot = (int)(l0 & 15);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int row = i * 16 + wave * 4 + (int)(l0 >> 4);
+          const uint32_t ko = (uint32_t)(((int64_t)row * a.k_ss + (slot ^ dual_swz(row)) * 8) * 2);
+          const uint32_t vo = (uint32_t)(((int64_t)row * a.v_ss + (slot ^ (row & 15)) * 8) * 2);
+          __builtin_amdgcn_global_load_lds((gbl_void*)(kt + ko), (lds_void*)(sK + (i * 16 + wave * 4) * 256), 16, 0, 0);
+          __builtin_amdgcn_global_load_lds((gbl_void*)(vt + vo), (lds_void*)(sV + (i * 16 + wave * 4) * 256), 16, 0, 0);
+        }
+      } else {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         __builtin_amdgcn_global_load_lds((gbl_void*)(kt + koff[i]), (lds_void*)(sK + (i * 16 + wave * 4) * 256), 16, 0, 0);
         __builtin_amdgcn_global_load_lds((gbl_void*)(vt + voff[i]), (lds_void*)(sV + (i * 16 + wave * 4) * 256), 16, 0, 0);
+      }
       }
     } else {
 #pragma unroll
@@ -290,6 +311,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnBwdArgs a
   // (document masks: the tile's 64 key ids in one register - lane i holds key 64 t + i - requested one tile ahead and gathered by
   // ds_bpermute, as in the forward kernel)
   int docv = (GENERAL && docrow && t < kt_end) ? docrow[min(t * BKV + lane, a.S - 1)] : 0, docv_next = 0;
+  AttnDropKey dkey = {0u, 0u};
+  if constexpr (DROPOUT) dkey = attn_dropout_key(a.rng[0], a.rng[1], a.stream_id, b, h);
   while (t < kt_end) {
     int cls_m = 0;
     uint32_t mbits = 0;
@@ -342,7 +365,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnBwdArgs a
       }
       // dS^T = P^T * (dP^T - delta)
 #pragma unroll
-      for (int e = 0; e < 16; ++e) st[e] = st[e] * (dp[e] - my_delta);
+      for (int e = 0; e < 16; ++e) {
+        float dpe = dp[e];
+        if constexpr (DROPOUT) {  // dP^T = keep * c o (V.dO^T); the P in front stays the undropped one
+          const int kk = t * BKV + kb * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+          dpe = attn_drop_keep(attn_drop_row(dkey, qi), attn_drop_col(dkey, kk), a.drop_thr) ? dpe * a.drop_c : 0.f;
+        }
+        st[e] = st[e] * (dpe - my_delta);
+      }
       // dQ^T += K^T . dS^T: K^T fragments by transposed reads issued as inline asm (common.h: lds_tr_read - through the builtin hipcc
       // drains the next tile's LDS-DMA right here); the 8 reads of the second 16-key step fly under the MFMAs of the first
       {
@@ -428,8 +458,9 @@ typedef __attribute__((address_space(3))) bf16x8_t lds_bf16x8;
 typedef __attribute__((address_space(3))) f32x4_t lds_f32x4;
 #define DKV3_LDS_BYTES (0x10000 + 1024)
 
-template <int MODE, bool STAMP = false, bool DS = false>
+template <int MODE, bool STAMP = false, bool DS = false, bool DROPOUT = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv3_kernel(const AttnBwdArgs a, float* __restrict__ part) {
+  static_assert(!(DROPOUT && (MODE == BWD_MASK || STAMP || DS)), "dropout exists on the default route, in the causal and the rule mode");
   constexpr bool GENERAL = MODE == BWD_RULE;   // doc_ids / prefix_len
   constexpr bool FLAGS = MODE != BWD_CAUSAL;   // tile classes come from flags
   constexpr bool MASK = MODE == BWD_MASK;
@@ -613,6 +644,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv3_kernel(const AttnBwdArgs
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   int cur = 0;
+  AttnDropKey dkey = {0u, 0u};
+  if constexpr (DROPOUT) dkey = attn_dropout_key(a.rng[0], a.rng[1], a.stream_id, b, h);
   int nst = 0;
   auto stamp = [&]() {
     if constexpr (STAMP) {
@@ -714,9 +747,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv3_kernel(const AttnBwdArgs
         }
         if (qb32 == 0) stamp();  // 4: dP chain
         // first transposed fragments of the second phase fly under the dS arithmetic
+        // (the dropout builds request them behind the pack: the hash words need these eight registers while P and dP are both live)
         s16x4_t tdl[2], tdh[2], tql[2], tqh[2];
-        trf(qb32, 1, 0, tdl[0], tdh[0]);
-        trf(qb32, 0, 0, tql[0], tqh[0]);
+        if constexpr (!DROPOUT) {
+          trf(qb32, 1, 0, tdl[0], tdh[0]);
+          trf(qb32, 0, 0, tql[0], tqh[0]);
+        }
         // dS = P (dP - delta); P and dS are packed to bf16 for BOTH 16-row k-steps before the second phase starts, so that
         // phase holds 16 operand registers instead of the 32 fp32 ones (the register peak of this kernel)
         bf16x8_t pb[2], dsb[2];
@@ -726,8 +762,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv3_kernel(const AttnBwdArgs
 #pragma unroll
           for (int e2 = 0; e2 < 4; ++e2) {
             const int e = 4 * g4 + e2;
+            if constexpr (DROPOUT) {  // one keep decision per element serves both: dV takes P o keep * c, dS the undropped P
+              const int qi = qt * DKV_QT + qb32 * 32 + 8 * g4 + 4 * hh + e2;
+              const bool keep = attn_drop_keep(attn_drop_row(dkey, qi), attn_drop_col(dkey, key), a.drop_thr);
+              pb[e >> 3][e & 7] = (__bf16)(keep ? st[e] * a.drop_c : 0.f);
+              dsb[e >> 3][e & 7] = (__bf16)(st[e] * ((keep ? dp[e] * a.drop_c : 0.f) - d4[e2]));
+            } else {
             pb[e >> 3][e & 7] = (__bf16)st[e];
             dsb[e >> 3][e & 7] = (__bf16)(st[e] * (dp[e] - d4[e2]));
+            }
           }
         }
         if constexpr (DS) {
@@ -743,6 +786,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv3_kernel(const AttnBwdArgs
             const int piece = ((((wave & 1) * 2 + (qt & 1)) * 2 + qb32) * 2 + s2) * 64;  // 64 chunks = 1 KiB per store instruction
             *reinterpret_cast<u32x4_t*>(dtile + (piece + (int)ln) * 8) = u32x4_t{r0[0], r1[0], r0[1], r1[1]};
           }
+        }
+        if constexpr (DROPOUT) {
+          __builtin_amdgcn_sched_barrier(0);
+          trf(qb32, 1, 0, tdl[0], tdh[0]);
+          trf(qb32, 0, 0, tql[0], tqh[0]);
         }
         __builtin_amdgcn_sched_barrier(0);
         if (qb32 == 0) stamp();  // 5: dS + pack
@@ -1096,11 +1144,13 @@ extern "C" int64_t llx_attn_bwd_ds_bytes(int64_t B, int64_t S, int64_t H) {
 }
 
 static int attn_bwd_set_attrs() {  // (each static is initialised once, by one thread)
-  static const hipError_t e0 = attn_lds_limit(DQ_LDS_BYTES, attn_bwd_dq_kernel<BWD_CAUSAL>, attn_bwd_dq_kernel<BWD_RULE>, attn_bwd_dq_kernel<BWD_MASK>);
+  static const hipError_t e0 = attn_lds_limit(DQ_LDS_BYTES, attn_bwd_dq_kernel<BWD_CAUSAL>, attn_bwd_dq_kernel<BWD_RULE>, attn_bwd_dq_kernel<BWD_MASK>,
+                                              attn_bwd_dq_kernel<BWD_CAUSAL, true>, attn_bwd_dq_kernel<BWD_RULE, true>);
   static const hipError_t e1 = attn_lds_limit(DQ2_LDS_BYTES, attn_bwd_dq2_kernel<false>, attn_bwd_dq2_kernel<true>);
   static const hipError_t e2 = attn_lds_limit(DKV3_LDS_BYTES, attn_bwd_dkv3_kernel<BWD_CAUSAL, false, false>, attn_bwd_dkv3_kernel<BWD_RULE, false, false>,
                                               attn_bwd_dkv3_kernel<BWD_MASK, false, false>, attn_bwd_dkv3_kernel<BWD_CAUSAL, true, false>,
-                                              attn_bwd_dkv3_kernel<BWD_CAUSAL, false, true>, attn_bwd_dkv3_kernel<BWD_RULE, false, true>);
+                                              attn_bwd_dkv3_kernel<BWD_CAUSAL, false, true>, attn_bwd_dkv3_kernel<BWD_RULE, false, true>,
+                                              attn_bwd_dkv3_kernel<BWD_CAUSAL, false, false, true>, attn_bwd_dkv3_kernel<BWD_RULE, false, false, true>);
   return e0 == hipSuccess && e1 == hipSuccess && e2 == hipSuccess ? LLX_OK : LLX_ERR_LAUNCH;
 }
 
@@ -1140,11 +1190,15 @@ static int attn_bwd_dkv(const char* fn, void (*kernel)(const AttnBwdArgs, float*
   return LLX_OK;
 }
 
-// Route (b) in one of the modes BWD_*: dQ, dK/dV partials, reduce.  With a.stamps (BWD_CAUSAL only) the dK/dV kernel is its stamping build.
+// Route (b) in one of the modes BWD_*: dQ, dK/dV partials, reduce.  With a.stamps (BWD_CAUSAL only) the dK/dV kernel is its stamping build;
+// with a.rng (BWD_CAUSAL, BWD_RULE) both kernels are their dropout builds.
 static int attn_bwd_run(const char* fn, const AttnBwdArgs& a, int mode, hipStream_t stream) {
-  void (*const dq[3])(const AttnBwdArgs) = {attn_bwd_dq_kernel<BWD_CAUSAL>, attn_bwd_dq_kernel<BWD_RULE>, attn_bwd_dq_kernel<BWD_MASK>};
-  void (*const dkv[3])(const AttnBwdArgs, float*) = {attn_bwd_dkv3_kernel<BWD_CAUSAL, false, false>, attn_bwd_dkv3_kernel<BWD_RULE, false, false>,
-                                                     attn_bwd_dkv3_kernel<BWD_MASK, false, false>};
+  void (*const dq[5])(const AttnBwdArgs) = {attn_bwd_dq_kernel<BWD_CAUSAL>, attn_bwd_dq_kernel<BWD_RULE>, attn_bwd_dq_kernel<BWD_MASK>,
+                                            attn_bwd_dq_kernel<BWD_CAUSAL, true>, attn_bwd_dq_kernel<BWD_RULE, true>};
+  void (*const dkv[5])(const AttnBwdArgs, float*) = {attn_bwd_dkv3_kernel<BWD_CAUSAL, false, false>, attn_bwd_dkv3_kernel<BWD_RULE, false, false>,
+                                                     attn_bwd_dkv3_kernel<BWD_MASK, false, false>, attn_bwd_dkv3_kernel<BWD_CAUSAL, false, false, true>,
+                                                     attn_bwd_dkv3_kernel<BWD_RULE, false, false, true>};
+  if (a.rng) mode += 3;  // (the dropout entry passes BWD_CAUSAL or BWD_RULE and no stamps)
   if (attn_bwd_set_attrs() != LLX_OK) { llx_set_error("%s: cannot raise LDS limit", fn); return LLX_ERR_LAUNCH; }
   // dQ first: it also publishes delta = rowsum(dO . O) and the sanitised -lse that the dK/dV kernel stages from global memory
   hipLaunchKernelGGL(dq[mode], dim3((unsigned)a.H, (unsigned)cdiv64(a.S, BQ), (unsigned)a.B), dim3(256), DQ_LDS_BYTES, stream, a);
@@ -1208,4 +1262,25 @@ extern "C" int llx_attn_mask_bwd(const void* q, int64_t q_sb, int64_t q_ss, cons
   LLX_REQUIRE(m_sq >= S && m_sb >= 0, "llx_attn_mask_bwd: mask rows overlap");
   a.flags = (const uint8_t*)flags; a.mask = (const uint8_t*)mask; a.m_sb = m_sb; a.m_sq = m_sq;
   return attn_bwd_run("llx_attn_mask_bwd", a, BWD_MASK, stream);
+}
+
+// llx_attn_bwd with attention dropout: the backward of llx_attn_fwd_dropout.  The same operands as llx_attn_bwd (ds must be null: the dS
+// scratch route has no dropout build), then threshold / rng / stream_id exactly as the forward was given them - rng must still hold the
+// forward's (seed, counter): callers keep a copy per step (the ticket) instead of pointing both at a live counter.
+extern "C" int llx_attn_bwd_dropout(const void* q, int64_t q_sb, int64_t q_ss, const void* k, int64_t k_sb, int64_t k_ss, const void* v,
+                                    int64_t v_sb, int64_t v_ss, const void* o, int64_t o_sb, int64_t o_ss, const void* d_o, int64_t do_sb,
+                                    int64_t do_ss, const float* lse, float* delta, void* dq, int64_t dq_sb, int64_t dq_ss, void* dk,
+                                    int64_t dk_sb, int64_t dk_ss, void* dv, int64_t dv_sb, int64_t dv_ss, const int* doc_ids,
+                                    const int* prefix_len, const void* flags, const float* rope, void* ds, int64_t B, int64_t S, int64_t H,
+                                    int64_t KVH, int64_t head_dim, float scale, int64_t threshold, const void* rng, int64_t stream_id,
+                                    hipStream_t stream) {
+  AttnBwdArgs a;
+  if (int rc = attn_bwd_args("llx_attn_bwd_dropout", a, q, q_sb, q_ss, k, k_sb, k_ss, v, v_sb, v_ss, o, o_sb, o_ss, d_o, do_sb, do_ss, lse, delta, dq, dq_sb,
+                             dq_ss, dk, dk_sb, dk_ss, dv, dv_sb, dv_ss, rope, B, S, H, KVH, head_dim, scale)) return rc;
+  if (int rc = attn_dropout_check("llx_attn_bwd_dropout", threshold, rng, stream_id, B, H)) return rc;
+  LLX_REQUIRE(!(doc_ids || prefix_len) || flags, "llx_attn_bwd_dropout: tile flags required with doc_ids/prefix_len");
+  LLX_REQUIRE(!ds, "llx_attn_bwd_dropout: the dS scratch route has no dropout build (pass ds = null)");
+  a.doc_ids = doc_ids; a.prefix_len = prefix_len; a.flags = (doc_ids || prefix_len) ? (const uint8_t*)flags : nullptr;
+  a.rng = (const int64_t*)rng; a.drop_thr = (uint32_t)threshold << 16; a.drop_c = 65536.f / (float)(65536 - threshold); a.stream_id = (int)stream_id;
+  return attn_bwd_run("llx_attn_bwd_dropout", a, a.flags ? BWD_RULE : BWD_CAUSAL, stream);
 }

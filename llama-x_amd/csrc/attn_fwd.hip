@@ -15,6 +15,7 @@
 //                   come from the row-major LDS tile through ds_read_b64_tr_b16)
 // K/V tiles are double-buffered in LDS by global_load_lds with the bank swizzle applied on the source address.
 #include "attn.h"
+#include "attn_dropout.h"
 
 #define KV_TILE_BYTES TILE_BYTES
 #define ATT_STAGE_BYTES (2 * KV_TILE_BYTES)  // K + V
@@ -34,6 +35,11 @@ struct AttnFwdArgs {
   int64_t k_sh, v_sh;     // element stride between kv heads ([B,KVH,Smax,128] cache, or 128 for views of a q|k|v row buffer)
   const uint8_t* mask;    // [B | 1, Sq, Skv] bool / uint8, last dim dense; nonzero = attend
   int64_t m_sb, m_sq;     // mask strides in bytes (m_sb = 0: broadcast over the batch)
+  // attention dropout only (attn_fwd_dropout_kernel; attn_dropout.h):
+  const int64_t* rng;     // device: (seed, counter) - the ticket of this training step
+  uint32_t drop_thr;      // t << 16, t = round(p * 65536): an element is dropped iff the top 16 bits of its word are below t
+  float drop_c;           // 65536 / (65536 - t)
+  int stream_id;          // one value per attention module
 };
 
 enum { ATT_CAUSAL = 0, ATT_GENERAL = 1, ATT_MASK = 2 };
@@ -49,13 +55,23 @@ template <bool GENERAL_, bool STAMP = false, int NW = 8>
 __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_kernel(const AttnFwdArgs a) {
   static_assert(NW == 8, "NW stays a parameter only because bench.py, tools/ and profiles/ key on the symbol attn_fwd_kernel<*, *, 8>");
   constexpr int MODE = GENERAL_ ? ATT_GENERAL : ATT_CAUSAL;
+  constexpr bool DROPOUT = false;
+#include "attn_fwd_body.h"
+}
+
+// Training with attention dropout (llx_attn_fwd_dropout): the DROPOUT build of the same body, causal and rule mode.  A kernel of its
+// own and not a fourth template argument of attn_fwd_kernel: that would rename the measured instances (see the static_assert above).
+template <bool GENERAL_>
+__global__ __launch_bounds__(512, 2) void attn_fwd_dropout_kernel(const AttnFwdArgs a) {
+  constexpr int MODE = GENERAL_ ? ATT_GENERAL : ATT_CAUSAL, NW = 8;
+  constexpr bool STAMP = false, DROPOUT = true;
 #include "attn_fwd_body.h"
 }
 
 // KV-cache prefill / explicit bool mask (llx_attn_mask_fwd): the same tile loop, driven by the mask bytes.
 __global__ __launch_bounds__(512, 2) void attn_mask_fwd_kernel(const AttnFwdArgs a) {
   constexpr int MODE = ATT_MASK, NW = 8;
-  constexpr bool STAMP = false;
+  constexpr bool STAMP = false, DROPOUT = false;
 #include "attn_fwd_body.h"
 }
 
@@ -112,7 +128,8 @@ static int attn_fwd_args(const char* fn, AttnFwdArgs& a, const void* q, int64_t 
 // Any forward instance: 8 waves per 256 query rows of a (head, batch).  The static is initialised once, by one thread (checkpointing enters from several).
 static int attn_fwd_launch(const char* fn, void (*kernel)(const AttnFwdArgs), const AttnFwdArgs& a, hipStream_t stream) {
   static const hipError_t err = attn_lds_limit(ATT_LDS_BYTES, attn_fwd_kernel<false, false, 8>, attn_fwd_kernel<true, false, 8>,
-                                               attn_fwd_kernel<false, true, 8>, attn_mask_fwd_kernel);
+                                               attn_fwd_kernel<false, true, 8>, attn_mask_fwd_kernel, attn_fwd_dropout_kernel<false>,
+                                               attn_fwd_dropout_kernel<true>);
   if (err != hipSuccess) { llx_set_error("%s: %s", fn, hipGetErrorString(err)); return LLX_ERR_LAUNCH; }
   hipLaunchKernelGGL(kernel, dim3((unsigned)a.H, (unsigned)cdiv64(a.S, 256), (unsigned)a.B), dim3(512), ATT_LDS_BYTES, stream, a);
   LLX_LAUNCH_CHECK(fn);
@@ -130,6 +147,57 @@ extern "C" int llx_attn_fwd(const void* q, int64_t q_sb, int64_t q_ss, const voi
   a.doc_ids = doc_ids; a.prefix_len = prefix_len; a.flags = (doc_ids || prefix_len) ? (const uint8_t*)flags : nullptr;
   LLX_REQUIRE(S < (1 << 24), "llx_attn_fwd: S too large");
   return attn_fwd_launch("llx_attn_fwd", a.flags ? attn_fwd_kernel<true, false, 8> : attn_fwd_kernel<false, false, 8>, a, stream);
+}
+
+// The operands that the dropout entries (forward, backward, keep bytes) share: threshold = t = round(p * 65536), rng = device (seed, counter).
+int attn_dropout_check(const char* fn, int64_t threshold, const void* rng, int64_t stream_id, int64_t B, int64_t H) {
+  LLX_REQUIRE(rng && (uintptr_t)rng % 8 == 0, "%s: rng must be a device pointer to two int64 (seed, counter)", fn);
+  LLX_REQUIRE(threshold > 0 && threshold < 65536, "%s: threshold=%lld out of range (0 < round(p * 65536) < 65536)", fn, (long long)threshold);
+  LLX_REQUIRE(stream_id >= 0 && stream_id < (1ll << 31), "%s: stream_id=%lld out of range", fn, (long long)stream_id);
+  LLX_REQUIRE(B < 65536 && H < 65536, "%s: B and H must stay below 65536 (the mask key takes 16 bits of each)", fn);
+  return LLX_OK;
+}
+
+// llx_attn_fwd with attention dropout (SDPA's dropout_p in training): the same operands, then threshold = round(p * 65536), rng = device
+// pointer to (seed, counter) as int64, stream_id = one value per attention module.  lse is that of the undropped rows.
+extern "C" int llx_attn_fwd_dropout(const void* q, int64_t q_sb, int64_t q_ss, const void* k, int64_t k_sb, int64_t k_ss, const void* v,
+                                    int64_t v_sb, int64_t v_ss, void* o, int64_t o_sb, int64_t o_ss, float* lse, const int* doc_ids,
+                                    const int* prefix_len, const void* flags, int64_t B, int64_t S, int64_t H, int64_t KVH, int64_t head_dim,
+                                    float scale, int64_t threshold, const void* rng, int64_t stream_id, hipStream_t stream) {
+  AttnFwdArgs a;
+  if (int rc = attn_fwd_args("llx_attn_fwd_dropout", a, q, q_sb, q_ss, k, k_sb, k_ss, v, v_sb, v_ss, o, o_sb, o_ss, lse, B, S, H, KVH, head_dim, scale)) return rc;
+  if (int rc = attn_dropout_check("llx_attn_fwd_dropout", threshold, rng, stream_id, B, H)) return rc;
+  LLX_REQUIRE(!(doc_ids || prefix_len) || flags, "llx_attn_fwd_dropout: tile flags required with doc_ids/prefix_len");
+  LLX_REQUIRE(S < (1 << 24), "llx_attn_fwd_dropout: S too large");
+  a.doc_ids = doc_ids; a.prefix_len = prefix_len; a.flags = (doc_ids || prefix_len) ? (const uint8_t*)flags : nullptr;
+  a.rng = (const int64_t*)rng; a.drop_thr = (uint32_t)threshold << 16; a.drop_c = 65536.f / (float)(65536 - threshold); a.stream_id = (int)stream_id;
+  return attn_fwd_launch("llx_attn_fwd_dropout", a.flags ? attn_fwd_dropout_kernel<true> : attn_fwd_dropout_kernel<false>, a, stream);
+}
+
+// keep[b, h, q, k] = 1 where attention dropout keeps the element, 0 where it drops it: the bytes of the mask that llx_attn_fwd_dropout /
+// llx_attn_bwd_dropout apply with the same (threshold, rng, stream_id), written out (tests; inspection).
+__global__ __launch_bounds__(256) void attn_dropout_keep_kernel(uint8_t* __restrict__ keep, const int64_t* __restrict__ rng, int stream_id,
+                                                               uint32_t thr16, int H, int Sq, int Skv, int64_t total) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int k = (int)(idx % Skv);
+  int64_t r = idx / Skv;
+  const int q = (int)(r % Sq);
+  r /= Sq;
+  keep[idx] = attn_dropout_keep(rng[0], rng[1], stream_id, (int)(r / H), (int)(r % H), q, k, thr16) ? 1 : 0;
+}
+
+extern "C" int llx_attn_dropout_keep(void* keep, int64_t B, int64_t H, int64_t Sq, int64_t Skv, int64_t threshold, const void* rng,
+                                     int64_t stream_id, hipStream_t stream) {
+  LLX_REQUIRE(keep && B > 0 && H > 0 && Sq > 0 && Skv > 0, "llx_attn_dropout_keep: bad arguments");
+  if (int rc = attn_dropout_check("llx_attn_dropout_keep", threshold, rng, stream_id, B, H)) return rc;
+  LLX_REQUIRE(Sq < (1 << 24) && Skv < (1 << 24), "llx_attn_dropout_keep: Sq or Skv too large");
+  const int64_t total = B * H * Sq * Skv;
+  LLX_REQUIRE(cdiv64(total, 256) < (1ll << 31), "llx_attn_dropout_keep: too many elements");
+  hipLaunchKernelGGL(attn_dropout_keep_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, stream, (uint8_t*)keep, (const int64_t*)rng,
+                     (int)stream_id, (uint32_t)threshold << 16, (int)H, (int)Sq, (int)Skv, total);
+  LLX_LAUNCH_CHECK("llx_attn_dropout_keep");
+  return LLX_OK;
 }
 
 // Tile classes of a dense bool mask [B | 1, Sq, Skv] (row stride m_sq, batch stride m_sb, bytes): the layout llx_attn_tile_flags writes,

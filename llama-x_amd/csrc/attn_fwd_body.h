@@ -1,6 +1,8 @@
 // Body of the attention forward kernels (attn_fwd.hip), included once per __global__ function: as a __device__ function template
 // the same text compiles to a different register allocation of attn_fwd_kernel<true, false, 8> (214 instead of 244 VGPRs), and the
-// measured kernels are to stay what they are.  Expects `a` (AttnFwdArgs) and the constants MODE, STAMP, NW in scope.
+// measured kernels are to stay what they are.  Expects `a` (AttnFwdArgs) and the constants MODE, STAMP, NW, DROPOUT in scope.
+// DROPOUT (attn_dropout.h): only the P that feeds P.V is masked and scaled, where it is packed to bf16; the row maximum, the row sum,
+// the deferred base and lse are those of the undropped row.
   constexpr bool GENERAL = MODE != ATT_CAUSAL;  // tile classes come from flags
   constexpr bool DOCS = MODE == ATT_GENERAL;    // doc_ids / prefix_len
   constexpr bool MASK = MODE == ATT_MASK;
@@ -107,6 +109,12 @@
 #pragma unroll
     for (int e = 0; e < 16; ++e) o[i][e] = 0.f;
   float m_run = -INFINITY, l_run = 0.f;
+  AttnDropKey dkey = {0u, 0u};
+  uint32_t drow = 0;  // the row term of this lane's query row
+  if constexpr (DROPOUT) {
+    dkey = attn_dropout_key(a.rng[0], a.rng[1], a.stream_id, b, h);
+    drow = attn_drop_row(dkey, qi);
+  }
 
   const int* docrow = (DOCS && a.doc_ids) ? a.doc_ids + (int64_t)b * a.S : nullptr;
   const int my_doc = docrow ? docrow[qrow] : 0;
@@ -293,7 +301,14 @@
         constexpr int st_ = decltype(set_tag)::value, step = decltype(step_tag)::value;
         bf16x8_t pb;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) pb[j] = (__bf16)st[step >> 1][8 * (step & 1) + j];
+        for (int j = 0; j < 8; ++j) {
+          float p = st[step >> 1][8 * (step & 1) + j];
+          if constexpr (DROPOUT) {  // absolute key index of element j (the map above), also in a ragged last tile
+            const int kk = t * BKV + 32 * (step >> 1) + 16 * (step & 1) + 8 * (j >> 2) + 4 * hh + (j & 3);
+            p = attn_drop_keep(drow, attn_drop_col(dkey, kk), a.drop_thr) ? p * a.drop_c : 0.f;
+          }
+          pb[j] = (__bf16)p;
+        }
         if constexpr (step < 3) lds_tr_wait8<8>(Vl[st_], Vh[st_]);
         else lds_tr_wait8<0>(Vl[st_], Vh[st_]);
 #pragma unroll

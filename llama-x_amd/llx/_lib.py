@@ -29,6 +29,8 @@ SIGNATURES: dict[str, tuple] = {
     "llx_attn_flags_bytes": (c_int64, [_L, _L]),
     "llx_attn_tile_flags": (c_int, [_P, _P, _P, _L, _L, _P]),
     "llx_attn_fwd": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _P, _P, _P, _L, _L, _L, _L, _L, _F, _P]),
+    "llx_attn_fwd_dropout": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _P, _P, _P, _L, _L, _L, _L, _L, _F, _L, _P, _L, _P]),
+    "llx_attn_dropout_keep": (c_int, [_P, _L, _L, _L, _L, _L, _P, _L, _P]),
     "llx_attn_dense_fwd": (c_int, [_P, _L, _L, _L, _P, _L, _L, _L, _P, _L, _L, _L, _P, _L, _L, _L, _P, _L, _L, _L, _L, _L, _L, _L, _L, _L, _F, _P]),
     "llx_attn_mask_flags_bytes": (c_int64, [_L, _L, _L]),
     "llx_attn_mask_tile_flags": (c_int, [_P, _L, _L, _P, _L, _L, _L, _P]),
@@ -52,6 +54,8 @@ SIGNATURES: dict[str, tuple] = {
     "llx_attn_bwd_ds_bytes": (c_int64, [_L, _L, _L]),
     "llx_attn_bwd": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _P, _P, _L, _L, _P, _L, _L, _P, _L, _L,
                              _P, _P, _P, _P, _P, _L, _L, _L, _L, _L, _F, _P]),
+    "llx_attn_bwd_dropout": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _P, _P, _L, _L, _P, _L, _L, _P, _L, _L,
+                                     _P, _P, _P, _P, _P, _L, _L, _L, _L, _L, _F, _L, _P, _L, _P]),
     "llx_attn_mask_bwd": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _P, _P, _L, _L, _P, _L, _L, _P, _L, _L,
                                   _P, _L, _L, _P, _P, _L, _L, _L, _L, _L, _F, _P]),
     "llx_embedding_fwd": (c_int, [_P, _P, _P, _L, _L, _L, _L, _L, _L, _P]),

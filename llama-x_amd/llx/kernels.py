@@ -615,14 +615,45 @@ def maskspec_from_dense(mask: Tensor, B: int, S: int) -> Optional[MaskSpec]:
     return MaskSpec(doc.to(torch.int32) if has_doc else None, prefix.to(torch.int32) if has_prefix else None)
 
 
-def attn_fwd(q: Tensor, k: Tensor, v: Tensor, mask: Optional[MaskSpec] = None) -> tuple[Tensor, Tensor]:
-    """q [B,S,H,128], k/v [B,S,KVH,128] (last two dims dense; batch/seq strides free) -> o [B,S,H,128], lse [B,H,S]."""
+def attn_dropout_threshold(p: float) -> int:
+    """t = round(p * 65536) for 0 < p < 1: the kernels drop an element with probability t / 65536 and scale a kept one by
+    65536 / (65536 - t) (csrc/attn_dropout.h), so the realised probability and the scale match exactly."""
+    if not (isinstance(p, (int, float)) and 0.0 < p < 1.0):
+        raise L.LlxError(f"attn_dropout={p!r} must lie in [0, 1)")  # (0 itself never gets here: it takes the kernels without dropout)
+    return min(65535, max(1, int(round(p * 65536))))
+
+
+def _dropout_operands(dropout, device, fn: str):
+    """(threshold, rng pointer, stream_id) of a ``dropout=(threshold, rng, stream_id)`` argument: rng is the int64 [2] device tensor
+    (seed, counter) the kernels read - the ticket of the step, the same tensor in forward and backward."""
+    t, rng, sid = dropout
+    if not (isinstance(rng, Tensor) and rng.dtype is torch.int64 and rng.numel() == 2 and rng.is_contiguous() and rng.device == device):
+        raise L.LlxError(f"{fn}: attn_dropout needs rng = a contiguous int64 [2] tensor (seed, counter) on {device}")
+    return int(t), L.ptr(rng), int(sid)
+
+
+def attn_dropout_keep(B: int, H: int, Sq: int, Skv: int, dropout) -> Tensor:
+    """The keep bytes [B, H, Sq, Skv] (1 = kept, 0 = dropped) that attn_fwd / attn_bwd apply under the same
+    ``dropout=(threshold, rng, stream_id)``: written by the device function the attention kernels call."""
+    t, rng, sid = dropout
+    keep = torch.empty(B, H, Sq, Skv, device=rng.device, dtype=torch.uint8)
+    t, rp, sid = _dropout_operands(dropout, keep.device, "attn_dropout_keep")
+    L.check(_lib().llx_attn_dropout_keep(L.ptr(keep), B, H, Sq, Skv, t, rp, sid, L.stream()), "llx_attn_dropout_keep")
+    return keep
+
+
+def attn_fwd(q: Tensor, k: Tensor, v: Tensor, mask: Optional[MaskSpec] = None, dropout=None) -> tuple[Tensor, Tensor]:
+    """q [B,S,H,128], k/v [B,S,KVH,128] (last two dims dense; batch/seq strides free) -> o [B,S,H,128], lse [B,H,S].
+    dropout = (threshold, rng, stream_id) or None: attention dropout as SDPA's dropout_p in training (attn_dropout_threshold,
+    an int64 [2] device tensor (seed, counter), one id per attention module); lse stays that of the undropped rows."""
     _chk_bf16(q, k, v)
     B, S, H, hd = q.shape
     KVH = k.shape[2]
     for t in (q, k, v):
         assert t.stride(3) == 1 and t.stride(2) == hd
     if mask is not None and mask.dense is not None:  # any bool mask: the mask-driven tile loop, o as the rows `wo` reads
+        if dropout is not None:
+            raise L.LlxError("attn_dropout: MaskSpec(dense=...) has no dropout kernels (the rule forms doc_ids / prefix_len and the causal mask have)")
         mask = mask.prepared(B, S, q.device)
         o, lse = attn_mask_fwd(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), mask._rows, lse=True)
         return o.view(B, S, H, hd), lse
@@ -633,9 +664,12 @@ def attn_fwd(q: Tensor, k: Tensor, v: Tensor, mask: Optional[MaskSpec] = None) -
         mask = mask.prepared(B, S, q.device)
         d, p, fl = mask.doc_ids, mask.prefix_len, mask._flags
     ev = _trace_begin(ATTN_TRACE)
-    L.check(_lib().llx_attn_fwd(L.ptr(q), q.stride(0), q.stride(1), L.ptr(k), k.stride(0), k.stride(1), L.ptr(v), v.stride(0), v.stride(1),
-                                L.ptr(o), o.stride(0), o.stride(1), L.ptr(lse), L.ptr(d), L.ptr(p), L.ptr(fl), B, S, H, KVH, hd,
-                                1.0 / math.sqrt(hd), L.stream()), "llx_attn_fwd")
+    args = (L.ptr(q), q.stride(0), q.stride(1), L.ptr(k), k.stride(0), k.stride(1), L.ptr(v), v.stride(0), v.stride(1), L.ptr(o), o.stride(0),
+            o.stride(1), L.ptr(lse), L.ptr(d), L.ptr(p), L.ptr(fl), B, S, H, KVH, hd, 1.0 / math.sqrt(hd))
+    if dropout is not None:
+        L.check(_lib().llx_attn_fwd_dropout(*args, *_dropout_operands(dropout, q.device, "attn_fwd"), L.stream()), "llx_attn_fwd_dropout")
+    else:
+        L.check(_lib().llx_attn_fwd(*args, L.stream()), "llx_attn_fwd")
     _trace_end(ATTN_TRACE, ev, "fwd", B, S, H)
     return o, lse
 
@@ -665,13 +699,16 @@ def _attn_bwd_operands(q: Tensor, k: Tensor, v: Tensor, o: Tensor, do: Tensor, l
 
 
 def attn_bwd(q: Tensor, k: Tensor, v: Tensor, o: Tensor, do: Tensor, lse: Tensor, dq: Tensor, dk: Tensor, dv: Tensor,
-             mask: Optional[MaskSpec] = None, rope: Optional[Tensor] = None) -> None:
-    """rope (fp32 table [>= S, 64, 2]): q, k are the rotated projections; dq, dk come out as gradients of the un-rotated ones."""
+             mask: Optional[MaskSpec] = None, rope: Optional[Tensor] = None, dropout=None) -> None:
+    """rope (fp32 table [>= S, 64, 2]): q, k are the rotated projections; dq, dk come out as gradients of the un-rotated ones.
+    dropout: exactly what attn_fwd was given (the rng tensor must still hold the forward's seed and counter)."""
     B, S, H = q.shape[:3]
     d = p = fl = None
     if mask is not None:
         mask = mask.prepared(B, S, q.device)
         if mask.dense is not None:
+            if dropout is not None:
+                raise L.LlxError("attn_dropout: MaskSpec(dense=...) has no dropout kernels (the rule forms doc_ids / prefix_len and the causal mask have)")
             return attn_mask_bwd(q, k, v, o, do, lse, dq, dk, dv, mask._rows, rope=rope)
         d, p, fl = mask.doc_ids, mask.prefix_len, mask._flags
     lead, trail, ws = _attn_bwd_operands(q, k, v, o, do, lse, dq, dk, dv, rope)
@@ -681,6 +718,12 @@ def attn_bwd(q: Tensor, k: Tensor, v: Tensor, o: Tensor, do: Tensor, lse: Tensor
     # whose dQ kernel recomputes S and dP.
     ds = None
     ds_bytes = _lib().llx_attn_bwd_ds_bytes(B, S, H)
+    if dropout is not None:  # the default route only: the dS scratch route has no dropout build
+        ev = _trace_begin(ATTN_TRACE)
+        L.check(_lib().llx_attn_bwd_dropout(*lead, L.ptr(d), L.ptr(p), L.ptr(fl), L.ptr(rope), None, *trail[:-1],
+                                            *_dropout_operands(dropout, q.device, "attn_bwd"), trail[-1]), "llx_attn_bwd_dropout")
+        _trace_end(ATTN_TRACE, ev, "bwd", B, S, H)
+        return
     if _ATTN_BWD_DS and ds_bytes <= _ATTN_BWD_DS_MAX:
         ds = torch.empty(ds_bytes // 2, device=q.device, dtype=BF16)
     ev = _trace_begin(ATTN_TRACE)

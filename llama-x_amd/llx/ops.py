@@ -637,17 +637,53 @@ def rmsnorm(x: Tensor, w: Tensor, eps: float) -> Tensor:
 # =================================================================================================
 # attention residual branch:  [x +] wo( attn( rope(wq xn), rope(wk xn), wv xn ) ),  xn = [rmsnorm(x)]
 # =================================================================================================
+# Attention dropout state: one int64 [2] tensor (seed, counter) per device, created at the first training forward with dropout from
+# torch.initial_seed() (so the ranks of a data-parallel job differ by their torch seeds, as in PyTorch) and counter 0.  A training step
+# takes a TICKET - a clone of the state - and advances the counter, both as launches on the device (no host read: capturable, and a
+# replayed graph draws a new mask on every replay).  The kernels of the step's forward and backward read the ticket, never the live
+# state: two forwards before a backward keep their own masks, and recomputation under activation checkpointing sees the same ticket.
+_ATTN_RNG: dict = {}
+
+
+def _attn_rng(device) -> Tensor:
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    st = _ATTN_RNG.get(device)
+    if st is None:
+        st = _ATTN_RNG[device] = torch.tensor([torch.initial_seed() & (2**63 - 1), 0], dtype=torch.int64, device=device)
+    return st
+
+
+def seed_attn_dropout(seed: int, counter: int = 0, device=None) -> None:
+    """Set the attention-dropout state (seed, counter) of ``device`` (default: the current one), in place: a captured training step
+    that was recorded against the state keeps working and continues from the new values."""
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    _attn_rng(device).copy_(torch.tensor([int(seed) & (2**63 - 1), int(counter)], dtype=torch.int64))
+
+
+def attn_dropout_ticket(device) -> Tensor:
+    """The (seed, counter) a training step's attention kernels read: a clone of the device's state, whose counter then advances."""
+    st = _attn_rng(device)
+    ticket = st.clone()
+    st[1:].add_(1)
+    return ticket
+
+
 class AttnBlockMeta:
-    def __init__(self, qkv: GroupPlan, wo: GroupPlan, num_heads, num_kv_heads, head_dim, mask, eps, fuse_norm, fuse_residual):
+    def __init__(self, qkv: GroupPlan, wo: GroupPlan, num_heads, num_kv_heads, head_dim, mask, eps, fuse_norm, fuse_residual,
+                 dropout: Optional[tuple] = None):
         self.qkv, self.wo = qkv, wo
         self.H, self.KVH, self.hd = num_heads, num_kv_heads, head_dim
         self.mask, self.eps = mask, eps
         self.fuse_norm, self.fuse_residual = fuse_norm, fuse_residual
+        self.dropout = dropout  # (threshold, stream_id) or None; the ticket travels as a tensor argument of AttnBlockFn
 
 
 class AttnBlockFn(Function):
     @staticmethod
-    def forward(ctx, x: Tensor, rope: Tensor, norm_w: Optional[Tensor], meta: AttnBlockMeta, *tensors):
+    def forward(ctx, x: Tensor, rope: Tensor, norm_w: Optional[Tensor], meta: AttnBlockMeta, ticket: Optional[Tensor], *tensors):
         K.L.require_cuda(x)
         B, S, D = x.shape
         H, KVH, hd = meta.H, meta.KVH, meta.hd
@@ -663,24 +699,24 @@ class AttnBlockFn(Function):
         q = qkv3[..., : H * hd].unflatten(-1, (H, hd))
         k = qkv3[..., H * hd : (H + KVH) * hd].unflatten(-1, (KVH, hd))
         v = qkv3[..., (H + KVH) * hd :].unflatten(-1, (KVH, hd))
-        o, lse = K.attn_fwd(q, k, v, meta.mask)
+        o, lse = K.attn_fwd(q, k, v, meta.mask, dropout=(meta.dropout[0], ticket, meta.dropout[1]) if meta.dropout else None)
         o2 = o.view(B * S, H * hd)
         y, to = meta.wo.forward(o2, None, x2 if meta.fuse_residual else None)
         ctx.meta = meta
         # x2 is x itself (or its contiguous copy) and xn == x2 without the fused norm: saved once, by identity, below
-        _save(ctx, x, rope, norm_w, x2, xn if meta.fuse_norm else None, rstd, qkv3, o, lse, tqkv, to)
+        _save(ctx, x, rope, norm_w, x2, xn if meta.fuse_norm else None, rstd, qkv3, o, lse, tqkv, to, ticket if meta.dropout else None)
         return y.view(B, S, D)
 
     @staticmethod
     def backward(ctx, dy: Tensor):
         meta: AttnBlockMeta = ctx.meta
-        x, rope, norm_w, x2, xn, rstd, qkv3, o, lse, tqkv, to = _load(ctx)
+        x, rope, norm_w, x2, xn, rstd, qkv3, o, lse, tqkv, to, ticket = _load(ctx)
         if xn is None:
             xn = x2
         B, S, D = x.shape
         H, KVH, hd = meta.H, meta.KVH, meta.hd
         dy2 = K._rows2d(dy.contiguous())
-        needs = list(ctx.needs_input_grad[4:])
+        needs = list(ctx.needs_input_grad[5:])
         n_qkv = len(meta.qkv.tensors())
         nqkv, no = needs[:n_qkv], needs[n_qkv:]
         pend = []  # second stages of the four adapter-gradient products of this block: one launch at the end
@@ -696,7 +732,8 @@ class AttnBlockFn(Function):
         dk = dqkv[..., H * hd : (H + KVH) * hd].unflatten(-1, (KVH, hd))
         dv = dqkv[..., (H + KVH) * hd :].unflatten(-1, (KVH, hd))
         # apply_rope's transpose rides in the dQ epilogue and the dK/dV reduce
-        K.attn_bwd(q, k, v, o, do2.view(B, S, H, hd), lse, dq, dk, dv, meta.mask, rope=rope)
+        K.attn_bwd(q, k, v, o, do2.view(B, S, H, hd), lse, dq, dk, dv, meta.mask, rope=rope,
+                   dropout=(meta.dropout[0], ticket, meta.dropout[1]) if meta.dropout else None)
         d2 = dqkv.view(B * S, W)
         need_dx = ctx.needs_input_grad[0]
         need_dxn = need_dx or (meta.fuse_norm and ctx.needs_input_grad[2])  # the norm weight gradient needs d(xn) too
@@ -704,7 +741,7 @@ class AttnBlockFn(Function):
         _, g_qkv = meta.qkv.backward(d2, xn, tqkv, nqkv, need_dxn, dxn, pending=pend)
         K.skinny_tn_flush(pend)
         dx, dnw = _norm_epilogue(dxn, x2, norm_w, rstd, ctx.needs_input_grad[2], dy2 if (need_dx and meta.fuse_residual) else None, meta.fuse_norm)
-        return (dx.view(B, S, D) if (dx is not None and need_dx) else None, None, dnw, None, *g_qkv, *g_o)
+        return (dx.view(B, S, D) if (dx is not None and need_dx) else None, None, dnw, None, None, *g_qkv, *g_o)
 
 
 # =================================================================================================

@@ -149,6 +149,16 @@ def _as_maskspec(block_mask):
     )
 
 
+def _refuse_block_mask_with_dropout(p: float, block_mask) -> None:
+    """Train mode with attn_dropout set and an explicit block_mask=: refused, before any launch."""
+    if isinstance(block_mask, MaskSpec) and block_mask.dense is not None:
+        raise LlxError(f"attn_dropout={p} in train mode with block_mask=MaskSpec(dense=...): the mask-driven kernels have no dropout - "
+                       "set attn_dropout=0 or call model.eval()")
+    if block_mask is not None:
+        raise LlxError(f"attn_dropout={p} in train mode with an explicit block_mask=: the reference's flex_attention branch applies no "
+                       "dropout, so the field would be ignored - set attn_dropout=0, or pass the mask as mask=")
+
+
 # ------------------------------------------------------------------------------------------------- blocks
 class Attention(nn.Module):
     def __init__(self, config: LlamaConfig) -> None:
@@ -164,30 +174,52 @@ class Attention(nn.Module):
         self.wv = Linear(self.embed_dim, self.num_kv_heads * self.head_dim, bias=False)
         self.wo = Linear(self.num_heads * self.head_dim, self.embed_dim, bias=False)
         self.kv_cache = None
+        self.dropout_stream_id = 0  # which mask stream of a step this module draws from: Llama.__init__ assigns the layer index
 
     def plans(self):
         return ops.GroupPlan((self.wq, self.wk, self.wv)), ops.GroupPlan((self.wo,))
 
-    def _run(self, x: Tensor, rope: Tensor, norm: nn.Module | None, residual: bool, mask, input_pos, block_mask, plans=None) -> Tensor:
+    def _dropout(self) -> bool:
+        """Attention dropout is active: train mode and 0 < attn_dropout < 1 (the reference: ``self.attn_dropout if self.training else 0.0``)."""
+        if not self.training or self.attn_dropout == 0.0:
+            return False
+        if not (isinstance(self.attn_dropout, (int, float)) and 0.0 < self.attn_dropout < 1.0):
+            raise LlxError(f"attn_dropout={self.attn_dropout!r} must lie in [0, 1)")
+        return True
+
+    def _run(self, x: Tensor, rope: Tensor, norm: nn.Module | None, residual: bool, mask, input_pos, block_mask, plans=None,
+             attn_ticket: Tensor | None = None) -> Tensor:
+        drop = self._dropout()
+        mask_arg_none = mask is None  # (a recognised dense mask= becomes a block_mask below)
         if mask is not None and self.kv_cache is None and torch.is_grad_enabled() and (
                 x.requires_grad or any(p.requires_grad for p in self.parameters()) or (norm is not None and norm.weight.requires_grad)):
             # training through the reference's dense-mask route (llama.py:135-137): a mask that the MaskSpec rule reproduces exactly
             # (causal / prefix-LM / contiguous documents) runs on the fused kernels with their backward; anything else trains through
             # block_mask=MaskSpec(dense=mask) (this route keeps the reference's mask= semantics and does not guess)
             spec = ops._cached(mask, "maskspec", lambda: (K.maskspec_from_dense(mask, x.shape[0], x.shape[1]),))[0]
+            if spec is None and drop:
+                raise LlxError(f"attn_dropout={self.attn_dropout} with a dense mask= that is not of the form (k <= q or k < prefix[b]) and "
+                               "same-document: the mask-driven kernels have no dropout - use a mask of that form or set attn_dropout=0")
             if spec is None:
                 raise LlxError("training with a dense mask= needs a mask of the form (k <= q or k < prefix[b]) and same-document "
                                "(contiguous documents): pass block_mask=MaskSpec(dense=mask) to train through any other bool mask")
             mask, block_mask = None, (spec if (spec.doc_ids is not None or spec.prefix_len is not None) else None)
         if self.kv_cache is not None or mask is not None:
             return self._run_dense(x, rope, norm, residual, mask, input_pos)
-        if self.training and self.attn_dropout > 0.0:
-            raise LlxError("attention dropout is not supported by the HIP attention kernel (reference default is 0.0)")
+        dropout = None
+        if drop:
+            # Dropout applies where the reference's SDPA branch runs: no mask (causal) and a dense mask= recognised as a rule (above).
+            # Its flex_attention branch (block_mask=) applies none, so an explicit block_mask with attn_dropout set is refused, not ignored.
+            if mask_arg_none:
+                _refuse_block_mask_with_dropout(self.attn_dropout, block_mask)
+            dropout = (K.attn_dropout_threshold(self.attn_dropout), int(self.dropout_stream_id))
+            if attn_ticket is None:  # a stand-alone Attention / TransformerLayer draws its own
+                attn_ticket = ops.attn_dropout_ticket(x.device)
         qkv, wo = plans or self.plans()
         meta = ops.AttnBlockMeta(qkv, wo, self.num_heads, self.num_kv_heads, self.head_dim, _as_maskspec(block_mask),
-                                 norm.eps if norm is not None else 0.0, norm is not None, residual)
+                                 norm.eps if norm is not None else 0.0, norm is not None, residual, dropout)
         tensors = qkv.tensors() + wo.tensors()
-        return ops.AttnBlockFn.apply(x, _rope_f32(rope), norm.weight if norm is not None else None, meta, *tensors)
+        return ops.AttnBlockFn.apply(x, _rope_f32(rope), norm.weight if norm is not None else None, meta, attn_ticket if drop else None, *tensors)
 
     def _run_dense(self, x: Tensor, rope: Tensor, norm, residual: bool, mask, input_pos) -> Tensor:
         """Inference path: KV cache and/or an explicit bool mask (SDPA branch with is_causal=False, llama.py:126-127,135-137).
@@ -224,8 +256,8 @@ class Attention(nn.Module):
         return y.view(B, L_, -1)
 
     def forward(self, x: Tensor, rope: Tensor, *, mask: Tensor | None = None, input_pos: Tensor | None = None,
-                block_mask=None) -> Tensor:
-        return self._run(x, rope, None, False, mask, input_pos, block_mask)
+                block_mask=None, attn_ticket: Tensor | None = None) -> Tensor:
+        return self._run(x, rope, None, False, mask, input_pos, block_mask, attn_ticket=attn_ticket)
 
 
 class FeedForward(nn.Module):
@@ -258,15 +290,17 @@ class TransformerLayer(nn.Module):
         self.feed_forward = FeedForward(config)
 
     def forward(self, x: Tensor, rope: Tensor, *, mask: Tensor | None = None, input_pos: Tensor | None = None,
-                block_mask=None) -> Tensor:
+                block_mask=None, attn_ticket: Tensor | None = None) -> Tensor:
         # x + attention(attention_norm(x)) and x + feed_forward(ffn_norm(x)), each as one fused autograd node
         if D.layer_ok(self, x, mask) and not (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))):
             return D.layer_forward(self, x, _rope_f32(rope).contiguous(), mask, input_pos)  # decode: every linear a weight stream
+        if mask is None and self.attention.kv_cache is None and self.attention._dropout():
+            _refuse_block_mask_with_dropout(self.attention.attn_dropout, block_mask)
         pa = pf = None
         if x.is_cuda and self.attention.kv_cache is None and mask is None:
             pa, pf = self.attention.plans(), self.feed_forward.plans()
             ops.prepack((*pa, *pf))  # the LoRA operand images of the layer's four linear groups from one launch
-        x = self.attention._run(x, rope, self.attention_norm, True, mask, input_pos, block_mask, pa)
+        x = self.attention._run(x, rope, self.attention_norm, True, mask, input_pos, block_mask, pa, attn_ticket)
         return self.feed_forward._run(x, self.ffn_norm, True, pf)
 
 
@@ -275,6 +309,8 @@ class Llama(nn.Module):
         super().__init__()
         self.tok_embeddings = Embedding(config.vocab_size, config.embed_dim)
         self.layers = nn.ModuleList([TransformerLayer(config) for _ in range(config.num_layers)])
+        for i, layer in enumerate(self.layers):
+            layer.attention.dropout_stream_id = i  # attention dropout: every layer draws its own mask from the step's ticket
         self.norm = RMSNorm(config.embed_dim, eps=1e-5)
         self.output = Linear(config.embed_dim, config.vocab_size, bias=False)
         self.config = config
@@ -292,6 +328,12 @@ class Llama(nn.Module):
             self.register_buffer("causal_mask", torch.tril(torch.ones(L, L, dtype=torch.bool)), persistent=False)
 
     def _run_layers(self, x: Tensor, rope: Tensor, lo: int = 0, hi: int | None = None, **kw) -> Tensor:
+        if self.training and self.config.attn_dropout != 0.0 and kw.get("input_pos") is None and x.is_cuda:
+            K.attn_dropout_threshold(self.config.attn_dropout)  # (the range check, before any launch)
+            _refuse_block_mask_with_dropout(self.config.attn_dropout, kw.get("block_mask"))
+            # one ticket per step (two launches on the device, no host read); the layers differ by their stream ids, and a layer that is
+            # recomputed under activation checkpointing gets the same ticket again
+            kw["attn_ticket"] = ops.attn_dropout_ticket(x.device)
         for layer in self.layers[lo:hi]:
             if self.config.activation_checkpointing:
                 x = checkpoint(layer, x, rope, use_reentrant=False, **kw)
