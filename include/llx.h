@@ -212,6 +212,16 @@ int llx_gemv_i8(const void* w0, int64_t ldw0, int64_t n0, const void* w1, int64_
                 int64_t c_ss, const int64_t* input_pos, const void* bext0, const void* bext1, const void* bext2, int64_t rank0, int64_t rank1,
                 int64_t rank2, const void* t, int64_t ldt, float lora_scale, const void* scale0, const void* scale1, const void* scale2,
                 int dynamic, llx_stream_t s);
+/* llx_gemv_bf16 on DoRA linears (modelling/lora.py:51-59) whose row factor c_s = m / ||W_s + s B_s A_s||_row the caller has cached:
+ * colscale_s [n_s] bf16, one for every present segment (2-byte aligned).  Per output feature: z = bf16(x . W^T + lora_scale * t . bext[row]),
+ * v = bf16(z * colscale[row]) - the roundings of out * (m / norm) in the bf16 eager graph -, then the epilogue of llx_gemv_bf16 on v
+ * (q and k are scaled before RoPE, gate and up each by their own factor before SwiGLU).  Every other operand as llx_gemv_bf16. */
+int llx_gemv_bf16_dora(const void* w0, int64_t ldw0, int64_t n0, const void* w1, int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2, int64_t n2,
+                       const void* x, int64_t ldx, int64_t M, int64_t K, const void* norm_w, float eps, int epilogue, void* out, int64_t ldo,
+                       const void* res, int64_t ldr, const float* rope, int64_t n_q, int64_t n_k, void* k_cache, void* v_cache, int64_t c_sh,
+                       int64_t c_ss, const int64_t* input_pos, const void* bext0, const void* bext1, const void* bext2, int64_t rank0, int64_t rank1,
+                       int64_t rank2, const void* t, int64_t ldt, float lora_scale, const void* colscale0, const void* colscale1,
+                       const void* colscale2, llx_stream_t s);
 /* *extent (device int) = 1 + the largest key index any of the `rows` bool mask rows (row stride in bytes) allows; 0 if none: the
  * mask of the cached path is data (rows of a tril matrix gathered at input_pos, :194,:205), its extent sizes the decode key ranges. */
 int llx_mask_extent(const void* mask, int64_t row_stride, int64_t rows, int64_t Skv, int* extent, llx_stream_t s);

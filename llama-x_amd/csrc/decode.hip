@@ -88,8 +88,11 @@ __device__ __forceinline__ int wave_sum_valu_i(int v) {
 // int8 kinds: a lane's 16 bytes are 16 elements, a piece is 1024 elements.  WK_I8W keeps x in LDS as bf16, each piece stored as its
 // lanes' first eight elements (1 KiB) followed by their second eight, so that both 16-byte reads of a lane are conflict-free;
 // WK_I8D keeps x as int8 (after the optional norm each row is quantised here, the row scales stay in registers).
-template <int MT, int EPI, bool NORM, int RPW = 4, int WK = WK_BF16>
+// DORA (bf16 rows): a.wscale holds DoRA's per-row factors.  A build of its own, not a test of the pointer: the test cost the existing
+// instances 2-7 SGPRs and the 4-token q|k|v instance four more spilled registers.
+template <int MT, int EPI, bool NORM, int RPW = 4, int WK = WK_BF16, bool DORA = false>
 __global__ __launch_bounds__(256, 2) void gemv_kernel(const GemvArgs a) {
+  static_assert(!DORA || WK == WK_BF16, "DoRA factors ride on bf16 rows only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -110,7 +113,9 @@ __global__ __launch_bounds__(256, 2) void gemv_kernel(const GemvArgs a) {
   // ---- row groups: RPW output rows per wave at a time.  SWIGLU: the gate and up rows of RPW / 2 hidden units (W[0] rows UPG g .. and
   // W[1] rows UPG g ..; r = matrix * UPG + unit), so that the epilogue has g and u of one unit side by side.
   constexpr int UPG = RPW / 2;  // hidden units per SwiGLU group
-  struct Grp { const WT* wr[RPW]; int row0, seg; float sc[RPW]; };  // sc: the rows' weight scales (int8 kinds)
+  // sc: the rows' weight scales (int8 kinds); cp: where the rows' DoRA factors sit (DORA; clamped like the weight rows; wave-uniform,
+  // so the addresses wait in scalar registers while the rows stream and the factors themselves are only read in the epilogue)
+  struct Grp { const WT* wr[RPW]; int row0, seg; float sc[RPW]; const bf16_t* cp[RPW]; };
   auto setup = [&](int g, Grp& G) {
     if constexpr (EPI == GV_SWIGLU) {
       const int half = a.N / 2;
@@ -120,6 +125,10 @@ __global__ __launch_bounds__(256, 2) void gemv_kernel(const GemvArgs a) {
       if constexpr (WK != WK_BF16) {
 #pragma unroll
         for (int r = 0; r < RPW; ++r) G.sc[r] = bf2f(a.wscale[r / UPG][min(G.row0 + (r % UPG), half - 1)]);
+      }
+      if constexpr (DORA) {
+#pragma unroll
+        for (int r = 0; r < RPW; ++r) G.cp[r] = a.wscale[r / UPG] + min(G.row0 + (r % UPG), half - 1);
       }
     } else {
       G.row0 = RPW * g;
@@ -131,6 +140,10 @@ __global__ __launch_bounds__(256, 2) void gemv_kernel(const GemvArgs a) {
       if constexpr (WK != WK_BF16) {
 #pragma unroll
         for (int r = 0; r < RPW; ++r) G.sc[r] = bf2f(a.wscale[G.seg][min(G.row0 - base + r, last)]);
+      }
+      if constexpr (DORA) {
+#pragma unroll
+        for (int r = 0; r < RPW; ++r) G.cp[r] = a.wscale[G.seg] + min(G.row0 - base + r, last);
       }
     }
   };
@@ -299,6 +312,9 @@ __global__ __launch_bounds__(256, 2) void gemv_kernel(const GemvArgs a) {
 #pragma unroll
           for (int m = 1; m < MT; ++m) sm = lane == m ? acc[r][m] : sm;
           v[r] = bf2f(f2bf(sm));  // the linear's bf16 output
+          // DoRA (modelling/lora.py:57-59): times the row's cached factor c = m / ||W + s B A||, rounded - out * (m / norm) of the bf16
+          // eager graph.  Read here, by the lanes that write, through the address setup left in scalar registers
+          if constexpr (DORA) v[r] = bf2f(f2bf(v[r] * bf2f(*G.cp[r])));
         } else {
           float ls = lacc[r][0];
 #pragma unroll
@@ -356,34 +372,34 @@ __global__ __launch_bounds__(256, 2) void gemv_kernel(const GemvArgs a) {
   }
 }
 
-template <int MT, int EPI, int RPW, int WK>
-static int launch_gemv_n(const GemvArgs& a, int grid, size_t lds, hipStream_t stream) {
-  if (a.norm_w) hipLaunchKernelGGL((gemv_kernel<MT, EPI, true, RPW, WK>), dim3(grid), dim3(256), lds, stream, a);
-  else hipLaunchKernelGGL((gemv_kernel<MT, EPI, false, RPW, WK>), dim3(grid), dim3(256), lds, stream, a);
-  LLX_LAUNCH_CHECK(WK == WK_BF16 ? "llx_gemv_bf16" : "llx_gemv_i8");
+template <int MT, int EPI, int RPW, int WK, bool DORA>
+static int launch_gemv_n(const char* fn, const GemvArgs& a, int grid, size_t lds, hipStream_t stream) {
+  if (a.norm_w) hipLaunchKernelGGL((gemv_kernel<MT, EPI, true, RPW, WK, DORA>), dim3(grid), dim3(256), lds, stream, a);
+  else hipLaunchKernelGGL((gemv_kernel<MT, EPI, false, RPW, WK, DORA>), dim3(grid), dim3(256), lds, stream, a);
+  LLX_LAUNCH_CHECK(fn);
   return LLX_OK;
 }
 
-template <int MT, int RPW, int WK>
-static int launch_gemv_m(const GemvArgs& a, int epi, int grid, size_t lds, hipStream_t stream) {
+template <int MT, int RPW, int WK, bool DORA>
+static int launch_gemv_m(const char* fn, const GemvArgs& a, int epi, int grid, size_t lds, hipStream_t stream) {
   switch (epi) {
-    case GV_NONE: return launch_gemv_n<MT, GV_NONE, RPW, WK>(a, grid, lds, stream);
-    case GV_RESIDUAL: return launch_gemv_n<MT, GV_RESIDUAL, RPW, WK>(a, grid, lds, stream);
-    case GV_QKV: return launch_gemv_n<MT, GV_QKV, RPW, WK>(a, grid, lds, stream);
-    default: return launch_gemv_n<MT, GV_SWIGLU, RPW, WK>(a, grid, lds, stream);
+    case GV_NONE: return launch_gemv_n<MT, GV_NONE, RPW, WK, DORA>(fn, a, grid, lds, stream);
+    case GV_RESIDUAL: return launch_gemv_n<MT, GV_RESIDUAL, RPW, WK, DORA>(fn, a, grid, lds, stream);
+    case GV_QKV: return launch_gemv_n<MT, GV_QKV, RPW, WK, DORA>(fn, a, grid, lds, stream);
+    default: return launch_gemv_n<MT, GV_SWIGLU, RPW, WK, DORA>(fn, a, grid, lds, stream);
   }
 }
 
-template <int RPW, int WK>
-static int launch_gemv_mt(const GemvArgs& a, int MT, int epi, int grid, size_t lds, hipStream_t stream) {
+template <int RPW, int WK, bool DORA = false>
+static int launch_gemv_mt(const char* fn, const GemvArgs& a, int MT, int epi, int grid, size_t lds, hipStream_t stream) {
   switch (MT) {
-    case 1: return launch_gemv_m<1, RPW, WK>(a, epi, grid, lds, stream);
-    case 2: return launch_gemv_m<2, RPW, WK>(a, epi, grid, lds, stream);
+    case 1: return launch_gemv_m<1, RPW, WK, DORA>(fn, a, epi, grid, lds, stream);
+    case 2: return launch_gemv_m<2, RPW, WK, DORA>(fn, a, epi, grid, lds, stream);
     default:
       // (weight-only int8 has no 4-token build: 16 fp32 activations per lane and token next to the two weight register sets do not fit
       // the 256 registers of two workgroups per CU without scratch; its callers run 3 and 4 tokens as two passes of the 2-token build)
       if constexpr (WK == WK_I8W) { llx_set_error("llx_gemv_i8: no 4-token build of the weight-only kind"); return LLX_ERR_UNSUPPORTED; }
-      else return launch_gemv_m<4, RPW, WK>(a, epi, grid, lds, stream);
+      else return launch_gemv_m<4, RPW, WK, DORA>(fn, a, epi, grid, lds, stream);
   }
 }
 
@@ -393,8 +409,9 @@ static int launch_gemv_mt(const GemvArgs& a, int MT, int epi, int grid, size_t l
 // The epilogues are wstream.h's; q|k|v rotates row m by table row m and writes its k / v heads at input_pos[m] (device int64), caches
 // through (head, position) strides.  LoRA (nullable bext_s [n_s, rank_s], t [M, sum rank] bf16 = x . A^T, offsets t_off_s, scale):
 // out += scale * t_s . bext_s[row].
-// the two entry points below: fn = the caller's name for messages, wk = weight kind, ws_s = per-row scales of W_s (int8 kinds)
-static int gemv_run(const char* fn, int wk, const void* ws0, const void* ws1, const void* ws2, const void* w0, int64_t ldw0, int64_t n0, const void* w1, int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2,
+// the three entry points below: fn = the caller's name for messages, wk = weight kind, ws_s = per-row scales of W_s (int8 kinds) or
+// DoRA's per-row factors (bf16 rows with dora set: every present segment has one)
+static int gemv_run(const char* fn, int wk, bool dora, const void* ws0, const void* ws1, const void* ws2, const void* w0, int64_t ldw0, int64_t n0, const void* w1, int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2,
                              int64_t n2, const void* x, int64_t ldx, int64_t M, int64_t K, const void* norm_w, float eps, int epilogue,
                              void* out, int64_t ldo, const void* res, int64_t ldr, const float* rope, int64_t n_q, int64_t n_k, void* k_cache,
                              void* v_cache, int64_t c_sh, int64_t c_ss, const int64_t* input_pos, const void* bext0, const void* bext1,
@@ -405,8 +422,8 @@ static int gemv_run(const char* fn, int wk, const void* ws0, const void* ws1, co
   const int rc0 = stream_check_fill(fn, a, 1, 4, "larger row counts run the MFMA GEMM", wa, 4, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps,
                                     epilogue, out, ldo, res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sh, c_ss, input_pos);
   if (rc0 != LLX_OK) return rc0;
-  if (wk != WK_BF16) {
-    const int rc1 = stream_check_fill_scales(fn, a, ws0, ws1, ws2, n1, n2);
+  if (wk != WK_BF16 || dora) {
+    const int rc1 = stream_check_fill_scales(fn, a, dora ? "DoRA" : "int8", ws0, ws1, ws2, n1, n2);
     if (rc1 != LLX_OK) return rc1;
   }
   const bool lora = bext0 || bext1 || bext2;
@@ -449,9 +466,10 @@ static int gemv_run(const char* fn, int wk, const void* ws0, const void* ws1, co
     if (a.t) b.t = a.t + (int64_t)m0 * a.ldt;
     const int MT = mc == 1 ? 1 : (mc == 2 ? 2 : 4);
     const size_t lds = (size_t)MT * Kp * xb + 64;
-    if (wk == WK_I8W) return launch_gemv_mt<2, WK_I8W>(b, MT, epilogue, grid, lds, stream);
-    if (wk == WK_I8D) return launch_gemv_mt<2, WK_I8D>(b, MT, epilogue, grid, lds, stream);
-    return rpw == 2 ? launch_gemv_mt<2, WK_BF16>(b, MT, epilogue, grid, lds, stream) : launch_gemv_mt<4, WK_BF16>(b, MT, epilogue, grid, lds, stream);
+    if (wk == WK_I8W) return launch_gemv_mt<2, WK_I8W>(fn, b, MT, epilogue, grid, lds, stream);
+    if (wk == WK_I8D) return launch_gemv_mt<2, WK_I8D>(fn, b, MT, epilogue, grid, lds, stream);
+    if (dora) return rpw == 2 ? launch_gemv_mt<2, WK_BF16, true>(fn, b, MT, epilogue, grid, lds, stream) : launch_gemv_mt<4, WK_BF16, true>(fn, b, MT, epilogue, grid, lds, stream);
+    return rpw == 2 ? launch_gemv_mt<2, WK_BF16>(fn, b, MT, epilogue, grid, lds, stream) : launch_gemv_mt<4, WK_BF16>(fn, b, MT, epilogue, grid, lds, stream);
   };
   // tokens per pass: all of them where their LDS stage fits, else pairs, else one (each pass streams the weights again); the
   // weight-only int8 kind has no 4-token build
@@ -473,8 +491,21 @@ extern "C" int llx_gemv_bf16(const void* w0, int64_t ldw0, int64_t n0, const voi
                              void* v_cache, int64_t c_sh, int64_t c_ss, const int64_t* input_pos, const void* bext0, const void* bext1,
                              const void* bext2, int64_t rank0, int64_t rank1, int64_t rank2, const void* t, int64_t ldt, float lora_scale,
                              hipStream_t stream) {
-  return gemv_run("llx_gemv_bf16", WK_BF16, nullptr, nullptr, nullptr, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue, out, ldo, res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sh,
+  return gemv_run("llx_gemv_bf16", WK_BF16, false, nullptr, nullptr, nullptr, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue, out, ldo, res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sh,
                   c_ss, input_pos, bext0, bext1, bext2, rank0, rank1, rank2, t, ldt, lora_scale, stream);
+}
+
+// llx_gemv_bf16 on DoRA linears (modelling/lora.py:51-59) with the row factor c_s = m / ||W_s + s B_s A_s||_row cached by the caller
+// (bf16 [n_s], one per present segment): out = epilogue(bf16(bf16(x . W^T + lora_scale * t . bext[row]) * c[row])) - the rounding points
+// of out * (m / norm) in the bf16 eager graph; gate and up are scaled by their own factors before SwiGLU, q and k before RoPE.
+extern "C" int llx_gemv_bf16_dora(const void* w0, int64_t ldw0, int64_t n0, const void* w1, int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2,
+                                  int64_t n2, const void* x, int64_t ldx, int64_t M, int64_t K, const void* norm_w, float eps, int epilogue,
+                                  void* out, int64_t ldo, const void* res, int64_t ldr, const float* rope, int64_t n_q, int64_t n_k, void* k_cache,
+                                  void* v_cache, int64_t c_sh, int64_t c_ss, const int64_t* input_pos, const void* bext0, const void* bext1,
+                                  const void* bext2, int64_t rank0, int64_t rank1, int64_t rank2, const void* t, int64_t ldt, float lora_scale,
+                                  const void* colscale0, const void* colscale1, const void* colscale2, hipStream_t stream) {
+  return gemv_run("llx_gemv_bf16_dora", WK_BF16, true, colscale0, colscale1, colscale2, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue, out, ldo, res, ldr, rope, n_q, n_k,
+                  k_cache, v_cache, c_sh, c_ss, input_pos, bext0, bext1, bext2, rank0, rank1, rank2, t, ldt, lora_scale, stream);
 }
 
 // The same product on int8 weight rows (subclasses/int8.py:106-121): W_s [n_s, K] int8 row-major (ldw_s in bytes, multiples of 16),
@@ -489,7 +520,7 @@ extern "C" int llx_gemv_i8(const void* w0, int64_t ldw0, int64_t n0, const void*
                            void* v_cache, int64_t c_sh, int64_t c_ss, const int64_t* input_pos, const void* bext0, const void* bext1,
                            const void* bext2, int64_t rank0, int64_t rank1, int64_t rank2, const void* t, int64_t ldt, float lora_scale,
                            const void* scale0, const void* scale1, const void* scale2, int dynamic, hipStream_t stream) {
-  return gemv_run("llx_gemv_i8", dynamic ? WK_I8D : WK_I8W, scale0, scale1, scale2, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue, out, ldo, res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sh,
+  return gemv_run("llx_gemv_i8", dynamic ? WK_I8D : WK_I8W, false, scale0, scale1, scale2, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue, out, ldo, res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sh,
                   c_ss, input_pos, bext0, bext1, bext2, rank0, rank1, rank2, t, ldt, lora_scale, stream);
 }
 

@@ -316,7 +316,7 @@ static int rows16_run(const char* fn, int wk, const void* ws0, const void* ws1, 
                                    n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue, out, ldo, res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sh, c_ss, pos);
   if (rc != LLX_OK) return rc;
   if (wk != WK_BF16) {
-    const int rc1 = stream_check_fill_scales(fn, a, ws0, ws1, ws2, n1, n2);
+    const int rc1 = stream_check_fill_scales(fn, a, "int8", ws0, ws1, ws2, n1, n2);
     if (rc1 != LLX_OK) return rc1;
   }
   LLX_REQUIRE(epilogue != GV_QKV || (n_q > 0 && Smax > 0 && Smax < (1ll << 31) && c_sb % 4 == 0),

@@ -15,7 +15,8 @@ enum { WK_BF16 = 0, WK_I8W = 1, WK_I8D = 2 };
 
 struct StreamArgs {
   const bf16_t* W[3]; int64_t ldw[3]; int seg_end[3];  // output rows [seg_end[s-1], seg_end[s]) come from W[s] (row-major [rows, K])
-  const bf16_t* wscale[3];                              // int8 kinds: per-row scales of W[s] (W[s] then points at int8 rows, ldw in bytes)
+  const bf16_t* wscale[3];                              // int8 kinds: per-row scales of W[s] (W[s] then points at int8 rows, ldw in bytes);
+                                                        // bf16 rows in gemv_kernel: DoRA's per-row factors m / ||W + s B A|| (null: none)
   const bf16_t* x; int64_t ldx;                         // [M, K]
   const bf16_t* norm_w; float eps;                      // NORM: x <- rmsnorm(x) * norm_w, rounded to bf16 (nn.RMSNorm, single rounding)
   int M, N, K;
@@ -132,9 +133,11 @@ static inline int stream_check_fill(const char* fn, StreamArgs& a, int m_lo, int
   return LLX_OK;
 }
 
-// ---- host: the per-row scales of int8 weights (bf16 [n_s]), after stream_check_fill; scales of absent segments repeat segment 0
-static inline int stream_check_fill_scales(const char* fn, StreamArgs& a, const void* ws0, const void* ws1, const void* ws2, int64_t n1, int64_t n2) {
-  LLX_REQUIRE(ws0 && (ws1 || n1 == 0) && (ws2 || n2 == 0), "%s: null scale (every int8 weight needs its per-row scales)", fn);
+// ---- host: the per-row scales of int8 weights, or the per-row DoRA factors of bf16 weights (bf16 [n_s]; what = "int8" | "DoRA"), after
+// stream_check_fill; scales of absent segments repeat segment 0
+static inline int stream_check_fill_scales(const char* fn, StreamArgs& a, const char* what, const void* ws0, const void* ws1, const void* ws2, int64_t n1,
+                                           int64_t n2) {
+  LLX_REQUIRE(ws0 && (ws1 || n1 == 0) && (ws2 || n2 == 0), "%s: null scale (every %s weight needs its per-row scales)", fn, what);
   LLX_REQUIRE(((uintptr_t)ws0 | (uintptr_t)ws1 | (uintptr_t)ws2) % 2 == 0, "%s: scale pointers must be 2-byte aligned", fn);
   a.wscale[0] = (const bf16_t*)ws0; a.wscale[1] = (const bf16_t*)(ws1 ? ws1 : ws0); a.wscale[2] = (const bf16_t*)(ws2 ? ws2 : ws0);
   return LLX_OK;

@@ -39,6 +39,8 @@ SIGNATURES: dict[str, tuple] = {
                               _P, _P, _P, _L, _L, _L, _P, _L, _F, _P]),
     "llx_gemv_i8": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _F, _I, _P, _L, _P, _L, _P, _L, _L, _P, _P, _L, _L, _P,
                             _P, _P, _P, _L, _L, _L, _P, _L, _F, _P, _P, _P, _I, _P]),
+    "llx_gemv_bf16_dora": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _F, _I, _P, _L, _P, _L, _P, _L, _L, _P, _P, _L, _L, _P,
+                                   _P, _P, _P, _L, _L, _L, _P, _L, _F, _P, _P, _P, _P]),
     "llx_mask_extent": (c_int, [_P, _L, _L, _L, _P, _P]),
     "llx_kv_scatter": (c_int, [_P, _P, _L, _L, _L, _P, _P, _L, _L, _L, _P, _L, _L, _L, _L, _L, _P]),
     "llx_kv_scatter_rows": (c_int, [_P, _P, _L, _L, _L, _P, _P, _L, _L, _L, _P, _L, _L, _L, _L, _L, _L, _P]),

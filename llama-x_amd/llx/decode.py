@@ -2,7 +2,8 @@
 
 Reference semantics: the cached branch of Attention.forward (modelling/llama.py:126-127,135-137) inside TransformerLayer.forward
 (:163-174) and the head of Llama.forward (:216) - same values as the generic inference path of modelling/llama.py::_run_dense, which
-stays for every call this path does not take (more than 4 tokens, more than 16 query rows per kv head, biases, DoRA linears).
+stays for every call this path does not take (more than 4 tokens, more than 16 query rows per kv head, biases, adapters of rank
+above 64 or not a multiple of 8, a fused group that mixes DoRA and other members, DoRA on an int8 weight).
 Int8LinearWeight linears (weight-only or dynamic, subclasses/int8.py:106-121) stream their int8 rows (llx_gemv_i8): no bf16 image of
 the matrix is built or read.
 
@@ -19,6 +20,12 @@ Per layer (M <= 4 tokens at batch 1):
     h            = silu(gemv(w1, rmsnorm(x))) * gemv(w3, rmsnorm(x))                                       1 launch
     x            = x + gemv(w2, h)                                                                         1 launch
 LoRA-dressed linears (modelling/lora.py:43) add one small launch per group for t = x @ A^T; the B factors ride in the main launch.
+DoRA linears (modelling/lora.py:51-59, bf16 weights) are LoRA linears whose bf16 output is multiplied by c = m / ||W + s B A||_row
+in the same launch (llx_gemv_bf16_dora).  c depends on parameters only: ops.dora_scale_cached keeps it per linear (2 bytes per
+output row, rebuilt when weight, lora_a, lora_b or m change), so a token costs a DoRA model the launches and the one weight pass
+of a LoRA model.  The factor is built at a linear's first use: prepare(model) builds them all up front, which a caller that
+captures a decode step into a graph must do (or run one warm-up step) before the capture - a tensor first allocated while
+capturing lives in the capture's private pool.  generate() calls prepare().
 """
 from __future__ import annotations
 
@@ -41,13 +48,17 @@ KIND_BF16, KIND_I8W, KIND_I8D = "bf16", "int8-weight-only", "int8-dynamic"
 
 def _plain(m: nn.Linear) -> Optional[str]:
     """The kind of a linear this path streams, or None: bf16 weight or Int8LinearWeight (bf16 scale; weight-only or dynamic), no bias,
-    optionally a LoRA adapter (rank a multiple of 8)."""
+    optionally a LoRA adapter (rank a multiple of 8), or - bf16 weights only - a DoRA adapter (rank a multiple of 8 up to 64, the
+    ranks dora_scale_cached builds; bf16 factors and magnitude vector)."""
     from subclasses.int8 import Int8LinearWeight
 
-    if m.bias is not None or m.weight.dtype is not BF16 or getattr(m, "m", None) is not None:
+    if m.bias is not None or m.weight.dtype is not BF16:
         return None
     rank = int(getattr(m, "rank", 0) or 0)
     if not (rank == 0 or (rank % 8 == 0 and m.lora_a.dtype is BF16)):
+        return None
+    if _dora(m) and not (rank <= 64 and m.lora_b.dtype is BF16 and m.m.dtype is BF16 and tuple(m.m.shape) == (m.out_features,)
+                         and not isinstance(m.weight, Int8LinearWeight)):
         return None
     if isinstance(m.weight, Int8LinearWeight):
         if m.weight.scale.dtype is not BF16 or m.in_features % 16 != 0:
@@ -56,9 +67,17 @@ def _plain(m: nn.Linear) -> Optional[str]:
     return KIND_BF16
 
 
+def _dora(m: nn.Linear) -> bool:
+    """A DoRALinear with an adapter (modelling/lora.py:51: rank 0 attaches no magnitude vector)."""
+    return int(getattr(m, "rank", 0) or 0) > 0 and getattr(m, "m", None) is not None
+
+
 def _w(mods) -> dict:
-    """The weight operands of one gemv call: (ws, wscale, dynamic) of a group of linears of one kind."""
+    """The weight operands of one gemv call: (ws, wscale, dynamic) of a group of linears of one kind; bf16 DoRA members add their cached
+    row factors (colscale)."""
     if _plain(mods[0]) == KIND_BF16:
+        if _dora(mods[0]):  # (layer_ok: all members or none)
+            return dict(ws=[m.weight.detach() for m in mods], colscale=[ops.dora_scale_cached(m) for m in mods])
         return dict(ws=[m.weight.detach() for m in mods])
     return dict(ws=[m.weight.int_data for m in mods], wscale=[m.weight.scale for m in mods], dynamic=bool(mods[0].weight.dynamic_int8_act))
 
@@ -88,9 +107,11 @@ def layer_ok(layer, x: Tensor, mask: Optional[Tensor]) -> bool:
                 and G <= 16 and all(_batch_group(g) for g in ((att.wq, att.wk, att.wv), (att.wo,), (ff.w1, ff.w3), (ff.w2,))))
     if x.shape[0] != 1 or x.shape[1] > MAX_TOKENS or x.shape[1] * G > 16 or not all(_plain(m) is not None for m in lins):
         return False
-    for grp in ((att.wq, att.wk, att.wv), (ff.w1, ff.w3)):  # one t vector, one scale and one weight kind per fused group
+    for grp in ((att.wq, att.wk, att.wv), (ff.w1, ff.w3)):  # one t vector, one scale and one weight kind per fused group, all DoRA or none
         ranks = {int(getattr(m, "rank", 0) or 0) > 0 for m in grp}
         if len(ranks) != 1 or len({float(getattr(m, "scale", 1.0)) for m in grp}) != 1 or len({_plain(m) for m in grp}) != 1:
+            return False
+        if len({_dora(m) for m in grp}) != 1:
             return False
     return att.wq.out_features % 4 == 0 and att.wk.out_features % 4 == 0
 
@@ -140,6 +161,17 @@ def layer_forward(layer, x: Tensor, rope: Tensor, mask: Tensor, input_pos: Tenso
     h = lin((ff.w1, ff.w3), x1, norm=(layer.ffn_norm.weight.detach(), layer.ffn_norm.eps), epilogue=K.GV_SWIGLU)
     x3 = lin((ff.w2,), h, epilogue=K.GV_RESIDUAL, res=x1)
     return x3.view(x.shape)
+
+
+def prepare(model):
+    """Build the cached row factor of every DoRA linear of `model` that the decode path streams (a no-op for other models) and return
+    the model.  Call it - or run one warm-up step - before capturing a decode step into a graph: built lazily, the first factors would
+    be allocated inside the capture and live in its private pool."""
+    with torch.no_grad():
+        for m in model.modules():
+            if isinstance(m, nn.Linear) and _dora(m) and m.weight.is_cuda and _plain(m) is not None:
+                ops.dora_scale_cached(m)
+    return model
 
 
 def head_ok(model, x: Tensor) -> bool:

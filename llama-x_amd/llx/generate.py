@@ -12,6 +12,7 @@ from typing import Optional, Sequence
 import torch
 from torch import Tensor
 
+from . import decode as D
 from . import kernels as K
 from ._lib import LlxError
 from .sampling import check_params
@@ -146,7 +147,9 @@ def generate(model, prompt: Tensor, max_new_tokens: int, *, temperature: float =
     launch): the rows of `prompt` are right-padded prompts of these lengths; default: every row is P long.  For a batch the result is as
     wide as the longest row; with `eos_id` a row that ended earlier is padded with `eos_id`, and the loop stops when every row has
     ended.  The draw also takes the row index, and row r does not depend on what the other rows hold.  The decode steps of 2..16 sequences
-    with bf16 un-adapted linears stream every weight once for the whole batch (llx/decode.py); anything else runs the generic path.
+    with bf16 or dynamic-int8 un-adapted linears stream every weight once for the whole batch (llx/decode.py); a single sequence streams
+    bf16 and int8 linears with or without LoRA, and bf16 DoRA linears through their cached row factors (decode.prepare builds them here,
+    before the prefill); anything else runs the generic path.
 
     The draw for the token at absolute position q uses the counter q - 1 (the position of the logits row it is sampled from), so the
     same arguments give the same tokens whatever `prefill_chunk` and `check_every` are.  With `eos_id` the result ends at the first
@@ -159,6 +162,7 @@ def generate(model, prompt: Tensor, max_new_tokens: int, *, temperature: float =
     on an exception): do not drive the same model from another thread meanwhile."""
     check_params(temperature, top_k, top_p, seed)
     lens = _check(model, prompt, max_new_tokens, eos_id, prefill_chunk, check_every, prompt_lens)
+    D.prepare(model)
     dev, P, n = prompt.device, prompt.shape[1], max_new_tokens
     if prompt.shape[0] > 1 or (lens is not None and lens != [P]):
         return _generate_batch(model, prompt, n, lens if lens is not None else [P] * prompt.shape[0],

@@ -887,13 +887,21 @@ def _stream_operands(ws, x: Tensor, norm, epilogue: int, out: Optional[Tensor], 
 
 def gemv(ws: Sequence[Tensor], x: Tensor, *, norm: Optional[tuple[Tensor, float]] = None, epilogue: int = GV_NONE, out: Optional[Tensor] = None,
          res: Optional[Tensor] = None, qkv: Optional[tuple] = None, lora: Optional[tuple] = None, wscale: Optional[Sequence[Tensor]] = None,
-         dynamic: bool = False) -> Tensor:
+         dynamic: bool = False, colscale: Optional[Sequence[Tensor]] = None) -> Tensor:
     """out = epilogue([rmsnorm(x) | x] @ cat(ws)^T) for M = x.shape[0] <= 4 rows: every CU streams weight rows (llx_gemv_bf16).
     ws: 1-3 weights [n_s, K]; norm = (weight, eps); res [M, N] for GV_RESIDUAL; qkv = (rope_table, n_q, n_k, k_cache, v_cache, input_pos)
     for GV_QKV (caches [1, KVH, Smax, 128]; returns q [M, n_q]); GV_SWIGLU returns h [M, n_0]; lora = (b factors, t [M, sum r], scale).
     int8 ws (the int_data of Int8LinearWeights, all members of the call) with wscale = their bf16 per-row scales run llx_gemv_i8:
-    weight-only arithmetic, or with dynamic=True the rows of x quantised on chip and integer dot products (subclasses/int8.py:106-121)."""
+    weight-only arithmetic, or with dynamic=True the rows of x quantised on chip and integer dot products (subclasses/int8.py:106-121).
+    colscale (bf16 weights only): one contiguous bf16 [n_s] factor per weight, DoRA's cached m / ||W + s B A||_row (ops.dora_scale_cached);
+    the linear's bf16 output is multiplied by it and rounded before the epilogue (llx_gemv_bf16_dora)."""
     i8 = [w.dtype is torch.int8 for w in ws]
+    if colscale is not None:
+        if any(i8):
+            raise L.LlxError("gemv: colscale (DoRA) on int8 weights is not supported")
+        if len(colscale) != len(ws) or not all(c.dtype is BF16 and c.shape == (w.shape[0],) and c.is_contiguous() for c, w in zip(colscale, ws)):
+            raise L.LlxError("gemv: colscale must hold one contiguous bf16 [n_s] tensor per weight")
+        L.require_cuda(*colscale)
     if any(i8):
         if not all(i8):
             raise L.LlxError("gemv: bf16 and int8 weights in one call (all members of a fused group must be of one kind)")
@@ -921,6 +929,9 @@ def gemv(ws: Sequence[Tensor], x: Tensor, *, norm: Optional[tuple[Tensor, float]
     if any(i8):
         sp = [L.ptr(sc) for sc in wscale] + [None] * (3 - len(ws))
         L.check(_lib().llx_gemv_i8(*args, sp[0], sp[1], sp[2], int(bool(dynamic)), L.stream()), "llx_gemv_i8")
+    elif colscale is not None:
+        cp = [L.ptr(c) for c in colscale] + [None] * (3 - len(ws))
+        L.check(_lib().llx_gemv_bf16_dora(*args, cp[0], cp[1], cp[2], L.stream()), "llx_gemv_bf16_dora")
     else:
         L.check(_lib().llx_gemv_bf16(*args, L.stream()), "llx_gemv_bf16")
     return out

@@ -75,6 +75,7 @@ class LinearPlan:
         self.dora_m = getattr(m, "m", None) if self.rank > 0 else None  # DoRALinear's magnitude vector (modelling/lora.py:51)
         self.int8 = isinstance(self.weight, Int8LinearWeight)
         self.dynamic = bool(self.int8 and self.weight.dynamic_int8_act)
+        self.no_grad = False  # set by linear(): the call runs with grad disabled
         if self.dora_m is not None and self.int8:
             # the reference cannot run this combination either: (weight + delta).norm() has no Int8LinearWeight dispatch (subclasses/int8.py:102)
             raise LlxError("DoRA on an Int8LinearWeight is not supported (nor by the reference: no dispatch for weight + delta)")
@@ -98,7 +99,8 @@ class LinearPlan:
 
     # ---- forward: y = linear(x) [+ residual]; returns (y, saved) where saved is the LoRA intermediate t = x @ A^T
     # (DoRA: the tuple (t, z, c, inv_norm) - un-scaled output, column scale m / ||W + sBA||, 1 / norm)
-    def forward(self, x: Tensor, out: Optional[Tensor] = None, residual: Optional[Tensor] = None, gelu: bool = False):
+    # cached_scale: no backward will follow (the caller's inputs need no gradient): DoRA's c comes from dora_scale_cached, inv_norm is not made
+    def forward(self, x: Tensor, out: Optional[Tensor] = None, residual: Optional[Tensor] = None, gelu: bool = False, cached_scale: bool = False):
         t = b2 = None
         if self.rank > 0:
             t = K.skinny_nt(x, self.lora_a.detach())
@@ -107,7 +109,7 @@ class LinearPlan:
             if gelu:
                 raise LlxError("DoRA + GELU epilogue is not supported")
             w = self.weight.detach()
-            c, inv = dora_colscale([self], w, self.lora_a.detach(), b2)
+            c, inv = (dora_scale_cached(self), None) if cached_scale else dora_colscale([self], w, self.lora_a.detach(), b2)
             z = K.gemm_nt(x, w, a2=t, b2=b2, k2_eff=self.rank)
             direct = residual is None
             y = K.colscale_bias(z, c, self.bias.detach() if self.bias is not None else None, out=out if direct else None)
@@ -192,12 +194,12 @@ class LinearPlan:
         return dx, grads
 
 
-def dora_colscale(members: Sequence[LinearPlan], w_cat: Tensor, a_cat: Tensor, b2: Tensor) -> tuple[Tensor, Tensor]:
+def dora_colscale(members: Sequence[LinearPlan], w_cat: Tensor, a_cat: Tensor, b2: Tensor, wn2_tag: str = "wn2") -> tuple[Tensor, Tensor]:
     """DoRA's per-output-row factor for one linear or a fused group (modelling/lora.py:55-59, norm detached from A and B):
     c [N] bf16 = m / ||W + s B A||_row and inv_norm [N] fp32, from ||W_n||^2 (cached with the frozen weight), G = W A^T and A A^T -
     W is read once by the skinny MFMA kernel, no [out, in] temporary is formed.  b2 = the [N, 64] image of s * B (block diagonal)."""
     N, R = w_cat.shape[0], a_cat.shape[0]
-    wn2 = _cached_multi([m.weight for m in members], "wn2", lambda: K.rownorm2(w_cat))
+    wn2 = _cached_multi([m.weight for m in members], wn2_tag, lambda: K.rownorm2(w_cat))
     G = K.skinny_nt(w_cat, a_cat)
     AAt = K.skinny_nt(a_cat, a_cat)
     c = torch.empty(N, device=w_cat.device, dtype=BF16)
@@ -208,6 +210,27 @@ def dora_colscale(members: Sequence[LinearPlan], w_cat: Tensor, a_cat: Tensor, b
         K.dora_colscale(wn2[sl], G[sl], b2[sl], AAt, m.dora_m.detach(), c[sl], inv[sl], R)
         off += m.N
     return c, inv
+
+
+def dora_scale_cached(m) -> Tensor:
+    """c [out_features] bf16 = m / ||W + s B A||_row of ONE DoRA linear (an nn.Linear dressed by modelling/lora.py, or its LinearPlan),
+    built once by dora_colscale and kept on the weight: the factor depends on parameters only, so a forward that no backward follows
+    (decode, prefill, eval loss) need not read W a second time per call.  Per member, never from a concatenated image: the decode path
+    keeps no second copy of a weight.  Next to it stays ||W_n||^2 (fp32, tag "wn2m"): 6 bytes per output row in all.
+
+    The cache key is the version counter and device of weight, lora_a, lora_b and m: an optimizer step, load_state_dict, any in-place
+    update under no_grad or a move of one of them rebuilds it.  What the key cannot see - as for the "wn2" and "wt" images: a write
+    through .data (or any other write that bypasses the version counter) leaves a stale factor; bump the version (p.add_(0) under
+    no_grad) or drop p._llx_cache after such a write."""
+    plan = m if isinstance(m, LinearPlan) else None
+    mag = plan.dora_m if plan is not None else m.m
+
+    def build():
+        p = plan if plan is not None else LinearPlan(m)
+        c, _ = dora_colscale([p], p.weight.detach(), p.lora_a.detach(), K.pad64(p.lora_b.detach(), p.scale), wn2_tag="wn2m")
+        return c
+
+    return _cached_multi([m.weight, m.lora_a, m.lora_b, mag], "dora_c", build)
 
 
 class GroupPlan:
@@ -265,15 +288,24 @@ class GroupPlan:
         ss = [m.weight.scale for m in self.members]
         return _cached_multi(ss, "cat_scale", lambda: torch.cat(ss, 0) if len(ss) > 1 else ss[0])
 
+    def dora_scale_cached(self) -> Tensor:
+        """c [sum N] of a fused DoRA group: the members' cached factors side by side (each built from its own weight)."""
+        if len(self.members) == 1:
+            return dora_scale_cached(self.members[0])
+        srcs = [t for m in self.members for t in (m.weight, m.lora_a, m.lora_b, m.dora_m)]
+        return _cached_multi(srcs, "dora_c_cat", lambda: torch.cat([dora_scale_cached(m) for m in self.members], 0))
+
     # ---- forward
     def forward(self, x: Tensor, out: Optional[Tensor] = None, residual: Optional[Tensor] = None, swiglu_h: Optional[Tensor] = None,
-                rope: Optional[tuple[Tensor, int, int]] = None, xq: Optional[tuple[Tensor, Tensor]] = None, t_pre: Optional[Tensor] = None):
+                rope: Optional[tuple[Tensor, int, int]] = None, xq: Optional[tuple[Tensor, Tensor]] = None, t_pre: Optional[Tensor] = None,
+                cached_scale: bool = False):
         """out: [M, sum N] (row-strided view allowed; allocated when None).  ``residual`` [M, sum N] is added in the GEMM
         epilogue (x + linear(..), modelling/llama.py:172-173).  xq = quantize_int8_rowwise(x) / t_pre = x @ A_cat^T when the producer of
-        x already made them (the RMSNorm forward).  Returns (out, saved) - saved feeds backward()."""
+        x already made them (the RMSNorm forward).  cached_scale: no backward will follow - DoRA members take their factors from
+        dora_scale_cached and `saved` is not fit for backward().  Returns (out, saved) - saved feeds backward()."""
         if out is None:
             out = torch.empty(x.shape[0], self.N, device=x.device, dtype=BF16)
-        return out, self._forward(x, out, residual, swiglu_h, rope, xq, t_pre)
+        return out, self._forward(x, out, residual, swiglu_h, rope, xq, t_pre, cached_scale)
 
     def norm_can_make_t(self, dim: int) -> bool:
         """The preceding RMSNorm can emit t = xn @ A_cat^T itself: the operand images exist already (prepack) and the width fits."""
@@ -292,10 +324,12 @@ class GroupPlan:
         return self.fused and (not self.int8 or self.dynamic) and not self.dora and len(self.members) == 2 and self.Ns[0] % 128 == 0
 
     def _forward(self, x: Tensor, out: Tensor, residual: Optional[Tensor], swiglu_h: Optional[Tensor] = None,
-                 rope: Optional[tuple[Tensor, int, int]] = None, xq: Optional[tuple[Tensor, Tensor]] = None, t_pre: Optional[Tensor] = None):
+                 rope: Optional[tuple[Tensor, int, int]] = None, xq: Optional[tuple[Tensor, Tensor]] = None, t_pre: Optional[Tensor] = None,
+                 cached_scale: bool = False):
         if not self.fused:
             assert residual is None or len(self.members) == 1
-            return [m.forward(x, out=out[:, o : o + n], residual=residual)[1] for m, o, n in zip(self.members, self.n_off, self.Ns)]
+            return [m.forward(x, out=out[:, o : o + n], residual=residual, cached_scale=cached_scale)[1]
+                    for m, o, n in zip(self.members, self.n_off, self.Ns)]
         t = b2 = None
         if self.R > 0:
             # the four operand images (forward: a_cat, b2; backward: bT, a2t) come out of one launch and ride along in `saved`
@@ -306,7 +340,7 @@ class GroupPlan:
             # DoRA members: the un-scaled product z is kept for d m; rescale (and residual) are their own HBM-bound passes, so RoPE /
             # SwiGLU run stand-alone after this group (rope_fusable / swiglu_fusable are False)
             assert swiglu_h is None and rope is None
-            c, inv = dora_colscale(self.members, self.w_cat(), a_cat, b2)
+            c, inv = (self.dora_scale_cached(), None) if cached_scale else dora_colscale(self.members, self.w_cat(), a_cat, b2)
             z = K.gemm_nt(x, self.w_cat(), a2=t[0], b2=b2, k2_eff=self.k2_fwd)
             K.scale(z, colscale=c, out=out)
             if residual is not None:
@@ -592,7 +626,7 @@ class LinearFn(Function):
     def forward(ctx, x: Tensor, plan: LinearPlan, *tensors):
         K.L.require_cuda(x)
         x2 = K._rows2d(x)
-        y, t = plan.forward(x2)
+        y, t = plan.forward(x2, cached_scale=plan.no_grad or not any(ctx.needs_input_grad))
         ctx.plan = plan
         _save(ctx, x2, t)
         ctx.xshape = x.shape
@@ -610,6 +644,7 @@ class LinearFn(Function):
 
 def linear(x: Tensor, m: nn.Linear) -> Tensor:
     plan = LinearPlan(m)
+    plan.no_grad = not torch.is_grad_enabled()  # (inside Function.forward grad mode is always off: noted here)
     return LinearFn.apply(x, plan, *plan.tensors())
 
 
@@ -679,6 +714,7 @@ class AttnBlockMeta:
         self.mask, self.eps = mask, eps
         self.fuse_norm, self.fuse_residual = fuse_norm, fuse_residual
         self.dropout = dropout  # (threshold, stream_id) or None; the ticket travels as a tensor argument of AttnBlockFn
+        self.no_grad = not torch.is_grad_enabled()  # the caller's grad mode (inside Function.forward it is always off)
 
 
 class AttnBlockFn(Function):
@@ -692,7 +728,8 @@ class AttnBlockFn(Function):
         W = (H + 2 * KVH) * hd
         qkv = torch.empty(B * S, W, device=x.device, dtype=BF16)
         fuse_rope = meta.qkv.rope_fusable()
-        _, tqkv = meta.qkv.forward(xn, qkv, rope=(rope, S, (H + KVH) * hd) if fuse_rope else None, xq=xq, t_pre=t_pre)
+        infer = meta.no_grad or not any(ctx.needs_input_grad)  # no backward follows: DoRA groups take their cached row factors
+        _, tqkv = meta.qkv.forward(xn, qkv, rope=(rope, S, (H + KVH) * hd) if fuse_rope else None, xq=xq, t_pre=t_pre, cached_scale=infer)
         qkv3 = qkv.view(B, S, W)
         if not fuse_rope:
             K.rope_(qkv3, rope, H + KVH)
@@ -701,7 +738,7 @@ class AttnBlockFn(Function):
         v = qkv3[..., (H + KVH) * hd :].unflatten(-1, (KVH, hd))
         o, lse = K.attn_fwd(q, k, v, meta.mask, dropout=(meta.dropout[0], ticket, meta.dropout[1]) if meta.dropout else None)
         o2 = o.view(B * S, H * hd)
-        y, to = meta.wo.forward(o2, None, x2 if meta.fuse_residual else None)
+        y, to = meta.wo.forward(o2, None, x2 if meta.fuse_residual else None, cached_scale=infer)
         ctx.meta = meta
         # x2 is x itself (or its contiguous copy) and xn == x2 without the fused norm: saved once, by identity, below
         _save(ctx, x, rope, norm_w, x2, xn if meta.fuse_norm else None, rstd, qkv3, o, lse, tqkv, to, ticket if meta.dropout else None)
@@ -760,6 +797,7 @@ class MLPBlockMeta:
     def __init__(self, w13: GroupPlan, w2: GroupPlan, eps, fuse_norm, fuse_residual):
         self.w13, self.w2 = w13, w2
         self.eps, self.fuse_norm, self.fuse_residual = eps, fuse_norm, fuse_residual
+        self.no_grad = not torch.is_grad_enabled()  # the caller's grad mode (inside Function.forward it is always off)
 
 
 class MLPBlockFn(Function):
@@ -771,13 +809,14 @@ class MLPBlockFn(Function):
         xn, rstd, xq, t_pre = _norm_prologue(meta, meta.w13, x2, norm_w)
         T, I = x2.shape[0], meta.w13.Ns[0]
         gu = torch.empty(T, 2 * I, device=x.device, dtype=BF16)
+        infer = meta.no_grad or not any(ctx.needs_input_grad)  # no backward follows: DoRA groups take their cached row factors
         if meta.w13.swiglu_fusable():
             h = torch.empty(T, I, device=x.device, dtype=BF16)
-            _, t13 = meta.w13.forward(xn, gu, swiglu_h=h, xq=xq, t_pre=t_pre)  # SwiGLU in the epilogue of the gate|up GEMM
+            _, t13 = meta.w13.forward(xn, gu, swiglu_h=h, xq=xq, t_pre=t_pre, cached_scale=infer)  # SwiGLU in the epilogue of the gate|up GEMM
         else:
-            _, t13 = meta.w13.forward(xn, gu, xq=xq, t_pre=t_pre)
+            _, t13 = meta.w13.forward(xn, gu, xq=xq, t_pre=t_pre, cached_scale=infer)
             h = K.swiglu_fwd(gu[:, :I], gu[:, I:])
-        y, t2 = meta.w2.forward(h, None, x2 if meta.fuse_residual else None)
+        y, t2 = meta.w2.forward(h, None, x2 if meta.fuse_residual else None, cached_scale=infer)
         ctx.meta = meta
         _save(ctx, x, norm_w, x2, xn if meta.fuse_norm else None, rstd, gu, h, t13, t2)
         return y.view(shape)

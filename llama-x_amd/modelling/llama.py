@@ -232,7 +232,7 @@ class Attention(nn.Module):
         xn = norm(x) if norm is not None else x
         x2 = K._rows2d(xn.contiguous())
         qkv = torch.empty(B * L_, (H + 2 * KVH) * hd, device=x.device, dtype=x.dtype)
-        ops.GroupPlan((self.wq, self.wk, self.wv)).forward(x2, qkv)
+        ops.GroupPlan((self.wq, self.wk, self.wv)).forward(x2, qkv, cached_scale=True)  # forward-only: DoRA's row factors come from their cache
         qkv3 = qkv.view(B, L_, -1)
         K.rope_(qkv3, _rope_f32(rope).contiguous(), H + KVH)
         q = qkv3[..., : H * hd].unflatten(-1, (H, hd)).transpose(1, 2)
@@ -252,7 +252,7 @@ class Attention(nn.Module):
             o2 = K.attn_mask_fwd(q, k, v, mask).view(B * L_, H * hd)
         else:  # per-head masks
             o2 = K.attn_dense_fwd(q, k, v, mask).transpose(1, 2).reshape(B * L_, H * hd)  # [B,H,L,hd] -> rows
-        y, _ = ops.GroupPlan((self.wo,)).forward(o2, None, K._rows2d(x.contiguous()) if residual else None)
+        y, _ = ops.GroupPlan((self.wo,)).forward(o2, None, K._rows2d(x.contiguous()) if residual else None, cached_scale=True)
         return y.view(B, L_, -1)
 
     def forward(self, x: Tensor, rope: Tensor, *, mask: Tensor | None = None, input_pos: Tensor | None = None,
