@@ -261,6 +261,28 @@ int llx_gemm_rows16_i8(const void* w0, int64_t ldw0, int64_t n0, const void* w1,
                        const void* res, int64_t ldr, const float* rope, int64_t n_q, int64_t n_k, void* k_cache, void* v_cache, int64_t c_sb,
                        int64_t c_sh, int64_t c_ss, int64_t Smax, const int64_t* pos, void* workspace, int64_t workspace_bytes,
                        const void* scale0, const void* scale1, const void* scale2, llx_stream_t s);
+/* The two products above on LoRA / DoRA linears (modelling/lora.py:43,51-59), the leading arguments unchanged.  bext_s: bf16
+ * [n_s, rank_s] row-major, one for every present weight (and none for an absent one), 16-byte aligned; rank_s a multiple of 16, at most
+ * 64; t: bf16 [M, sum rank] = [rmsnorm(x) | x] . [A_0; A_1; A_2]^T from a call of llx_gemm_rows16_bf16 on the A factors, 16-byte
+ * aligned, ldt % 8 == 0.  The adapter term of a finished 16 x 16 tile is a short v_mfma_f32_16x16x32_bf16 chain where the tile's
+ * epilogue runs (main launch, or the combine launch of a split K); workspaces as the un-adapted entry points.  Rounding points of
+ * llx_gemv_bf16 / llx_gemv_bf16_dora / llx_gemv_i8(dynamic = 1):
+ *   bf16 rows:  v = bf16(acc + lora_scale * t_s . bext_s[row]); colscale_s (bf16 [n_s], DoRA's cached row factors; for every present
+ *               segment or for none): v = bf16(v * colscale_s[row]);
+ *   int8 rows:  v = bf16(bf16(((float)acc * x_scale[m]) * scale[row]) + lora_scale * t_s . bext_s[row]);
+ * then the epilogue.  Bad ranks, a weight without its factor (or the reverse), a null t and partial colscale are LLX_ERR_ARG. */
+int llx_gemm_rows16_bf16_lora(const void* w0, int64_t ldw0, int64_t n0, const void* w1, int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2,
+                              int64_t n2, const void* x, int64_t ldx, int64_t M, int64_t K, const void* norm_w, float eps, int epilogue, void* out,
+                              int64_t ldo, const void* res, int64_t ldr, const float* rope, int64_t n_q, int64_t n_k, void* k_cache, void* v_cache,
+                              int64_t c_sb, int64_t c_sh, int64_t c_ss, int64_t Smax, const int64_t* pos, void* workspace, int64_t workspace_bytes,
+                              const void* bext0, const void* bext1, const void* bext2, int64_t rank0, int64_t rank1, int64_t rank2, const void* t,
+                              int64_t ldt, float lora_scale, const void* colscale0, const void* colscale1, const void* colscale2, llx_stream_t s);
+int llx_gemm_rows16_i8_lora(const void* w0, int64_t ldw0, int64_t n0, const void* w1, int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2,
+                            int64_t n2, const void* x, int64_t ldx, int64_t M, int64_t K, const void* norm_w, float eps, int epilogue, void* out,
+                            int64_t ldo, const void* res, int64_t ldr, const float* rope, int64_t n_q, int64_t n_k, void* k_cache, void* v_cache,
+                            int64_t c_sb, int64_t c_sh, int64_t c_ss, int64_t Smax, const int64_t* pos, void* workspace, int64_t workspace_bytes,
+                            const void* scale0, const void* scale1, const void* scale2, const void* bext0, const void* bext1, const void* bext2,
+                            int64_t rank0, int64_t rank1, int64_t rank2, const void* t, int64_t ldt, float lora_scale, llx_stream_t s);
 /* SDPA(q, k_cache, v_cache, mask, is_causal=False, enable_gqa=True) (:135-137) for M query tokens with M * H / KVH <= 16: the cache of a
  * kv head is split over `nsplit` workgroups, the heads of its group share every K / V row read; partials merged in a second launch.
  * q / o [B, H, M, 128], caches [B, KVH, Skv, 128] through (batch, head, position) strides; mask bool [.., M, Skv] with broadcast

@@ -27,6 +27,12 @@
 // are exact in any order; a finished sum is dequantised as the reference does, bf16(((float)acc * x_scale[m]) * w_scale[row]), and
 // then takes the same epilogue.  Split K: the partial tiles are int32, and the M activation-row scales travel to the combine launch
 // in a 16-float header of the workspace (every workgroup computes identical bits; workgroup 0 stores them).
+//
+// LoRA / DoRA linears (AD_LORA / AD_DORA, instances of their own: the un-adapted builds keep their argument block and registers): the
+// adapter term l = t . Bext[row] of a finished tile (t = x . A^T from a previous launch of this stream on the A factors) is a chain of
+// one to four more v_mfma_f32_16x16x32_bf16 in the accumulator layout, rows16_adapter, run where the tile's epilogue runs - finish
+// (S == 1) or the combine launch - with the GEMV's rounding points (decode.hip, finish): bf16 rows v = bf16(acc + scale * l), DoRA then
+// v = bf16(v * c[row]) with the cached factors in wscale, dynamic int8 v = bf16(bf16((acc * xscale) * wscale) + scale * l).
 #include "wstream.h"
 #include <type_traits>
 
@@ -37,6 +43,22 @@ struct Rows16Args : StreamArgs {
   float* xscale;           // WK_I8D, S > 1: [16] the activation rows' scales for the combine launch (the workspace's header)
 };
 
+// adapters of the batched stream: none | LoRA (bf16 or dynamic int8 rows) | DoRA (bf16 rows; the cached row factors in wscale)
+enum { AD_NONE = 0, AD_LORA = 1, AD_DORA = 2 };
+// LoRA (modelling/lora.py:43): bext[s] [n_s, rank[s]] row-major, t [M, sum rank] with the ranks of segment s at t_off[s]; ranks are
+// multiples of 16 up to 64 (the t product's segments are 16-row tiles of this stream)
+struct Rows16LoraArgs : Rows16Args {
+  const bf16_t* bext[3]; int rank[3]; int t_off[3];
+  const bf16_t* t; int64_t ldt; float lora_scale;
+};
+// the argument block of an instance.  (A trait, not std::conditional_t<AD == AD_NONE, ..>: this type is part of the kernels' signatures,
+// and an expression on an unnamed enum is mangled with the enum's per-compilation number, which differs between the host and the
+// device pass - the host then registers a kernel name the code object does not have.)
+template <int AD> struct rows16_args { using type = Rows16LoraArgs; };
+template <> struct rows16_args<0> { using type = Rows16Args; };
+template <int AD>
+using rows16_args_t = typename rows16_args<AD>::type;
+
 // element offset inside a batch (32 chunks of EPL elements = 16 bytes: 256 bf16 or 512 int8 elements) of the chunk that lane group q
 // (= lane / 16) takes with load j of the batch: a lane's loads 2i and 2i+1 are adjacent (32 contiguous bytes per lane), so one
 // wave-instruction touches the whole 128-byte line of each of its 16 rows and the next one hits the same lines.  (The fragment's
@@ -44,19 +66,54 @@ struct Rows16Args : StreamArgs {
 template <int EPL>
 __device__ __forceinline__ int chunk_k(int j, int q) { return ((j >> 1) * 8 + q * 2 + (j & 1)) * EPL; }
 
+// The adapter term of one 16 x 16 tile in the accumulator layout: lane (q, m) gets l[e] = sum_r Bext[row 4q + e][r] * t[m][r].  A
+// operand: the tile's 16 rows of the B factor (lane = row lane % 16, clamped as row_ptr clamps the weight row; ranks 8q .. 8q + 7 of
+// chunk j), B operand: t[m][t_off + 32 j + 8 q ..].  Lanes whose rank chunk lies outside their row's ranks and columns m >= M hold
+// zeros in registers and load nothing.  SwiGLU: the tile interleaves gate and up rows, which multiply different slices of t - the
+// chain runs over the concatenated ranks [t_gate | t_up] (t_off = 0, rank_0), a gate row is zero over the up part and an up row over
+// the gate part.  Rank 16 fills half a chunk, 48 one and a half; the chunk test is wave-uniform.
+template <int EPI>
+__device__ __forceinline__ f32x4_t rows16_adapter(const Rows16LoraArgs& a, int tile, int lane) {
+  const int q = lane >> 4, r = lane & 15;
+  const bf16_t* bp;   // this lane's row of its B factor
+  int lo, rk, R, tb;  // the row's ranks are [lo, lo + rk) of the R ranks of the chain, which start at t column tb
+  if constexpr (EPI == GV_SWIGLU) {
+    const int mat = (r >> 1) & 1, unit = min(8 * tile + 2 * (r >> 2) + (r & 1), a.N / 2 - 1);
+    rk = a.rank[mat]; lo = mat ? a.rank[0] : 0; R = a.rank[0] + a.rank[1]; tb = 0;
+    bp = a.bext[mat] + (int64_t)unit * rk;
+  } else {
+    const int n0 = 16 * tile;
+    const int seg = n0 >= a.seg_end[0] ? (n0 >= a.seg_end[1] ? 2 : 1) : 0;
+    const int base = seg == 0 ? 0 : a.seg_end[seg - 1];
+    rk = a.rank[seg]; lo = 0; R = rk; tb = a.t_off[seg];
+    bp = a.bext[seg] + (int64_t)min(n0 - base + r, a.seg_end[seg] - 1 - base) * rk;
+  }
+  const bf16_t* tp = a.t + (int64_t)r * a.ldt + tb;  // (column m = r; only read for m < M)
+  f32x4_t l = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < (EPI == GV_SWIGLU ? 4 : 2); ++j) {
+    if (32 * j < R) {
+      const int kk = 32 * j + 8 * q;
+      u32x4_t bv = {0u, 0u, 0u, 0u}, tv = {0u, 0u, 0u, 0u};
+      if (kk >= lo && kk < lo + rk) bv = *reinterpret_cast<const u32x4_t*>(bp + (kk - lo));
+      if (r < a.M && kk < R) tv = *reinterpret_cast<const u32x4_t*>(tp + kk);
+      l = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, bv), __builtin_bit_cast(bf16x8_t, tv), l, 0, 0, 0);
+    }
+  }
+  return l;
+}
+
 // The epilogue of one finished 16 x 16 tile: lane (q = lane / 16, m = lane % 16) holds output features 4q .. 4q+3 of sequence m (SwiGLU:
-// gate and up of hidden units 8 tile + 2q, + 1).  WK_I8D: acc = the int32 sums, xscale = the scale of activation row m.
-template <int EPI, int WK, class Acc>
-__device__ __forceinline__ void rows16_epilogue(const Rows16Args& a, int tile, int lane, const Acc& acc, float xscale) {
+// gate and up of hidden units 8 tile + 2q, + 1).  WK_I8D: acc = the int32 sums, xscale = the scale of activation row m.  AD: ladd =
+// lora_scale * the adapter term of the same features (rows16_adapter); AD_DORA: a.wscale = the rows' cached DoRA factors.
+template <int EPI, int WK, int AD, class Acc>
+__device__ __forceinline__ void rows16_epilogue(const Rows16Args& a, int tile, int lane, const Acc& acc, float xscale, const f32x4_t& ladd) {
+  static_assert(AD != AD_DORA || WK == WK_BF16, "DoRA factors ride on bf16 rows only");
   const int q = lane >> 4, m = lane & 15;
   if (m >= a.M) return;
   float v[4];
-  if constexpr (WK == WK_BF16) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = bf2f(f2bf(acc[e]));  // the linear's bf16 output
-  } else {
-    // int32 sum x activation-row scale x weight-row scale in fp32, rounded (int8_mm.py:93-118), as gemv_kernel<.., WK_I8D>
-    float wsc[4];
+  float wsc[4];  // the rows' weight scales (WK_I8D) or DoRA factors (AD_DORA)
+  if constexpr (WK == WK_I8D || AD == AD_DORA) {
     if constexpr (EPI == GV_SWIGLU) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) wsc[e] = bf2f(a.wscale[e >> 1][min(8 * tile + 2 * q + (e & 1), a.N / 2 - 1)]);
@@ -67,8 +124,23 @@ __device__ __forceinline__ void rows16_epilogue(const Rows16Args& a, int tile, i
 #pragma unroll
       for (int e = 0; e < 4; ++e) wsc[e] = bf2f(a.wscale[seg][min(n0 - base + 4 * q + e, a.seg_end[seg] - 1 - base)]);
     }
+  }
+  if constexpr (WK == WK_BF16) {
 #pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = bf2f(f2bf(((float)acc[e] * xscale) * wsc[e]));
+    for (int e = 0; e < 4; ++e) {
+      if constexpr (AD == AD_NONE) v[e] = bf2f(f2bf(acc[e]));  // the linear's bf16 output
+      else v[e] = bf2f(f2bf(acc[e] + ladd[e]));                // base and adapter meet in fp32 (modelling/lora.py:43), as gemv_kernel
+      // DoRA (modelling/lora.py:57-59): times the row's cached factor c = m / ||W + s B A||, rounded, as gemv_kernel<.., DORA>
+      if constexpr (AD == AD_DORA) v[e] = bf2f(f2bf(v[e] * wsc[e]));
+    }
+  } else {
+    // int32 sum x activation-row scale x weight-row scale in fp32, rounded (int8_mm.py:93-118), as gemv_kernel<.., WK_I8D>; the adapter
+    // term meets the base after the base's bf16 rounding (modelling/lora.py:41-43)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      v[e] = bf2f(f2bf(((float)acc[e] * xscale) * wsc[e]));
+      if constexpr (AD != AD_NONE) v[e] = bf2f(f2bf(v[e] + ladd[e]));
+    }
   }
   auto kv_off = [&]() -> int64_t {
     const int64_t p = a.pos[m];
@@ -77,8 +149,16 @@ __device__ __forceinline__ void rows16_epilogue(const Rows16Args& a, int tile, i
   stream_epilogue<EPI, 4>(a, EPI == GV_SWIGLU ? 8 * tile + 2 * q : 16 * tile + 4 * q, m, a.rope, kv_off, v);
 }
 
-template <int EPI, bool NORM, int WK>
-__global__ __launch_bounds__(256, 2) void rows16_kernel(const Rows16Args a) {
+// what finish and the combine launch share: the adapter term of the tile (every lane takes part in its MFMAs), then the epilogue
+template <int EPI, int WK, int AD, class Acc>
+__device__ __forceinline__ void rows16_tile_out(const rows16_args_t<AD>& a, int tile, int lane, const Acc& acc, float xscale) {
+  f32x4_t ladd = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (AD != AD_NONE) ladd = rows16_adapter<EPI>(a, tile, lane) * a.lora_scale;
+  rows16_epilogue<EPI, WK, AD>(a, tile, lane, acc, xscale, ladd);
+}
+
+template <int EPI, bool NORM, int WK, int AD = AD_NONE>
+__global__ __launch_bounds__(256, 2) void rows16_kernel(const rows16_args_t<AD> a) {
   static_assert(WK == WK_BF16 || WK == WK_I8D, "weight kinds of the batched stream");
   using WT = std::conditional_t<WK == WK_BF16, bf16_t, int8_t>;      // a stored weight element
   using acc_t = std::conditional_t<WK == WK_BF16, f32x4_t, i32x4_t>;
@@ -190,7 +270,7 @@ __global__ __launch_bounds__(256, 2) void rows16_kernel(const Rows16Args a) {
     }
     float xm = 0.f;
     if constexpr (WK == WK_I8D) xm = xsc[min(m, M - 1)];
-    rows16_epilogue<EPI, WK>(a, tile, lane, acc, xm);
+    rows16_tile_out<EPI, WK, AD>(a, tile, lane, acc, xm);
   };
   // software pipeline over the flattened (tile, batch) sequence of this wave: while one register set is consumed the next batch's 8
   // loads (of this tile or of the wave's next tile) are in flight
@@ -220,9 +300,9 @@ __global__ __launch_bounds__(256, 2) void rows16_kernel(const Rows16Args a) {
   }
 }
 
-// S > 1: one wave per tile sums the S partial tiles in slice order and runs the epilogue
-template <int EPI, int WK>
-__global__ __launch_bounds__(256) void rows16_combine_kernel(const Rows16Args a) {
+// S > 1: one wave per tile sums the S partial tiles in slice order and runs the epilogue (AD: with the tile's adapter term)
+template <int EPI, int WK, int AD = AD_NONE>
+__global__ __launch_bounds__(256) void rows16_combine_kernel(const rows16_args_t<AD> a) {
   using acc_t = std::conditional_t<WK == WK_BF16, f32x4_t, i32x4_t>;
   const int lane = threadIdx.x & 63;
   const int tile = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -232,28 +312,31 @@ __global__ __launch_bounds__(256) void rows16_combine_kernel(const Rows16Args a)
   for (int s2 = 1; s2 < a.S; ++s2) sum += *reinterpret_cast<const acc_t*>(sl + ((int64_t)s2 << 8));
   float xm = 0.f;
   if constexpr (WK == WK_I8D) xm = a.xscale[min(lane & 15, a.M - 1)];
-  rows16_epilogue<EPI, WK>(a, tile, lane, sum, xm);
+  rows16_tile_out<EPI, WK, AD>(a, tile, lane, sum, xm);
 }
 
-template <int EPI, int WK>
-static int launch_rows16(const Rows16Args& a, int grid, size_t lds, hipStream_t stream) {
-  if (a.norm_w) hipLaunchKernelGGL((rows16_kernel<EPI, true, WK>), dim3(grid), dim3(256), lds, stream, a);
-  else hipLaunchKernelGGL((rows16_kernel<EPI, false, WK>), dim3(grid), dim3(256), lds, stream, a);
-  LLX_LAUNCH_CHECK(WK == WK_BF16 ? "llx_gemm_rows16_bf16" : "llx_gemm_rows16_i8");
+// fn = the entry point's name for messages
+template <int EPI, int WK, int AD>
+static int launch_rows16(const char* fn, const rows16_args_t<AD>& a, int grid, size_t lds, hipStream_t stream) {
+  if (a.norm_w) hipLaunchKernelGGL((rows16_kernel<EPI, true, WK, AD>), dim3(grid), dim3(256), lds, stream, a);
+  else hipLaunchKernelGGL((rows16_kernel<EPI, false, WK, AD>), dim3(grid), dim3(256), lds, stream, a);
+  LLX_LAUNCH_CHECK(fn);
   if (a.S > 1) {
-    hipLaunchKernelGGL((rows16_combine_kernel<EPI, WK>), dim3((a.ntiles + 3) / 4), dim3(256), 0, stream, a);
-    LLX_LAUNCH_CHECK(WK == WK_BF16 ? "llx_gemm_rows16_bf16(combine)" : "llx_gemm_rows16_i8(combine)");
+    hipLaunchKernelGGL((rows16_combine_kernel<EPI, WK, AD>), dim3((a.ntiles + 3) / 4), dim3(256), 0, stream, a);
+    char name[64];
+    snprintf(name, sizeof name, "%s(combine)", fn);
+    LLX_LAUNCH_CHECK(name);
   }
   return LLX_OK;
 }
 
-template <int WK>
-static int launch_rows16_epi(const Rows16Args& a, int epi, int grid, size_t lds, hipStream_t stream) {
+template <int WK, int AD>
+static int launch_rows16_epi(const char* fn, const rows16_args_t<AD>& a, int epi, int grid, size_t lds, hipStream_t stream) {
   switch (epi) {
-    case GV_NONE: return launch_rows16<GV_NONE, WK>(a, grid, lds, stream);
-    case GV_RESIDUAL: return launch_rows16<GV_RESIDUAL, WK>(a, grid, lds, stream);
-    case GV_QKV: return launch_rows16<GV_QKV, WK>(a, grid, lds, stream);
-    default: return launch_rows16<GV_SWIGLU, WK>(a, grid, lds, stream);
+    case GV_NONE: return launch_rows16<GV_NONE, WK, AD>(fn, a, grid, lds, stream);
+    case GV_RESIDUAL: return launch_rows16<GV_RESIDUAL, WK, AD>(fn, a, grid, lds, stream);
+    case GV_QKV: return launch_rows16<GV_QKV, WK, AD>(fn, a, grid, lds, stream);
+    default: return launch_rows16<GV_SWIGLU, WK, AD>(fn, a, grid, lds, stream);
   }
 }
 
@@ -302,15 +385,22 @@ extern "C" int64_t llx_gemm_rows16_i8_workspace_bytes(int64_t M, int64_t N, int6
   return rows16_workspace(M, N, K, epilogue, 1, ROWS16_I8_HEADER);
 }
 
-// the two entry points below: fn = the caller's name for messages, wk = WK_BF16 | WK_I8D, ws_s = per-row scales of W_s (WK_I8D)
-static int rows16_run(const char* fn, int wk, const void* ws0, const void* ws1, const void* ws2, const void* w0, int64_t ldw0, int64_t n0, const void* w1,
+// the adapter operands of the two _lora entry points: bext_s bf16 [n_s, rank_s] row-major, t bf16 [M, sum rank] (row stride ldt),
+// colscale_s bf16 [n_s] = DoRA's cached row factors (all null: LoRA)
+struct Rows16Lora {
+  const void* bext[3]; int64_t rank[3]; const void* t; int64_t ldt; float scale; const void* colscale[3];
+};
+
+// the four entry points below: fn = the caller's name for messages, wk = WK_BF16 | WK_I8D, ws_s = per-row scales of W_s (WK_I8D),
+// lo = the adapter operands (null: the un-adapted entry points)
+static int rows16_run(const char* fn, int wk, const Rows16Lora* lo, const void* ws0, const void* ws1, const void* ws2, const void* w0, int64_t ldw0, int64_t n0, const void* w1,
                       int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2, int64_t n2, const void* x, int64_t ldx, int64_t M, int64_t K,
                       const void* norm_w, float eps, int epilogue, void* out, int64_t ldo, const void* res, int64_t ldr, const float* rope, int64_t n_q,
                       int64_t n_k, void* k_cache, void* v_cache, int64_t c_sb, int64_t c_sh, int64_t c_ss, int64_t Smax, const int64_t* pos,
                       void* workspace, int64_t workspace_bytes, hipStream_t stream) {
   const int esz = wk == WK_BF16 ? 2 : 1;
   const int64_t header = wk == WK_BF16 ? 0 : ROWS16_I8_HEADER;
-  Rows16Args a;
+  Rows16LoraArgs a;
   const int rc = stream_check_fill(fn, a, 2, 16, wk == WK_BF16 ? "one row runs llx_gemv_bf16, more than 16 the MFMA GEMM" : "one row runs llx_gemv_i8, more than 16 the MFMA GEMM",
                                    16 / esz, epilogue == GV_SWIGLU ? 1 : 16, w0, ldw0, n0, w1, ldw1,
                                    n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue, out, ldo, res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sh, c_ss, pos);
@@ -318,6 +408,31 @@ static int rows16_run(const char* fn, int wk, const void* ws0, const void* ws1, 
   if (wk != WK_BF16) {
     const int rc1 = stream_check_fill_scales(fn, a, "int8", ws0, ws1, ws2, n1, n2);
     if (rc1 != LLX_OK) return rc1;
+  }
+  int ad = AD_NONE;
+  if (lo) {
+    const void* w[3] = {w0, n1 > 0 ? w1 : nullptr, n2 > 0 ? w2 : nullptr};
+    int64_t off = 0;
+    for (int s = 0; s < 3; ++s) {
+      LLX_REQUIRE((w[s] != nullptr) == (lo->bext[s] != nullptr), "%s: every present weight needs its B factor, and only those (segment %d)", fn, s);
+      LLX_REQUIRE(!w[s] || (lo->rank[s] >= 16 && lo->rank[s] <= 64 && lo->rank[s] % 16 == 0),
+                  "%s: rank %lld of segment %d must be a multiple of 16, at most 64", fn, (long long)lo->rank[s], s);
+      LLX_REQUIRE((uintptr_t)lo->bext[s] % 16 == 0, "%s: B factors must be 16-byte aligned", fn);
+      a.bext[s] = (const bf16_t*)lo->bext[s]; a.rank[s] = w[s] ? (int)lo->rank[s] : 0; a.t_off[s] = (int)off;
+      off += a.rank[s];
+    }
+    LLX_REQUIRE(lo->t && (uintptr_t)lo->t % 16 == 0 && lo->ldt % 8 == 0 && lo->ldt >= off,
+                "%s: t missing (bf16 [M, sum of ranks], 16-byte aligned, row stride a multiple of 8 and at least the sum of the ranks)", fn);
+    a.t = (const bf16_t*)lo->t; a.ldt = lo->ldt; a.lora_scale = lo->scale;
+    for (int s = 1; s < 3; ++s)
+      if (!w[s]) { a.bext[s] = a.bext[0]; a.rank[s] = a.rank[0]; a.t_off[s] = 0; }  // absent segments repeat segment 0, as W[]
+    ad = AD_LORA;
+    if (lo->colscale[0] || lo->colscale[1] || lo->colscale[2]) {
+      LLX_REQUIRE(wk == WK_BF16, "%s: DoRA factors ride on bf16 rows only", fn);
+      const int rc2 = stream_check_fill_scales(fn, a, "DoRA", lo->colscale[0], lo->colscale[1], lo->colscale[2], n1, n2);
+      if (rc2 != LLX_OK) return rc2;
+      ad = AD_DORA;
+    }
   }
   LLX_REQUIRE(epilogue != GV_QKV || (n_q > 0 && Smax > 0 && Smax < (1ll << 31) && c_sb % 4 == 0),
               "%s: the q|k|v epilogue needs q heads, a cache length below 2^31 and 8-byte aligned cache slots", fn);
@@ -330,7 +445,12 @@ static int rows16_run(const char* fn, int wk, const void* ws0, const void* ws1, 
   a.slab = (float*)((char*)workspace + header);
   const int grid = p.wgs * p.S;
   const size_t lds = (size_t)M * p.KS * esz;
-  return wk == WK_BF16 ? launch_rows16_epi<WK_BF16>(a, epilogue, grid, lds, stream) : launch_rows16_epi<WK_I8D>(a, epilogue, grid, lds, stream);
+  if (ad == AD_NONE) {
+    const Rows16Args& b = a;  // the un-adapted instances take the base block
+    return wk == WK_BF16 ? launch_rows16_epi<WK_BF16, AD_NONE>(fn, b, epilogue, grid, lds, stream) : launch_rows16_epi<WK_I8D, AD_NONE>(fn, b, epilogue, grid, lds, stream);
+  }
+  if (ad == AD_DORA) return launch_rows16_epi<WK_BF16, AD_DORA>(fn, a, epilogue, grid, lds, stream);
+  return wk == WK_BF16 ? launch_rows16_epi<WK_BF16, AD_LORA>(fn, a, epilogue, grid, lds, stream) : launch_rows16_epi<WK_I8D, AD_LORA>(fn, a, epilogue, grid, lds, stream);
 }
 
 extern "C" int llx_gemm_rows16_bf16(const void* w0, int64_t ldw0, int64_t n0, const void* w1, int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2,
@@ -338,7 +458,7 @@ extern "C" int llx_gemm_rows16_bf16(const void* w0, int64_t ldw0, int64_t n0, co
                                     void* out, int64_t ldo, const void* res, int64_t ldr, const float* rope, int64_t n_q, int64_t n_k,
                                     void* k_cache, void* v_cache, int64_t c_sb, int64_t c_sh, int64_t c_ss, int64_t Smax, const int64_t* pos,
                                     void* workspace, int64_t workspace_bytes, hipStream_t stream) {
-  return rows16_run("llx_gemm_rows16_bf16", WK_BF16, nullptr, nullptr, nullptr, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue, out, ldo,
+  return rows16_run("llx_gemm_rows16_bf16", WK_BF16, nullptr, nullptr, nullptr, nullptr, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue, out, ldo,
                     res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sb, c_sh, c_ss, Smax, pos, workspace, workspace_bytes, stream);
 }
 
@@ -353,6 +473,38 @@ extern "C" int llx_gemm_rows16_i8(const void* w0, int64_t ldw0, int64_t n0, cons
                                   void* k_cache, void* v_cache, int64_t c_sb, int64_t c_sh, int64_t c_ss, int64_t Smax, const int64_t* pos,
                                   void* workspace, int64_t workspace_bytes, const void* scale0, const void* scale1, const void* scale2,
                                   hipStream_t stream) {
-  return rows16_run("llx_gemm_rows16_i8", WK_I8D, scale0, scale1, scale2, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue, out, ldo,
+  return rows16_run("llx_gemm_rows16_i8", WK_I8D, nullptr, scale0, scale1, scale2, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue, out, ldo,
                     res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sb, c_sh, c_ss, Smax, pos, workspace, workspace_bytes, stream);
+}
+
+// llx_gemm_rows16_bf16 on LoRA linears (modelling/lora.py:43): bext_s bf16 [n_s, rank_s] row-major for every present weight, ranks
+// multiples of 16 up to 64, t bf16 [M, sum rank] = x . [A_0; A_1; A_2]^T from a call of llx_gemm_rows16_bf16 on the A factors
+// (16-byte aligned, ldt % 8 == 0): out = epilogue(bf16(x . W^T + lora_scale * t_s . bext_s[row])).  colscale_s (bf16 [n_s], all
+// present segments or none): DoRA's cached row factors (modelling/lora.py:51-59), out = epilogue(bf16(bf16(..) * colscale[row])) -
+// the rounding points of llx_gemv_bf16 / llx_gemv_bf16_dora.  Workspace: llx_gemm_rows16_workspace_bytes().
+extern "C" int llx_gemm_rows16_bf16_lora(const void* w0, int64_t ldw0, int64_t n0, const void* w1, int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2,
+                                         int64_t n2, const void* x, int64_t ldx, int64_t M, int64_t K, const void* norm_w, float eps, int epilogue,
+                                         void* out, int64_t ldo, const void* res, int64_t ldr, const float* rope, int64_t n_q, int64_t n_k,
+                                         void* k_cache, void* v_cache, int64_t c_sb, int64_t c_sh, int64_t c_ss, int64_t Smax, const int64_t* pos,
+                                         void* workspace, int64_t workspace_bytes, const void* bext0, const void* bext1, const void* bext2,
+                                         int64_t rank0, int64_t rank1, int64_t rank2, const void* t, int64_t ldt, float lora_scale,
+                                         const void* colscale0, const void* colscale1, const void* colscale2, hipStream_t stream) {
+  const Rows16Lora lo = {{bext0, bext1, bext2}, {rank0, rank1, rank2}, t, ldt, lora_scale, {colscale0, colscale1, colscale2}};
+  return rows16_run("llx_gemm_rows16_bf16_lora", WK_BF16, &lo, nullptr, nullptr, nullptr, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue,
+                    out, ldo, res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sb, c_sh, c_ss, Smax, pos, workspace, workspace_bytes, stream);
+}
+
+// llx_gemm_rows16_i8 on LoRA linears: out = epilogue(bf16(bf16(((float)acc * x_scale[m]) * scale[row]) + lora_scale * t_s . bext_s[row])),
+// the rounding points of llx_gemv_i8(dynamic = 1); t from llx_gemm_rows16_bf16 on the un-quantised x.  Workspace:
+// llx_gemm_rows16_i8_workspace_bytes().
+extern "C" int llx_gemm_rows16_i8_lora(const void* w0, int64_t ldw0, int64_t n0, const void* w1, int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2,
+                                       int64_t n2, const void* x, int64_t ldx, int64_t M, int64_t K, const void* norm_w, float eps, int epilogue,
+                                       void* out, int64_t ldo, const void* res, int64_t ldr, const float* rope, int64_t n_q, int64_t n_k,
+                                       void* k_cache, void* v_cache, int64_t c_sb, int64_t c_sh, int64_t c_ss, int64_t Smax, const int64_t* pos,
+                                       void* workspace, int64_t workspace_bytes, const void* scale0, const void* scale1, const void* scale2,
+                                       const void* bext0, const void* bext1, const void* bext2, int64_t rank0, int64_t rank1, int64_t rank2,
+                                       const void* t, int64_t ldt, float lora_scale, hipStream_t stream) {
+  const Rows16Lora lo = {{bext0, bext1, bext2}, {rank0, rank1, rank2}, t, ldt, lora_scale, {nullptr, nullptr, nullptr}};
+  return rows16_run("llx_gemm_rows16_i8_lora", WK_I8D, &lo, scale0, scale1, scale2, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue,
+                    out, ldo, res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sb, c_sh, c_ss, Smax, pos, workspace, workspace_bytes, stream);
 }

@@ -50,6 +50,10 @@ SIGNATURES: dict[str, tuple] = {
     "llx_gemm_rows16_i8_workspace_bytes": (c_int64, [_L, _L, _L, _I]),
     "llx_gemm_rows16_i8": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _F, _I, _P, _L, _P, _L, _P, _L, _L, _P, _P, _L, _L, _L,
                                    _L, _P, _P, _L, _P, _P, _P, _P]),
+    "llx_gemm_rows16_bf16_lora": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _F, _I, _P, _L, _P, _L, _P, _L, _L, _P, _P, _L, _L, _L,
+                                          _L, _P, _P, _L, _P, _P, _P, _L, _L, _L, _P, _L, _F, _P, _P, _P, _P]),
+    "llx_gemm_rows16_i8_lora": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _F, _I, _P, _L, _P, _L, _P, _L, _L, _P, _P, _L, _L, _L,
+                                        _L, _P, _P, _L, _P, _P, _P, _P, _P, _P, _L, _L, _L, _P, _L, _F, _P]),
     "llx_attn_decode_workspace_bytes": (c_int64, [_L, _L, _L, _L]),
     "llx_attn_decode": (c_int, [_P, _L, _L, _L, _P, _P, _L, _L, _L, _P, _L, _L, _L, _P, _L, _L, _L, _P, _P, _L, _L, _L, _L, _L, _L, _L, _F, _P]),
     "llx_attn_bwd_workspace_bytes": (c_int64, [_L, _L, _L, _L]),

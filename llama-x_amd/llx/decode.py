@@ -7,11 +7,14 @@ above 64 or not a multiple of 8, a fused group that mixes DoRA and other members
 Int8LinearWeight linears (weight-only or dynamic, subclasses/int8.py:106-121) stream their int8 rows (llx_gemv_i8): no bf16 image of
 the matrix is built or read.
 
-A batch of 2 <= B <= 16 sequences with one token each (x [B, 1, D], a cache of batch B, linears without adapters) takes the same
-steps per layer with the MFMA weight stream in place of the GEMV: the weights are read once for all B rows (a product whose K is
-split adds a small combine launch).  Every fused group is bf16 (llx_gemm_rows16_bf16) or dynamic int8 (llx_gemm_rows16_i8: the rows
-quantised in the prologue, int8 MFMA); groups of different kinds may sit next to each other in a layer, as at batch 1.  Weight-only
-int8 and LoRA / DoRA linears and B > 16 stay on the generic path at B > 1.
+A batch of 2 <= B <= 16 sequences with one token each (x [B, 1, D], a cache of batch B) takes the same steps per layer with the MFMA
+weight stream in place of the GEMV: the weights are read once for all B rows (a product whose K is split adds a small combine
+launch).  Every fused group is bf16 (llx_gemm_rows16_bf16) or dynamic int8 (llx_gemm_rows16_i8: the rows quantised in the prologue,
+int8 MFMA); groups of different kinds may sit next to each other in a layer, as at batch 1.  LoRA linears on either kind and DoRA
+linears on bf16 ride the same stream when every rank of the group is 16, 32, 48 or 64 (llx_gemm_rows16_bf16_lora /
+llx_gemm_rows16_i8_lora): t = x @ A^T is the stream itself run on the A factors - its segments are 16-row tiles, hence the ranks -
+and the B factors (and DoRA's cached row factors) enter where a tile's epilogue runs, as a short MFMA chain.  Weight-only int8,
+other ranks, a group that mixes adapted and plain members and B > 16 stay on the generic path at B > 1.
 
 Per layer (M <= 4 tokens at batch 1):
     q            = gemv([wq; wk; wv], rmsnorm(x))  + RoPE on q, k + k, v scattered into the caches        1 launch
@@ -86,14 +89,25 @@ def _batched(x: Tensor) -> bool:
     return x.dim() == 3 and 2 <= x.shape[0] <= MAX_BATCH and x.shape[1] == 1 and BATCHED
 
 
+BATCH_RANKS = (16, 32, 48, 64)  # adapter ranks of the batched stream: the t product's segments are its 16-row tiles
+
+
 def _batch_group(mods) -> bool:
-    """A fused group the batched stream takes: all members bf16, or all dynamic int8, none with an adapter."""
-    return ({_plain(m) for m in mods} in ({KIND_BF16}, {KIND_I8D})) and all(int(getattr(m, "rank", 0) or 0) == 0 for m in mods)
+    """A fused group the batched stream takes: all members bf16, or all dynamic int8; none with an adapter, or all with LoRA adapters
+    of ranks in BATCH_RANKS (bf16 factors) and one scale, or - bf16 only - all with such DoRA adapters."""
+    if {_plain(m) for m in mods} not in ({KIND_BF16}, {KIND_I8D}):
+        return False
+    ranks = [int(getattr(m, "rank", 0) or 0) for m in mods]
+    if not any(ranks):
+        return True
+    if not all(r in BATCH_RANKS and m.lora_b.dtype is BF16 for r, m in zip(ranks, mods)):
+        return False
+    return len({float(m.scale) for m in mods}) == 1 and len({_dora(m) for m in mods}) == 1
 
 
 def layer_ok(layer, x: Tensor, mask: Optional[Tensor]) -> bool:
     """x [1, M <= 4, D], or x [B, 1, D] with 2 <= B <= 16: a cache of batch B, a bool mask [B | 1, 1, 1, Skv], every fused group
-    bf16 or dynamic int8 without adapters."""
+    one that _batch_group takes."""
     att, ff = layer.attention, layer.feed_forward
     if att.kv_cache is None or mask is None or x.dim() != 3 or x.dtype is not BF16 or not x.is_cuda or mask.dtype is not torch.bool:
         return False
@@ -116,11 +130,11 @@ def layer_ok(layer, x: Tensor, mask: Optional[Tensor]) -> bool:
     return att.wq.out_features % 4 == 0 and att.wk.out_features % 4 == 0
 
 
-def _lora(mods, x: Tensor, norm):
-    """(b factors, t = [rmsnorm(x) | x] @ [A_0; A_1; ..]^T, scale) or None."""
+def _lora(mods, x: Tensor, norm, stream=K.gemv):
+    """(b factors, t = [rmsnorm(x) | x] @ [A_0; A_1; ..]^T, scale) or None; stream: the product that computes t (K.gemv | K.gemm_rows16)."""
     if int(getattr(mods[0], "rank", 0) or 0) == 0:
         return None
-    t = K.gemv([m.lora_a.detach() for m in mods], x, norm=norm)
+    t = stream([m.lora_a.detach() for m in mods], x, norm=norm)
     return [m.lora_b.detach() for m in mods], t, float(mods[0].scale)
 
 
@@ -131,12 +145,12 @@ def mask_extent(mask: Tensor) -> Tensor:
 
 def _lin(batched: bool):
     """lin(mods, x, **kw): the fused product of a group of linears on the rows of x - the GEMV (any streamed kind, adapters) at batch 1,
-    the MFMA weight stream for a batch (per group: bf16 or dynamic int8)."""
+    the MFMA weight stream for a batch (per group: bf16 or dynamic int8, adapters of the ranks in BATCH_RANKS)."""
     if batched:
-        def lin(mods, x, **kw):
+        def lin(mods, x, norm=None, **kw):
             w = _w(mods)
             w.pop("dynamic", None)  # int8 groups of a batch are of the dynamic kind (layer_ok)
-            return K.gemm_rows16(x=x, **w, **kw)
+            return K.gemm_rows16(x=x, norm=norm, lora=_lora(mods, x, norm, K.gemm_rows16), **w, **kw)
         return lin
     return lambda mods, x, norm=None, **kw: K.gemv(x=x, norm=norm, lora=_lora(mods, x, norm), **_w(mods), **kw)
 

@@ -941,15 +941,27 @@ _ROWS16_WS: dict = {}
 
 
 def gemm_rows16(ws: Sequence[Tensor], x: Tensor, *, norm: Optional[tuple[Tensor, float]] = None, epilogue: int = GV_NONE, out: Optional[Tensor] = None,
-                res: Optional[Tensor] = None, qkv: Optional[tuple] = None, wscale: Optional[Sequence[Tensor]] = None) -> Tensor:
+                res: Optional[Tensor] = None, qkv: Optional[tuple] = None, wscale: Optional[Sequence[Tensor]] = None, lora: Optional[tuple] = None,
+                colscale: Optional[Sequence[Tensor]] = None) -> Tensor:
     """gemv's product for 2 <= M = x.shape[0] <= 16 rows - a batch of sequences, one token each - on the matrix pipe (llx_gemm_rows16_bf16):
-    the weights stream once whatever M is.  bf16 weights without adapters; norm, res and the GV_* epilogues as gemv, except GV_QKV, which
-    is the batched mode: qkv = (rope_table, n_q, n_k, k_cache, v_cache, pos) with caches [B >= M, KVH, Smax, 128] and pos int64 [M]; row m
-    is rotated by table row 0 and its k / v heads go to cache[m] at pos[m]; returns q [M, n_q].
+    the weights stream once whatever M is.  bf16 weights; norm, res and the GV_* epilogues as gemv, except GV_QKV, which is the batched
+    mode: qkv = (rope_table, n_q, n_k, k_cache, v_cache, pos) with caches [B >= M, KVH, Smax, 128] and pos int64 [M]; row m is rotated by
+    table row 0 and its k / v heads go to cache[m] at pos[m]; returns q [M, n_q].
     int8 ws (the int_data of dynamic Int8LinearWeights, all members of the call) with wscale = their bf16 per-row scales run
     llx_gemm_rows16_i8: the rows of x quantised on chip, int8 MFMA, the reference's dequantisation (the dynamic kind only: the
-    weight-only kind has no batched stream)."""
+    weight-only kind has no batched stream).
+    lora = (b factors, t [M, sum r], scale) and colscale (bf16 weights only) as gemv's: one contiguous bf16 [n_s, r_s] factor per weight
+    with r_s in {16, 32, 48, 64}, t = gemm_rows16(a factors, x, norm=norm); the adapter term of a tile is an MFMA chain in its epilogue
+    (llx_gemm_rows16_bf16_lora - with colscale DoRA's cached row factors - and llx_gemm_rows16_i8_lora), gemv's rounding points."""
     i8 = [w.dtype is torch.int8 for w in ws]
+    if colscale is not None:
+        if any(i8):
+            raise L.LlxError("gemm_rows16: colscale (DoRA) on int8 weights is not supported")
+        if lora is None:
+            raise L.LlxError("gemm_rows16: colscale (DoRA) needs the lora operands")
+        if len(colscale) != len(ws) or not all(c.dtype is BF16 and c.shape == (w.shape[0],) and c.is_contiguous() for c, w in zip(colscale, ws)):
+            raise L.LlxError("gemm_rows16: colscale must hold one contiguous bf16 [n_s] tensor per weight")
+        L.require_cuda(*colscale)
     if any(i8):
         if not all(i8):
             raise L.LlxError("gemm_rows16: bf16 and int8 weights in one call (all members of a fused group must be of one kind)")
@@ -964,12 +976,32 @@ def gemm_rows16(ws: Sequence[Tensor], x: Tensor, *, norm: Optional[tuple[Tensor,
         _chk_bf16(x, *ws)
     args, out, N, kc, pos = _stream_operands(ws, x, norm, epilogue, out, res, qkv, batched=True)
     args += [kc.stride(0), kc.stride(1), kc.stride(2), kc.shape[2]] if kc is not None else [0, 0, 0, 0]
+    largs = None
+    if lora is not None:
+        b_list, t, lscale = lora
+        assert len(b_list) == len(ws) and t.dtype is BF16 and t.shape[0] == x.shape[0] and t.stride(1) == 1
+        bs, ranks = [None] * 3, [0] * 3
+        for i, b in enumerate(b_list):
+            assert b.dtype is BF16 and b.is_contiguous() and b.shape[0] == ws[i].shape[0]
+            bs[i], ranks[i] = b, b.shape[1]
+        assert t.shape[1] == sum(ranks)
+        L.require_cuda(t, *b_list)
+        largs = [L.ptr(bs[0]), L.ptr(bs[1]), L.ptr(bs[2]), ranks[0], ranks[1], ranks[2], L.ptr(t), t.stride(0), float(lscale)]
     if any(i8):
         wsp = _workspace(_ROWS16_WS, x.device, _lib().llx_gemm_rows16_i8_workspace_bytes(x.shape[0], N, x.shape[1], epilogue), 1 << 20)
         sp = [L.ptr(sc) for sc in wscale] + [None] * (3 - len(ws))
+        if largs is not None:
+            L.check(_lib().llx_gemm_rows16_i8_lora(*args, L.ptr(pos), L.ptr(wsp), wsp.numel(), sp[0], sp[1], sp[2], *largs, L.stream()),
+                    "llx_gemm_rows16_i8_lora")
+            return out
         L.check(_lib().llx_gemm_rows16_i8(*args, L.ptr(pos), L.ptr(wsp), wsp.numel(), sp[0], sp[1], sp[2], L.stream()), "llx_gemm_rows16_i8")
         return out
     wsp = _workspace(_ROWS16_WS, x.device, _lib().llx_gemm_rows16_workspace_bytes(x.shape[0], N, x.shape[1], epilogue), 1 << 20)
+    if largs is not None:
+        cp = [L.ptr(c) for c in colscale] + [None] * (3 - len(ws)) if colscale is not None else [None] * 3
+        L.check(_lib().llx_gemm_rows16_bf16_lora(*args, L.ptr(pos), L.ptr(wsp), wsp.numel(), *largs, cp[0], cp[1], cp[2], L.stream()),
+                "llx_gemm_rows16_bf16_lora")
+        return out
     L.check(_lib().llx_gemm_rows16_bf16(*args, L.ptr(pos), L.ptr(wsp), wsp.numel(), L.stream()), "llx_gemm_rows16_bf16")
     return out
 

@@ -21,7 +21,15 @@ fourth window times the batched step of a bf16 model of the same dimensions and 
 `bf16_batched_step_ms`.  The
 kernel table then has the five products through gemm_rows16 on int8 rows next to the bf16 rows16 and the int8 GEMV (dynamic) figures.
 
-    python tools/generate_batch_bench.py [--int8] [--prompt 1024] [--new 64] [--rounds 5] [--layers 32] [--out profiles/generate_batch_bench.json]
+--adapter lora|dora: every layer linear dressed with apply_linear_adapter_(model.layers, ..., rank=16, alpha=32) (B factors drawn
+N(0, 0.02^2)); with --int8 (LoRA only) on the dynamic-int8 layers.  The batched step then runs the adapter entry points of the weight
+stream (llx_gemm_rows16_bf16_lora / llx_gemm_rows16_i8_lora).  Four windows alternate for B in 2, 4, 8, 16: (a) the batched adapted step,
+(b) the same model on the generic inference path (llx.decode.BATCHED = False: the route of an adapted batch before these entry points
+existed), (c) B batch-1 steps, (d) the batched step of the un-adapted model of the same base and seed (`base_batched_step_ms`: what
+the adapters cost).  `keep_fast_path` holds when (a) beats both (b) and (c) by more than the larger of the two windows' min-max
+spreads.  The kernel table is skipped.  Default output: profiles/generate_batch_lora_bench[_dora | _int8].json.
+
+    python tools/generate_batch_bench.py [--int8] [--adapter lora|dora] [--prompt 1024] [--new 64] [--rounds 5] [--layers 32] [--out profiles/generate_batch_bench.json]
 (--int8: the default output is profiles/generate_batch_int8_bench.json)
 """
 import argparse
@@ -83,8 +91,11 @@ def main():
     ap.add_argument("--kernel-rounds", type=int, default=15)
     ap.add_argument("--kernels-only", action="store_true")
     ap.add_argument("--int8", action="store_true", help="dynamic-int8 layers (bf16 head): the int8 batched weight stream")
+    ap.add_argument("--adapter", choices=("lora", "dora"), default=None, help="rank-16 adapters on every layer linear (with --int8: lora only)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.adapter == "dora" and args.int8:
+        raise SystemExit("generate_batch_bench: DoRA rides on bf16 weights only")
     for p in (ROOT, os.path.join(ROOT, "llama-x_amd")):
         sys.path.insert(0, p)
     import torch
@@ -103,8 +114,11 @@ def main():
     g = torch.Generator(device=dev)
     g.manual_seed(1)
     prompts = torch.randint(0, cfg.vocab_size, (max(BATCHES), P), device=dev, generator=g)
-    res = {"workload": f"Llama-3.1-8B dimensions ({args.layers} layers), random weights{', layers dynamic int8 (bf16 head)' if args.int8 else ''}, "
+    res = {"workload": f"Llama-3.1-8B dimensions ({args.layers} layers), random weights{', layers dynamic int8 (bf16 head)' if args.int8 else ''}"
+                       f"{f', {args.adapter} r=16 alpha=32 on every layer linear' if args.adapter else ''}, "
                        f"max_seq_len 8192, prompts of {P} tokens, {n} new tokens, greedy; medians (min-max) of {args.rounds} alternating rounds"}
+    if args.adapter and args.out is None:
+        args.out = os.path.join(ROOT, "profiles", f"generate_batch_lora_bench{'_dora' if args.adapter == 'dora' else ''}{'_int8' if args.int8 else ''}.json")
     if args.int8 and args.out is None:
         args.out = os.path.join(ROOT, "profiles", "generate_batch_int8_bench.json")
 
@@ -133,15 +147,35 @@ def main():
     mods = {"wq": att.wq, "wk": att.wk, "wv": att.wv, "wo": att.wo, "w1": ff.w1, "w3": ff.w3, "w2": ff.w2, "output": model.output}
     bf = {k: m.weight.detach() for k, m in mods.items()}
     q8 = {}
+    model_bf16 = model_base = None
     if args.int8:
         from subclasses import quantize_linear_
         from subclasses.int8 import quantize_int8_rowwise
 
-        q8 = {k: quantize_int8_rowwise(w) for k, w in bf.items()}
+        if not args.adapter:
+            q8 = {k: quantize_int8_rowwise(w) for k, w in bf.items()}
         quantize_linear_(model.layers, "int8", dynamic_int8_act=True)
-        model_bf16, _ = build(args.layers, 8192, dev)  # the bf16 twin for the bf16 batched-step window
-        model_bf16.build_cache(inference=True)
-        model_bf16 = model_bf16.to(dev)
+        if not args.adapter:
+            model_bf16, _ = build(args.layers, 8192, dev)  # the bf16 twin for the bf16 batched-step window
+            model_bf16.build_cache(inference=True)
+            model_bf16 = model_bf16.to(dev)
+    if args.adapter:
+        from modelling import apply_linear_adapter_
+
+        model_base, _ = build(args.layers, 8192, dev)  # the un-adapted twin of the same base
+        model_base.build_cache(inference=True)
+        model_base = model_base.to(dev)
+        if args.int8:
+            quantize_linear_(model_base.layers, "int8", dynamic_int8_act=True)
+        apply_linear_adapter_(model.layers, args.adapter, rank=16, alpha=32.0)
+        with torch.no_grad():
+            for m in model.layers.modules():
+                if getattr(m, "lora_b", None) is not None:
+                    m.lora_b.normal_(0.0, 0.02, generator=g)
+        model.requires_grad_(False)
+        x1 = torch.zeros(2, 1, cfg.embed_dim, device=dev, dtype=torch.bfloat16)
+        install(model, caches_for(model, cfg, 2, dev))
+        assert DEC.layer_ok(model.layers[0], x1, model.causal_mask[torch.zeros(2, 1, dtype=torch.int64, device=dev)][:, None]), "the adapted layer is not on the batched fast path"
 
     def operands(kind, names):
         return dict(ws=[bf[k] for k in names]) if kind == "bf16" else dict(ws=[q8[k][0] for k in names], wscale=[q8[k][1] for k in names])
@@ -159,6 +193,8 @@ def main():
     variants += [(f"rows16 M={M}", K.gemm_rows16, M, (kc, vc), "bf16", {}) for M in (2, 8, 16)]
     if args.int8:
         variants += [(f"rows16 int8 M={M}", K.gemm_rows16, M, (kc, vc), "int8", {}) for M in (2, 8, 16)]
+    if args.adapter:
+        variants = []  # the adapter windows below are the measurement
     times = {(v[0], name): [] for v in variants for name in products}
     for r in range(args.kernel_rounds + 1):
         for vname, f, M, c, kind, extra in variants:
@@ -167,15 +203,16 @@ def main():
                 t = events(lambda: f(**w, **kw(M, c), **extra), 1)
                 if r > 0:  # the first round is untimed
                     times[(vname, name)].append(t * 1e3)
-    res["kernels_us_and_GBps"] = {name: {v[0]: {"us": stats(times[(v[0], name)]),
-                                                "GBps": round(products[name][1] * (2 if v[4] == "bf16" else 1) / (stats(times[(v[0], name)])["median"] * 1e-6) / 1e9, 1)}
-                                         for v in variants} for name in products}
+    if variants:
+        res["kernels_us_and_GBps"] = {name: {v[0]: {"us": stats(times[(v[0], name)]),
+                                                    "GBps": round(products[name][1] * (2 if v[4] == "bf16" else 1) / (stats(times[(v[0], name)])["median"] * 1e-6) / 1e9, 1)}
+                                             for v in variants} for name in products}
 
     # ---- decode steps and whole generate() calls, batched against sequential
     if not args.kernels_only:
         one = caches_for(model, cfg, 1, dev)
         res["batches"] = {}
-        for B in BATCHES:
+        for B in (BATCHES[1:] if args.adapter else BATCHES):
             many = one if B == 1 else caches_for(model, cfg, B, dev)
             pr = prompts[:B]
 
@@ -211,19 +248,23 @@ def main():
                 return (time.perf_counter() - t0) * 1e3
 
             gen_batched(), gen_sequential()  # untimed pass of both
-            ms = {"batched_step": [], "single_step": [], "batched_generate": [], "sequential_generate": [], "generic_step": [], "bf16_batched_step": []}
+            ms = {"batched_step": [], "single_step": [], "batched_generate": [], "sequential_generate": [], "generic_step": [], "bf16_batched_step": [],
+                  "base_batched_step": []}
             for _ in range(args.rounds):
                 install(model, many)
                 ms["batched_step"].append(step_ms(B))
-                if args.int8 and B > 1:  # the same step on the generic inference path
+                if (args.int8 or args.adapter) and B > 1:  # the same step on the generic inference path
                     DEC.BATCHED = False
                     try:
                         ms["generic_step"].append(step_ms(B))
                     finally:
                         DEC.BATCHED = True
-                if args.int8:  # the bf16 model's batched step against the same caches
+                if model_bf16 is not None:  # the bf16 model's batched step against the same caches
                     install(model_bf16, many)
                     ms["bf16_batched_step"].append(step_ms(B, model_bf16))
+                if model_base is not None:  # the un-adapted model's batched step against the same caches
+                    install(model_base, many)
+                    ms["base_batched_step"].append(step_ms(B, model_base))
                 install(model, one)
                 ms["single_step"].append(step_ms(1))
                 ms["batched_generate"].append(wall(gen_batched))
@@ -243,6 +284,13 @@ def main():
             if ms["bf16_batched_step"]:
                 fs = stats(ms["bf16_batched_step"])
                 res["batches"][str(B)].update({"bf16_batched_step_ms": fs, "int8_over_bf16_step": round(bs["median"] / fs["median"], 2)})
+            if ms["base_batched_step"]:
+                fs, gs = stats(ms["base_batched_step"]), stats(ms["generic_step"])
+                spread = lambda a, b: max(a["max"] - a["min"], b["max"] - b["min"])  # noqa: E731
+                res["batches"][str(B)].update({
+                    "base_batched_step_ms": fs, "adapted_over_base_step": round(bs["median"] / fs["median"], 2),
+                    "keep_fast_path": gs["median"] - bs["median"] > spread(gs, bs) and ss["median"] - bs["median"] > spread(ss, bs)})
+            print(f"B={B}: {json.dumps(res['batches'][str(B)])}", file=sys.stderr, flush=True)
             if B > 1:
                 del many
                 torch.cuda.empty_cache()
