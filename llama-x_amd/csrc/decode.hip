@@ -405,7 +405,7 @@ static int launch_gemv_mt(const char* fn, const GemvArgs& a, int MT, int epi, in
 
 // out[M, N] = epilogue( x[M, K] . [W0; W1; W2]^T ), M <= 4, bf16, fp32 accumulate; F.linear at decode shapes
 // (modelling/llama.py:118-120,140,152,216).  W_s: [n_s, K] row-major with row stride ldw_s (nullable from s = 1 on; n_s % 4 == 0 except
-// the last), K % 8 == 0.  norm_w (nullable): x is RMS-normalised with this weight first (llama.py:172-173,215).
+// the last, or any n_0 = n_1 under the SwiGLU epilogue), K % 8 == 0.  norm_w (nullable): x is RMS-normalised with this weight first (llama.py:172-173,215).
 // The epilogues are wstream.h's; q|k|v rotates row m by table row m and writes its k / v heads at input_pos[m] (device int64), caches
 // through (head, position) strides.  LoRA (nullable bext_s [n_s, rank_s], t [M, sum rank] bf16 = x . A^T, offsets t_off_s, scale):
 // out += scale * t_s . bext_s[row].
@@ -419,7 +419,8 @@ static int gemv_run(const char* fn, int wk, bool dora, const void* ws0, const vo
                     hipStream_t stream) {
   const int wa = wk == WK_BF16 ? 8 : 16;  // weight elements per 16-byte lane load
   GemvArgs a;
-  const int rc0 = stream_check_fill(fn, a, 1, 4, "larger row counts run the MFMA GEMM", wa, 4, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps,
+  // (inner segments in multiples of 4 rows keep a row group inside one weight; SwiGLU pairs gate row i with up row i whatever their count)
+  const int rc0 = stream_check_fill(fn, a, 1, 4, "larger row counts run the MFMA GEMM", wa, epilogue == GV_SWIGLU ? 1 : 4, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps,
                                     epilogue, out, ldo, res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sh, c_ss, input_pos);
   if (rc0 != LLX_OK) return rc0;
   if (wk != WK_BF16 || dora) {
