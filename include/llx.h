@@ -425,6 +425,19 @@ int llx_sample_rows(const void* logits, int dtype, int64_t ld, int64_t R, int64_
                     uint64_t seed, int64_t* pos, int64_t* token_out, int64_t* history, int64_t hist_ld, int64_t hist_cap, int64_t hist_base,
                     int advance, int64_t eos_id, int32_t* finished, float* aux_u, float* aux_thresh, int32_t* aux_kept, llx_stream_t s);
 
+/* ---- prompt-lookup drafting (generate(draft_tokens=k), llx/generate.py): the bookkeeping of one greedy speculative step, one workgroup,
+ *      no host read.  The step fed step_tok [k + 1] = [last token, k draft tokens] at step_pos; picks int64 [k + 1] are the greedy picks of
+ *      its k + 1 logits rows.  With a = the longest prefix with step_tok[1 + i] == picks[i], picks[0 .. a] are emitted - cut to the room
+ *      left (P + n - len[0]) and after the first eos_id (-1: none; it sets finished[0]) - and appended to seq (int64 [cap], cap >= P + n:
+ *      the prompt, then the generated tokens; len int64 [1]).  Then the next step is written: step_tok = [seq[len - 1], draft],
+ *      step_pos = len - 1 .. len - 1 + k, the draft by llx.sampling.lookup_draft (the most recent earlier occurrence of the last gg
+ *      tokens, gg = g .. 1, the longest first, continued; no match repeats the last token).  counters int64 [2] += (1, emitted - 1).
+ *      init != 0: the first token after the prefill - picks [1] is emitted, nothing is confirmed, step_tok is not read.  A launch that
+ *      finds finished[0] set or len[0] == P + n changes nothing.  k in 1..3, g in 1..8, P >= 1, n >= 1.  The caller keeps
+ *      len - 1 + k inside the KV cache. ---------------------------------------------------------------------------------------- */
+int llx_lookup_step(const int64_t* picks, int64_t* seq, int64_t cap, int64_t* len, int64_t* step_tok, int64_t* step_pos, int32_t* finished,
+                    int64_t* counters, int64_t P, int64_t n, int k, int g, int64_t eos_id, int init, llx_stream_t s);
+
 /* ---- small utilities of the backward pass ---------------------------------------------------------------------- */
 int llx_scale(const void* x, int64_t x_ld, void* y, int64_t y_ld, const float* dev_scalar, float host_scale, const void* colscale,
               int64_t rows, int64_t cols, llx_stream_t s);   /* (g * scale) of subclasses/int8.py:127; loss-scale of dX */

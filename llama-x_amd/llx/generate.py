@@ -4,9 +4,14 @@ The reference names its `input_pos` branch "used for inference i.e. generate" (m
 this is that loop.  Nothing in it reads the device inside a token: the sampler (csrc/sample.hip) writes the next input token, appends
 it to the history buffer and advances the position counter on the device, so the launch-bound decode path is never
 stalled by an `.item()`.  With `eos_id` the host looks at the finished flag once every `check_every` tokens.
+
+generate(draft_tokens=k) is the greedy loop with prompt-lookup drafts: a step feeds the last token and k draft tokens found in the sequence
+itself as one k + 1-row call of the batch-1 decode path (llx/decode.py: up to four rows for one pass over the weights) and keeps the
+prefix of the draft that the model confirms; accepting, appending and drafting are one launch of csrc/lookup.hip.
 """
 from __future__ import annotations
 
+from contextlib import contextmanager
 from typing import Optional, Sequence
 
 import torch
@@ -17,9 +22,12 @@ from . import kernels as K
 from ._lib import LlxError
 from .sampling import check_params
 
+MAX_NGRAM = 8  # the longest n-gram a lookup draft matches (csrc/lookup.hip)
 
-def _check(model, prompt: Tensor, max_new_tokens: int, eos_id, prefill_chunk, check_every, prompt_lens=None) -> Optional[list]:
-    """Raises LlxError on anything generate() cannot run, before any launch; returns the prompt lengths as a list (None: every row is P)."""
+
+def _check(model, prompt: Tensor, max_new_tokens: int, eos_id, prefill_chunk, check_every, prompt_lens=None, draft=None) -> Optional[list]:
+    """Raises LlxError on anything generate() cannot run, before any launch; returns the prompt lengths as a list (None: every row is P).
+    draft: (draft_tokens, draft_ngram, temperature) of a call with draft_tokens != 0."""
     from modelling.llama import Llama
 
     if not isinstance(model, Llama) or type(model)._embed is not Llama._embed:
@@ -41,6 +49,8 @@ def _check(model, prompt: Tensor, max_new_tokens: int, eos_id, prefill_chunk, ch
             raise LlxError(f"prompt_lens must hold {prompt.shape[0]} integer lengths, one per row of prompt")
         if not all(1 <= v <= prompt.shape[1] for v in lens):
             raise LlxError(f"prompt_lens {lens} must lie in [1, {prompt.shape[1]}] (prompt is right-padded to P = {prompt.shape[1]})")
+    if draft is not None:
+        _check_draft(model, prompt, max_new_tokens, lens, *draft)
     if not prompt.is_cuda or model.tok_embeddings.weight.device != prompt.device:
         raise LlxError("generate() runs on the HIP device: model and prompt must be on the same GPU")
     if not (isinstance(max_new_tokens, int) and max_new_tokens >= 1):
@@ -55,6 +65,26 @@ def _check(model, prompt: Tensor, max_new_tokens: int, eos_id, prefill_chunk, ch
     if not (isinstance(check_every, int) and check_every >= 1):
         raise LlxError(f"check_every={check_every!r} must be an integer >= 1")
     return lens
+
+
+def _check_draft(model, prompt: Tensor, max_new_tokens, lens, k, g, temperature) -> None:
+    """The conditions of generate(draft_tokens=k): greedy, one sequence, and room in the cache for the rows a draft step writes."""
+    if not (isinstance(k, int) and not isinstance(k, bool) and 0 <= k <= D.MAX_TOKENS - 1):
+        raise LlxError(f"draft_tokens={k!r} must be an integer in 0..{D.MAX_TOKENS - 1} (a decode step takes {D.MAX_TOKENS} rows)")
+    if not (isinstance(g, int) and not isinstance(g, bool) and 1 <= g <= MAX_NGRAM):
+        raise LlxError(f"draft_ngram={g!r} must be an integer in 1..{MAX_NGRAM}")
+    if temperature != 0:
+        raise LlxError(f"draft_tokens={k} needs temperature == 0 (got {temperature!r}): drafting confirms greedy picks; a sampled draft would "
+                       "change the random stream")
+    P = prompt.shape[1]
+    if prompt.shape[0] != 1 or (lens is not None and lens != [P]):
+        raise LlxError(f"draft_tokens={k} drives one sequence: a cache of batch 1 and prompt_lens None or [{P}] "
+                       f"(got a batch of {prompt.shape[0]}, prompt_lens {lens})")
+    if isinstance(max_new_tokens, int) and P + max_new_tokens + k > model.config.max_seq_len:
+        # a step writes keys and values at positions up to len - 1 + k <= P + max_new_tokens - 1 + k, and the decode path does not check
+        # positions against the cache: this bound is what keeps those writes inside it
+        raise LlxError(f"prompt ({P}) + max_new_tokens ({max_new_tokens}) + draft_tokens ({k}) exceeds max_seq_len ({model.config.max_seq_len}): "
+                       "a draft step writes cache rows up to k positions past the last token")
 
 
 # ---- history bookkeeping of a batch with prompts of different lengths (pure: no device, no model)
@@ -139,9 +169,73 @@ def _generate_batch(model, prompt: Tensor, n: int, lens: list, sampling: dict, e
     return history_rows(history, shifts, counts, T, eos_id if eos_id is not None else 0)
 
 
+# ---- greedy decoding with prompt-lookup drafts (generate(draft_tokens=k)): several rows of one sequence per step
+@contextmanager
+def decode_rope(model):
+    """While active, `model.rope` is a contiguous fp32 [4, head_dim / 2, 2] buffer that holds the table's row 0 four times; the table is
+    back afterwards, also on an exception.  forward rotates a call's rows by rope[:L], the index in the call (the reference's
+    modelling/llama.py:207), so the one-row decode steps of a plain loop rotate every generated token by row 0.  A step that feeds
+    several rows of the same sequence must rotate each of them by that row too, or drafting would change the result."""
+    table = model.rope
+    model.rope = table[:1].float().expand(D.MAX_TOKENS, -1, -1).contiguous()
+    try:
+        yield
+    finally:
+        model.rope = table
+
+
+def _draft_rows(model, k: int, dev) -> int:
+    """k, lowered to the largest k' for which the decode fast path takes a k' + 1-row step, if it takes a one-row step of this model
+    at all (a model on the generic path runs any number of rows there).  Probes only: nothing is launched."""
+    def fast(rows: int) -> bool:
+        x = torch.empty(1, rows, model.config.embed_dim, device=dev, dtype=model.tok_embeddings.weight.dtype)
+        mask = model.causal_mask[None, None, :rows]
+        return all(D.layer_ok(layer, x, mask) for layer in model.layers) and D.head_ok(model, x)
+
+    if not fast(1):
+        return k
+    while k > 0 and not fast(k + 1):
+        k -= 1
+    return k
+
+
+def _generate_draft(model, prompt: Tensor, logits: Tensor, n: int, k: int, g: int, eos_id, check_every: int, stats) -> Tensor:
+    """The decode loop of generate(draft_tokens=k) after the prefill (`logits`: the prefill's last call).  Per step: one model call on the
+    k + 1 rows of step_tok at step_pos, one sampler launch (the greedy pick of every row), one llx_lookup_step launch (accept, append,
+    draft, the next step's rows) - nothing reads the host."""
+    dev, P = prompt.device, prompt.shape[1]
+    seq = torch.empty(P + n, device=dev, dtype=torch.int64)  # the prompt, then the generated tokens
+    seq[:P] = prompt[0]
+    st = torch.zeros(3, device=dev, dtype=torch.int64)  # len | steps, accepted
+    length, counters = st[:1], st[1:]
+    length.fill_(P)
+    finished = torch.zeros(1, device=dev, dtype=torch.int32)
+    step_tok = torch.zeros(k + 1, device=dev, dtype=torch.int64)
+    step_pos = torch.zeros(k + 1, device=dev, dtype=torch.int64)
+    picks = torch.empty(k + 1, device=dev, dtype=torch.int64)
+    draw = torch.zeros(k + 1, device=dev, dtype=torch.int64)  # the sampler's draw counter: not used at temperature 0
+    kw = dict(P=P, n=n, k=k, g=g, eos_id=eos_id)
+    K.sample(logits[0, -1:], temperature=0.0, pos=draw[:1], out=picks[:1])
+    K.lookup_step(picks, seq, length, step_tok, step_pos, finished, counters, init=True, **kw)
+    with decode_rope(model):
+        for s in range(1, n + 1):
+            if s % check_every == 0 or s == n:
+                # one host read.  Every step that is not frozen emits a token, so after n - 1 steps the sequence is done at the latest.
+                total, steps, accepted, fin = torch.cat((st, finished.to(torch.int64))).tolist()
+                if fin or total == P + n or s == n:
+                    break
+            K.sample(model(step_tok[None], input_pos=step_pos)[0], temperature=0.0, pos=draw, out=picks)
+            K.lookup_step(picks, seq, length, step_tok, step_pos, finished, counters, **kw)
+    if stats is not None:
+        stats.update(steps=steps, tokens=total - P, accepted=accepted, draft_tokens=k, launched=s - 1,
+                     state=dict(seq=seq, len=length, step_tok=step_tok, step_pos=step_pos, finished=finished, counters=counters))
+    return seq[None, P:total]
+
+
 @torch.no_grad()
 def generate(model, prompt: Tensor, max_new_tokens: int, *, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
-             eos_id: Optional[int] = None, prefill_chunk: Optional[int] = None, check_every: int = 16, prompt_lens=None) -> Tensor:
+             eos_id: Optional[int] = None, prefill_chunk: Optional[int] = None, check_every: int = 16, prompt_lens=None,
+             draft_tokens: int = 0, draft_ngram: int = 3, stats: Optional[dict] = None) -> Tensor:
     """Continue `prompt` (int64 [B, P], B = the batch the KV cache was built for) by up to `max_new_tokens` tokens -> int64 [B, n_new] on
     the prompt's device.  `prompt_lens` (B lengths in [1, P], a sequence or an int64 tensor, read once on the host before the first
     launch): the rows of `prompt` are right-padded prompts of these lengths; default: every row is P long.  For a batch the result is as
@@ -159,9 +253,28 @@ def generate(model, prompt: Tensor, max_new_tokens: int, *, temperature: float =
     `check_every - 1` of them), each feeding `eos_id` at the position counter, which no longer advances.  The returned tokens are not
     affected, but after an early stop the cache row at the position that follows the `eos_id` holds that token's keys and values rather
     than nothing.  While a prefill chunk runs, `model.rope` is a shifted view of the table (restored before the first decode step, also
-    on an exception): do not drive the same model from another thread meanwhile."""
+    on an exception): do not drive the same model from another thread meanwhile.
+
+    `draft_tokens` = k in 1..3 (greedy only, one sequence, P + max_new_tokens + k <= max_seq_len; 0, the default, is the loop above):
+    prompt-lookup drafting.  Each decode step feeds the last token and k draft tokens as one k + 1-row call - the weights stream once for
+    all rows - and keeps the longest prefix of the draft that the model's own greedy picks confirm, so a step yields 1 .. k + 1 tokens.
+    The draft is what followed the most recent earlier occurrence of the last `draft_ngram` .. 1 tokens in the sequence itself (the longest
+    n-gram that occurs wins; sampling.lookup_draft).  The result is the greedy continuation: only the number of weight passes changes (a
+    row's logits may differ in the last bits between a one-row and a k + 1-row step, so a near-tie may fall the other way).  `eos_id`,
+    `check_every` and `prefill_chunk` keep their meaning; the host looks at the device once every `check_every` steps, also without an
+    `eos_id`, because the number of steps is not known in advance.  Between looks the device state is frozen once the sequence is done:
+    the extra steps feed the same tokens at the same positions and rewrite the same cache rows with the same values.  If the decode fast
+    path (llx/decode.py) takes a one-row step of this model but not a k + 1-row one, k is lowered to the largest row count it takes (0:
+    the plain loop).  Afterwards the cache rows 0 .. P + len(result) - 2 hold the keys and values of the sequence; later rows, up to
+    P + len(result) - 1 + k, may hold those of rejected drafts.  While the decode steps run, `model.rope` is decode_rope's table.
+
+    `stats` (a dict) receives, from the one host read that ends the loop: "steps" (model calls that yielded tokens, the prefill's last row
+    counted as one), "tokens" (= len(result)), "accepted" (draft tokens in the result: tokens - steps), "draft_tokens" (the k that ran)
+    and "launched" (decode steps launched, the frozen ones included); with drafting also "state", the device tensors of the loop (seq,
+    len, step_tok, step_pos, finished, counters), not read.  Without drafting the numbers come from the loop itself, without a read."""
     check_params(temperature, top_k, top_p, seed)
-    lens = _check(model, prompt, max_new_tokens, eos_id, prefill_chunk, check_every, prompt_lens)
+    lens = _check(model, prompt, max_new_tokens, eos_id, prefill_chunk, check_every, prompt_lens,
+                  (draft_tokens, draft_ngram, temperature) if draft_tokens != 0 else None)
     D.prepare(model)
     dev, P, n = prompt.device, prompt.shape[1], max_new_tokens
     if prompt.shape[0] > 1 or (lens is not None and lens != [P]):
@@ -179,6 +292,10 @@ def generate(model, prompt: Tensor, max_new_tokens: int, *, temperature: float =
             logits = model(prompt[:, s : s + chunk], input_pos=positions[s : s + chunk])
     finally:
         model.rope = table
+    if draft_tokens != 0:
+        draft_tokens = _draft_rows(model, draft_tokens, dev)
+    if draft_tokens != 0:
+        return _generate_draft(model, prompt, logits, n, draft_tokens, draft_ngram, eos_id, check_every, stats)
     pos = torch.full((1,), P - 1, device=dev, dtype=torch.int64)  # position of the row being sampled from; the sampler advances it
     tok = torch.empty(1, 1, device=dev, dtype=torch.int64)
     history = torch.empty(1, n, device=dev, dtype=torch.int64)
@@ -197,4 +314,6 @@ def generate(model, prompt: Tensor, max_new_tokens: int, *, temperature: float =
         if k == n:
             break
         K.sample(model(tok, input_pos=pos)[0], **kw)
+    if stats is not None:
+        stats.update(steps=count, tokens=count, accepted=0, draft_tokens=0, launched=k - 1)
     return history[:, :count]

@@ -1112,6 +1112,27 @@ def sample(logits: Tensor, *, temperature: float, top_k: int = 0, top_p: float =
     return (tokens, au, at, ak) if aux else tokens
 
 
+def lookup_step(picks: Tensor, seq: Tensor, length: Tensor, step_tok: Tensor, step_pos: Tensor, finished: Tensor, counters: Tensor, *,
+                P: int, n: int, k: int, g: int, eos_id: Optional[int] = None, init: bool = False) -> None:
+    """The bookkeeping of one greedy step with k prompt-lookup draft tokens, in one launch and without a host read (csrc/lookup.hip;
+    the host reference is sampling.lookup_accept then sampling.lookup_draft).  picks (int64 [k + 1]): the greedy picks of the logits rows
+    of the step that fed step_tok (int64 [k + 1]) at step_pos (int64 [k + 1]).  The confirmed tokens are appended to seq (int64 [cap],
+    cap >= P + n) at length (int64 [1]), step_tok / step_pos become the next step's, finished (int32 [1]) is set by an emitted eos_id,
+    counters (int64 [2]) += (1, emitted - 1).  init: the first token after the prefill (picks [1] or longer, only picks[0] is read).
+    Nothing changes once finished is set or length == P + n."""
+    L.require_cuda(picks, seq, length, step_tok, step_pos, finished, counters)
+    for name, t, dt, numel in (("picks", picks, torch.int64, 1 if init else k + 1), ("seq", seq, torch.int64, P + n), ("length", length, torch.int64, 1),
+                               ("step_tok", step_tok, torch.int64, k + 1), ("step_pos", step_pos, torch.int64, k + 1),
+                               ("finished", finished, torch.int32, 1), ("counters", counters, torch.int64, 2)):
+        exact = name not in ("picks", "seq")
+        if t.dtype is not dt or t.dim() != 1 or not t.is_contiguous() or (t.numel() != numel if exact else t.numel() < numel):
+            raise L.LlxError(f"lookup_step: {name} must be a contiguous device {str(dt).removeprefix('torch.')} [{numel}{'' if exact else ' or more'}] "
+                             f"(got {t.dtype} {tuple(t.shape)})")
+    L.check(_lib().llx_lookup_step(L.ptr(picks), L.ptr(seq), seq.numel(), L.ptr(length), L.ptr(step_tok), L.ptr(step_pos), L.ptr(finished),
+                                   L.ptr(counters), int(P), int(n), int(k), int(g), int(eos_id) if eos_id is not None else -1, 1 if init else 0,
+                                   L.stream()), "llx_lookup_step")
+
+
 # ------------------------------------------------------------------------------------------------- cross entropy
 def head_compact_index(labels: Tensor) -> tuple[Tensor, Tensor, Tensor, Tensor]:
     """(idx, inv, labels_c, count) for the labelled rows (labels != -100) in order; everything stays on the device."""

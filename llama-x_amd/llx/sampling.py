@@ -40,3 +40,35 @@ def check_params(temperature: float, top_k: int, top_p: float, seed: int = 0) ->
         raise LlxError(f"top_p={top_p!r} must lie in (0, 1] (1 = off)")
     if not (isinstance(seed, int) and 0 <= seed <= _M64):
         raise LlxError(f"seed={seed!r} must be an unsigned 64-bit integer")
+
+
+# ---- prompt-lookup drafting: the host reference of csrc/lookup.hip (generate(draft_tokens=k)); pure lists of ints
+def lookup_draft(seq: list, g: int, k: int) -> list:
+    """k draft tokens for the continuation of `seq`: for gg = g .. 1 (shorter than seq) the most recent earlier occurrence of the last gg
+    tokens, seq[j : j + gg] == seq[-gg:] with j + gg <= len(seq) - 1; the first gg that has one wins, so a longer n-gram beats a more
+    recent shorter one.  The draft is what followed it, read from seq extended by the draft so far: an occurrence that overlaps the tail
+    continues periodically.  Without any match the last token is repeated."""
+    L = len(seq)
+    for gg in range(g, 0, -1):
+        if gg >= L:
+            continue
+        for j in range(L - gg - 1, -1, -1):
+            if seq[j : j + gg] == seq[L - gg :]:
+                ext = list(seq)
+                for i in range(k):
+                    ext.append(ext[j + gg + i])
+                return ext[L:]
+    return [seq[-1]] * k
+
+
+def lookup_accept(fed: list, picks: list, k: int, eos_id, room: int) -> tuple:
+    """(emitted tokens, finished) of a step that fed `fed` = [last token, k draft tokens] and whose k + 1 logits rows have the greedy
+    picks `picks`: with a the longest prefix of the draft that the picks confirm (fed[1 + i] == picks[i]), picks[0 .. a] are emitted,
+    cut to `room` tokens (>= 1) and after the first `eos_id` (None or -1: none) among them, which sets finished."""
+    a = 0
+    while a < k and fed[1 + a] == picks[a]:
+        a += 1
+    out = list(picks[: min(a + 1, room)])
+    if eos_id is not None and eos_id >= 0 and eos_id in out:
+        return out[: out.index(eos_id) + 1], True
+    return out, False

@@ -378,7 +378,8 @@ class Llama(nn.Module):
     def generate(self, prompt: Tensor, max_new_tokens: int, **kwargs) -> Tensor:
         """llx.generate.generate(self, ...): prefill + one forward and one on-device sampler launch per token (the reference has no
         generate(); its input_pos branch above is what this drives).  prompt [B, P] with B the cache's batch; prompt_lens=... for
-        right-padded prompts of different lengths."""
+        right-padded prompts of different lengths; draft_tokens=k (greedy, one sequence) feeds k prompt-lookup draft tokens with every
+        step and keeps the ones the model confirms: the same tokens in fewer weight passes."""
         from llx.generate import generate
 
         return generate(self, prompt, max_new_tokens, **kwargs)
