@@ -336,6 +336,21 @@ int llx_ce_fwd_bwd_rows(const void* logits, int64_t ld, void* dlogits, int64_t d
 int llx_ce_fwd_bwd_part(const void* logits, int64_t ld, void* dlogits, int64_t dld, const int64_t* labels, float* loss, void* workspace, int64_t T,
                         int64_t V, int64_t row0, int64_t nrows, const int32_t* rows, int phase, llx_stream_t s);
 
+/* ---- per-token log-probabilities: -F.cross_entropy(logits.float(), labels, reduction="none", ignore_index=-100), the per-row terms of
+ *      the mean above, with a per-row upstream gradient.  fwd: logp[t] = x[label] - lse[t] (0 / 0 on ignored rows), top1 (nullable) =
+ *      argmax of the row, lowest index among ties, -1 on ignored rows; one read of the row, the logits are kept.  bwd:
+ *      dlogits[t, v] = bf16(g[t] * ((v == label) - exp(x[t, v] - lse[t]))), one rounding; zero rows where ignored or g[t] == 0;
+ *      dlogits may alias logits.  rows (nullable): as llx_ce_fwd_bwd_rows - rows at or past *rows rounded up to 256 are not read;
+ *      fwd writes zeros there, bwd nothing. ------------------------------------------------------------------------------ */
+int llx_logprob_rows_fwd(const void* logits, int64_t ld, const int64_t* labels, float* logp, float* lse, int32_t* top1 /* nullable */,
+                         int64_t T, int64_t V, const int32_t* rows /* nullable */, llx_stream_t s);
+int llx_logprob_rows_bwd(const void* logits, int64_t ld, void* dlogits, int64_t dld, const int64_t* labels, const float* lse, const float* g,
+                         int64_t T, int64_t V, const int32_t* rows /* nullable */, llx_stream_t s);
+/* the [T] vectors between positions and compacted rows (logp / top1 through inv, the upstream gradient through idx), one launch:
+ * dst[i] = map[i] >= 0 ? src[map[i]] : fill, for a float vector and (nullable pair) an int32 vector */
+int llx_logprob_map_rows(const int32_t* map, const float* src_f, float* dst_f, float fill_f, const int32_t* src_i /* nullable */,
+                         int32_t* dst_i /* nullable */, int32_t fill_i, int64_t T, llx_stream_t s);
+
 /* ---- LoRA skinny contractions (modelling/lora.py:43 and its autograd): T = X.W^T -> [M,64] zero padded;
  *      G = s * U^T.Y with fp32 split partials (deterministic). --------------------------------------------------- */
 int llx_skinny_nt(const void* X, int64_t ldx, const void* W, int64_t ldw, void* out, int64_t M, int64_t K, int64_t R,

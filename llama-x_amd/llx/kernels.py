@@ -1202,6 +1202,61 @@ def ce_chunk(logits: Tensor, labels_all: Tensor, ws: Tensor, loss: Tensor, row0:
     return logits if write_grad else None
 
 
+def logprob_rows_fwd(logits: Tensor, labels: Tensor, rows: Optional[Tensor] = None, want_top1: bool = False):
+    """Per-row log-probabilities of `labels` under bf16 `logits` [T, V]: (logp, lse, top1), fp32 [T] each with zeros on ignored rows
+    (label -100); top1 (None unless want_top1) int32 [T], the row's argmax (lowest index among ties), -1 on ignored rows.  The logits
+    are only read.  rows (device int32): compacted rows (head_compact_index), only the first `rows` (rounded up to 256) exist."""
+    _chk_bf16(logits)
+    L.require_cuda(labels)
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    T, V = logits.shape
+    labels = labels.reshape(-1).contiguous()
+    assert labels.dtype is torch.int64 and labels.numel() == T and labels.device == logits.device
+    assert rows is None or (rows.dtype is torch.int32 and rows.numel() == 1 and rows.device == logits.device)
+    logp = torch.empty(T, device=logits.device, dtype=torch.float32)
+    lse = torch.empty(T, device=logits.device, dtype=torch.float32)
+    top1 = torch.empty(T, device=logits.device, dtype=torch.int32) if want_top1 else None
+    L.check(_lib().llx_logprob_rows_fwd(L.ptr(logits), logits.stride(0), L.ptr(labels), L.ptr(logp), L.ptr(lse), L.ptr(top1), T, V, L.ptr(rows),
+                                        L.stream()), "llx_logprob_rows_fwd")
+    return logp, lse, top1
+
+
+def logprob_rows_bwd(logits: Tensor, labels: Tensor, lse: Tensor, g: Tensor, rows: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """d logits = bf16(g[t] * (onehot(label) - softmax(logits[t]))) for the per-row upstream gradient g (fp32 [T]) and the forward's lse;
+    zero rows where the label is -100 or g is 0.  Written over `logits` (returned) unless `out` is given.  rows: as logprob_rows_fwd -
+    rows at or past `rows` rounded up to 256 are left untouched."""
+    _chk_bf16(logits, out)
+    L.require_cuda(labels, lse, g)
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    T, V = logits.shape
+    labels = labels.reshape(-1).contiguous()
+    assert labels.dtype is torch.int64 and labels.numel() == T and labels.device == logits.device
+    assert lse.dtype is torch.float32 and lse.is_contiguous() and lse.numel() == T and lse.device == logits.device
+    assert g.dtype is torch.float32 and g.is_contiguous() and g.numel() == T and g.device == logits.device
+    assert rows is None or (rows.dtype is torch.int32 and rows.numel() == 1 and rows.device == logits.device)
+    if out is None:
+        out = logits
+    assert out.shape == logits.shape and out.stride(1) == 1 and out.device == logits.device
+    L.check(_lib().llx_logprob_rows_bwd(L.ptr(logits), logits.stride(0), L.ptr(out), out.stride(0), L.ptr(labels), L.ptr(lse), L.ptr(g), T, V,
+                                        L.ptr(rows), L.stream()), "llx_logprob_rows_bwd")
+    return out
+
+
+def logprob_map_rows(index: Tensor, src: Tensor, fill: float = 0.0, src_i: Optional[Tensor] = None, fill_i: int = 0):
+    """dst[i] = src[index[i]] where index[i] >= 0, `fill` elsewhere (index int32 [T], src fp32 [T]); with src_i (int32 [T]) the same for
+    it from the same launch -> (dst, dst_i).  The per-row vectors of the compacted head rows back to their positions (index = inv), the
+    per-position upstream gradient to the compacted rows (index = idx)."""
+    L.require_cuda(index, src, src_i)
+    T = index.numel()
+    assert index.dtype is torch.int32 and index.is_contiguous() and src.dtype is torch.float32 and src.is_contiguous() and src.numel() == T
+    assert src_i is None or (src_i.dtype is torch.int32 and src_i.is_contiguous() and src_i.numel() == T)
+    dst = torch.empty_like(src)
+    dst_i = torch.empty_like(src_i) if src_i is not None else None
+    L.check(_lib().llx_logprob_map_rows(L.ptr(index), L.ptr(src), L.ptr(dst), float(fill), L.ptr(src_i), L.ptr(dst_i), int(fill_i), T, L.stream()),
+            "llx_logprob_map_rows")
+    return dst, dst_i
+
+
 # ------------------------------------------------------------------------------------------------- skinny (LoRA)
 def skinny_nt(x: Tensor, w: Tensor, kranges: Optional[Sequence[int]] = None, colscale: Optional[Tensor] = None):
     """[M,K] @ [R,K]^T -> [M,64] bf16, zero beyond column R.

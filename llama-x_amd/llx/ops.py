@@ -964,3 +964,132 @@ class HeadLossFn(Function):
             K.scale(dxn, dev_scalar=g32, out=dxn)
         dx, dnw = _norm_epilogue(dxn, x2, norm_w, rstd, ctx.needs_input_grad[1])
         return (dx.view(x.shape) if dx is not None else None, dnw, None, None, None, *grads)
+
+
+# =================================================================================================
+# final norm + LM head + per-token log-probabilities: -F.cross_entropy(..., reduction="none", ignore_index=-100)
+# =================================================================================================
+class HeadLogprobFn(Function):
+    """HeadLossFn's sibling for the per-row terms of its mean: fp32 [T] log-probabilities of the labels (0 at ignored positions), with the
+    row argmax as a second, non-differentiable output with want_top1.  Same routes: a plain head runs over the compacted labelled
+    rows (gather -> row-limited GEMM -> row kernel -> scatter through `inv`), any other head through its plan.  The upstream gradient is
+    per row, so - unlike the loss path, whose one scalar can be applied after the fact - d logits is not written in the forward: the
+    forward keeps the logits in the buffer where the loss path keeps d logits, and the backward turns them into d logits in place once
+    g is known (one bf16 rounding, the same traffic over forward + backward).  Without gradients nothing is saved, and a row set beyond
+    one logits buffer is walked in chunks (one GEMM and one row-kernel launch each; same per-row arithmetic, bit-identical)."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, norm_w: Tensor, labels: Tensor, eps: float, plan: LinearPlan, want_top1: bool, *tensors):
+        K.L.require_cuda(x, labels)
+        x2 = K._rows2d(x.contiguous())
+        xn, rstd = K.rmsnorm_fwd(x2, norm_w.detach(), eps)
+        need_grad = any(ctx.needs_input_grad) and not getattr(plan, "no_grad", False)  # (needs_input_grad does not see the caller's no_grad)
+        ctx.plan = plan
+        plain = not plan.int8 and plan.rank == 0 and plan.bias is None and plan.dora_m is None
+        ctx.plain_head = plain and not any(ctx.needs_input_grad[6:])
+        ctx.plain_trainable = plain and not ctx.plain_head and _HEAD_COMPACT
+        ctx.compact = _HEAD_COMPACT and plain
+        ctx.m_expect = None
+        T, V = x2.shape[0], plan.N
+        if need_grad and V % 64 != 0:  # (as the loss path: its d-hidden GEMM contracts over the vocabulary; said here, not in the middle of backward)
+            raise LlxError(f"token log-probabilities with gradients need a vocabulary that is a multiple of 64 (got {V}): the d-hidden GEMM "
+                           "contracts over it in 64-column steps - score under torch.no_grad() or pad the vocabulary")
+        chunk = _HEAD_CHUNK_ROWS if (_HEAD_CHUNK_FORCED or T * V * 2 >= 2**32) else 0
+        if chunk and T > chunk and need_grad:
+            raise LlxError(f"LM head over {T} rows x {V} vocabulary entries exceeds one logits buffer (4 GiB) and token log-probabilities "
+                           "with gradients are not chunked: score under torch.no_grad() or lower the number of positions per step")
+        labels_in = labels.reshape(-1).contiguous()
+        idx = inv = cnt = None
+        rows_in = xn
+        if ctx.compact:
+            idx, inv, labels_in, cnt = K.head_compact_index(labels)
+            rows_in = K.gather_rows(xn, idx, cnt)
+        if chunk and T > chunk:
+            parts = []
+            for r0 in range(0, T, chunk):
+                r1 = min(T, r0 + chunk)
+                if ctx.compact:
+                    cnt_c = torch.clamp(cnt - r0, min=0, max=r1 - r0).to(torch.int32)  # labelled rows inside this chunk
+                    lg = torch.empty(r1 - r0, V, device=x.device, dtype=BF16)
+                    K.gemm_nt(rows_in[r0:r1], plan.weight.detach(), out=lg, m_valid=cnt_c)
+                else:
+                    cnt_c = None
+                    lg, _ = plan.forward(rows_in[r0:r1])
+                parts.append(K.logprob_rows_fwd(lg, labels_in[r0:r1], rows=cnt_c, want_top1=want_top1))
+            logp = torch.cat([p[0] for p in parts])
+            top1 = torch.cat([p[2] for p in parts]) if want_top1 else None
+            return HeadLogprobFn._finish(ctx, logp, top1, inv)
+        t = None
+        if ctx.compact:
+            logits = torch.empty(T, V, device=x.device, dtype=BF16)
+            ctx.m_expect = float(cnt.item()) if K.GEMM_TRACE is not None else None  # accounting of the traced eager step only
+            K.gemm_nt(rows_in, plan.weight.detach(), out=logits, m_valid=cnt, m_expect=ctx.m_expect)
+        else:
+            logits, t = plan.forward(xn)
+        logp, lse, top1 = K.logprob_rows_fwd(logits, labels_in, rows=cnt, want_top1=want_top1)
+        if need_grad:
+            keep_rows = rows_in if (ctx.plain_trainable or not (ctx.plain_head or ctx.plain_trainable)) else None
+            _save(ctx, x, norm_w, x2, keep_rows, rstd, logits, lse, labels_in, (idx, inv, cnt), t)
+        return HeadLogprobFn._finish(ctx, logp, top1, inv)
+
+    @staticmethod
+    def _finish(ctx, logp: Tensor, top1: Optional[Tensor], inv: Optional[Tensor]):
+        if inv is not None:  # compacted rows back to their positions: [T] vectors, zeros / -1 at the ignored positions
+            logp, top1 = K.logprob_map_rows(inv, logp, 0.0, top1, -1)
+        if top1 is None:
+            return logp
+        ctx.mark_non_differentiable(top1)
+        return logp, top1
+
+    @staticmethod
+    def backward(ctx, g: Tensor, *_):
+        plan: LinearPlan = ctx.plan
+        if getattr(ctx, "consumed", False):
+            raise LlxError("token log-probabilities: a second backward through the same forward - the saved logits were turned into "
+                           "d logits in place by the first one; run the forward again")
+        ctx.consumed = True
+        x, norm_w, x2, xn, rstd, logits, lse, labels_in, (idx, inv, cnt), t = _load(ctx)
+        needs = ctx.needs_input_grad[6:]
+        g32 = g.detach().to(torch.float32).reshape(-1).contiguous()
+        if idx is not None:  # the upstream gradient of the j-th labelled row (rows past the count are ignored rows: any value)
+            g32, _ = K.logprob_map_rows(idx, g32)
+        dlogits = K.logprob_rows_bwd(logits, labels_in, lse, g32, rows=cnt)  # in place: the saved logits become d logits
+        need_dxn = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        if ctx.plain_head or ctx.plain_trainable:
+            # d hidden through the calls of HeadLossFn.backward without its scalar (the same K split: bit-identical products)
+            dx = dnw = None
+            if need_dxn:
+                wt = weight_t(plan.weight)
+                if wt.shape[1] % (64 * _HEAD_SPLITK) == 0:
+                    dxn = K.gemm_nt_splitk(dlogits, wt, _HEAD_SPLITK, m_valid=cnt, inv=inv, m_expect=ctx.m_expect)
+                elif ctx.compact:
+                    dxn = K.scatter_rows(K.gemm_nt(dlogits, wt, m_valid=cnt, m_expect=ctx.m_expect), inv)
+                else:
+                    dxn = K.gemm_nt(dlogits, wt)
+                dx, dnw = _norm_epilogue(dxn, x2, norm_w, rstd, ctx.needs_input_grad[1])
+            gw = K.gemm_tn(dlogits, xn, m_valid=cnt, m_expect=ctx.m_expect) if ctx.plain_trainable else None
+            return (dx.view(x.shape) if dx is not None else None, dnw, None, None, None, None, *([gw] + [None] * (len(needs) - 1) if needs else []))
+        dxn, grads = plan.backward(dlogits, xn, t, needs, need_dx=need_dxn)
+        dx, dnw = _norm_epilogue(dxn, x2, norm_w, rstd, ctx.needs_input_grad[1])
+        return (dx.view(x.shape) if dx is not None else None, dnw, None, None, None, None, *grads)
+
+
+def _check_labels(labels, shape, device, what: str) -> None:
+    if not isinstance(labels, Tensor) or labels.dtype is not torch.int64:
+        raise LlxError(f"{what}: labels must be an int64 tensor (got {getattr(labels, 'dtype', type(labels).__name__)})")
+    if tuple(labels.shape) != tuple(shape):
+        raise LlxError(f"{what}: labels {tuple(labels.shape)} must have the shape of tokens {tuple(shape)}")
+    if not labels.is_cuda or labels.device != device:
+        raise LlxError(f"{what}: labels live on {labels.device}, the hidden states on {device}: both must be on the same GPU")
+
+
+def head_logprobs(x: Tensor, norm: nn.Module, output: nn.Linear, labels: Tensor, return_top1: bool = False):
+    """fp32 log-probabilities [*labels.shape] of `labels` under output(norm(x)), 0 at labels == -100; with return_top1 also the int32
+    argmax of every labelled position (-1 at the others)."""
+    _check_labels(labels, x.shape[:-1], x.device, "token_logprobs")
+    plan = LinearPlan(output)
+    plan.no_grad = not torch.is_grad_enabled()  # (inside Function.forward grad mode is always off: noted here)
+    out = HeadLogprobFn.apply(x, norm.weight, labels, norm.eps, plan, bool(return_top1), *plan.tensors())
+    if return_top1:
+        return out[0].view(labels.shape), out[1].view(labels.shape)
+    return out.view(labels.shape)

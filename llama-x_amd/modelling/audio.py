@@ -14,7 +14,7 @@ from typing import NamedTuple
 import torch
 from torch import Tensor, nn
 
-from llx import audio_ops
+from llx import audio_ops, ops
 from llx._lib import LlxError
 
 from .llama import Llama, LlamaConfig, _get_hf_config, _get_hf_state_dict
@@ -59,6 +59,15 @@ class LlamaAudio(Llama):
         if n_audio:
             x = x[:, n_audio:]  # remove audio embs
         return self._head(x, labels)
+
+    def token_logprobs(self, audio: Tensor | None, tokens: Tensor, labels: Tensor, *, block_mask=None, return_top1: bool = False):
+        """Llama.token_logprobs over the text positions ([B, St]): as in forward, the audio prefix is dropped before the head."""
+        ops._check_labels(labels, tokens.shape, tokens.device, "token_logprobs")
+        x, n_audio = self._embed(tokens, audio)
+        x = self._run_layers(x, self.rope[: x.shape[1]], mask=None, input_pos=None, block_mask=block_mask)
+        if n_audio:
+            x = x[:, n_audio:]  # remove audio embs
+        return ops.head_logprobs(x, self.norm, self.output, labels, return_top1)
 
     @staticmethod
     def from_hf(model_id: str, **kwargs):
