@@ -453,6 +453,30 @@ int llx_sample_rows(const void* logits, int dtype, int64_t ld, int64_t R, int64_
 int llx_lookup_step(const int64_t* picks, int64_t* seq, int64_t cap, int64_t* len, int64_t* step_tok, int64_t* step_pos, int32_t* finished,
                     int64_t* counters, int64_t P, int64_t n, int k, int g, int64_t eos_id, int init, llx_stream_t s);
 
+/* ---- beam search (generate(num_beams=W), llx/generate.py; the rule is llx.sampling.beam_shortlist / beam_step).  Three
+ *      launches per step, no host read.
+ *      llx_beam_rows: logits [W, V] (dtype 0 = bf16, 1 = fp32; row stride ld >= V elements, rows may start at any element; V > W) ->
+ *      cand_score fp32 / cand_token int32 [W, W + 1]: log-probability (z - zmax) - log sum exp(z - zmax) and index of each row's W + 1
+ *      best tokens by (logit descending, index ascending).  The sum is over floor(expf(z - zmax) * 2^40) in uint64.
+ *      llx_beam_merge: orders the W * (W + 1) candidates by (s[r] + cand_score descending, row, rank) and walks them: a token eos_id
+ *      (-1: none) is a finished hypothesis of final score score / len^length_penalty (len = tokens generated, the eos counted) that
+ *      enters the bank if there is room or it beats the worst entry; any other becomes live beam j: parent[j] = r (int32 [W]), tok[j]
+ *      (int64 [W], the next step's input), s[j] (fp32 [W]); the walk stops at W live beams.  hist int64 [W, n] (row stride hist_ld) is
+ *      permuted by parent and appended to; bank_tok int64 [W, n] (row stride bank_ld), bank_len int32 [W], bank_score fp32 [W];
+ *      meta int32 [3] = (hypotheses in the bank, done, tokens generated).  done is set when the bank holds W or n tokens are generated;
+ *      the live beams are then offered to the bank with s / len^length_penalty.  init != 0: the first step after the prefill - the
+ *      state is not read and only row 0 takes part.  A launch that finds done set writes parent = identity and nothing else.
+ *      llx_kv_reorder_rows: table = DEVICE array of n_caches base pointers of bf16 caches [>= W, KVH, Smax, 128] with the common
+ *      element strides sb, sh, ss (multiples of 8; last dim dense), parent = DEVICE int32 [W] (a value outside [0, W) reads as "stays"):
+ *      cache[b, :, :len] <- cache[parent[b], :, :len], b < W, in place in every cache.  Slots with parent[b] == b, positions >= len
+ *      and slots >= W are not written.  W in 2..16, len in [1, Smax], head_dim 128. ------------------------------------------------ */
+int llx_beam_rows(const void* logits, int dtype, int64_t ld, int64_t W, int64_t V, float* cand_score, int32_t* cand_token, llx_stream_t s);
+int llx_beam_merge(const float* cand_score, const int32_t* cand_token, float* s, int32_t* parent, int64_t* tok, int64_t* hist, int64_t hist_ld,
+                   int64_t* bank_tok, int64_t bank_ld, int32_t* bank_len, float* bank_score, int32_t* meta, int64_t W, int64_t n,
+                   int64_t eos_id, float length_penalty, int init, llx_stream_t stream);
+int llx_kv_reorder_rows(const void* const* table, int64_t n_caches, int64_t sb, int64_t sh, int64_t ss, const int32_t* parent, int64_t W,
+                        int64_t KVH, int64_t len, int64_t Smax, int64_t head_dim, llx_stream_t s);
+
 /* ---- small utilities of the backward pass ---------------------------------------------------------------------- */
 int llx_scale(const void* x, int64_t x_ld, void* y, int64_t y_ld, const float* dev_scalar, float host_scale, const void* colscale,
               int64_t rows, int64_t cols, llx_stream_t s);   /* (g * scale) of subclasses/int8.py:127; loss-scale of dX */

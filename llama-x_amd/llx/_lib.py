@@ -123,6 +123,9 @@ SIGNATURES: dict[str, tuple] = {
     "llx_gemm_nt_bf16_rope": (c_int, [_P, _L, _P, _L, _P, _L, _L, _L, _L, _P, _L, _P, _L, _L, _P, _L, _L, _P]),
     "llx_sample_rows": (c_int, [_P, _I, _L, _L, _L, _F, _L, _F, c_uint64, _P, _P, _P, _L, _L, _L, _I, _L, _P, _P, _P, _P, _P]),
     "llx_lookup_step": (c_int, [_P, _P, _L, _P, _P, _P, _P, _P, _L, _L, _I, _I, _L, _I, _P]),
+    "llx_beam_rows": (c_int, [_P, _I, _L, _L, _L, _P, _P, _P]),
+    "llx_beam_merge": (c_int, [_P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _L, _L, _L, _F, _I, _P]),
+    "llx_kv_reorder_rows": (c_int, [_P, _L, _L, _L, _L, _P, _L, _L, _L, _L, _L, _P]),
 }
 
 # include/llx_debug.h: diagnostic probes, bound for tools/ only

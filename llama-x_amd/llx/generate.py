@@ -8,6 +8,10 @@ stalled by an `.item()`.  With `eos_id` the host looks at the finished flag once
 generate(draft_tokens=k) is the greedy loop with prompt-lookup drafts: a step feeds the last token and k draft tokens found in the sequence
 itself as one k + 1-row call of the batch-1 decode path (llx/decode.py: up to four rows for one pass over the weights) and keeps the
 prefix of the draft that the model confirms; accepting, appending and drafting are one launch of csrc/lookup.hip.
+
+generate(num_beams=W) is beam search: the W beams of one prompt are the W rows of a batched decode step, and choosing the next beams, the
+hypothesis bookkeeping and moving each surviving beam's keys and values to its cache slot are three launches of csrc/beam.hip (DESIGN
+8.17).  generate(audio=clips) drives a LlamaAudio: clip and prompt are prefilled as one sequence, the decode steps feed text tokens.
 """
 from __future__ import annotations
 
@@ -25,13 +29,15 @@ from .sampling import check_params
 MAX_NGRAM = 8  # the longest n-gram a lookup draft matches (csrc/lookup.hip)
 
 
-def _check(model, prompt: Tensor, max_new_tokens: int, eos_id, prefill_chunk, check_every, prompt_lens=None, draft=None) -> Optional[list]:
+def _check(model, prompt: Tensor, max_new_tokens: int, eos_id, prefill_chunk, check_every, prompt_lens=None, draft=None, beams=None,
+           audio=None) -> Optional[list]:
     """Raises LlxError on anything generate() cannot run, before any launch; returns the prompt lengths as a list (None: every row is P).
-    draft: (draft_tokens, draft_ngram, temperature) of a call with draft_tokens != 0."""
+    draft: (draft_tokens, draft_ngram, temperature) of a call with draft_tokens != 0; beams: (num_beams, length_penalty, temperature,
+    top_k, top_p, draft_tokens) of a call with num_beams != 1; audio: the clips of a call with audio."""
     from modelling.llama import Llama
 
-    if not isinstance(model, Llama) or type(model)._embed is not Llama._embed:
-        raise LlxError(f"generate() drives a text Llama (got {type(model).__name__})")
+    if not isinstance(model, Llama):
+        raise LlxError(f"generate() drives a Llama or a LlamaAudio (got {type(model).__name__})")
     if model.training:
         raise LlxError("generate() needs the model in eval mode: call model.eval()")
     if any(layer.attention.kv_cache is None for layer in model.layers) or not hasattr(model, "causal_mask"):
@@ -39,7 +45,9 @@ def _check(model, prompt: Tensor, max_new_tokens: int, eos_id, prefill_chunk, ch
     if not (isinstance(prompt, Tensor) and prompt.dtype is torch.int64 and prompt.dim() == 2 and prompt.shape[0] >= 1 and prompt.shape[1] >= 1):
         raise LlxError("generate(): prompt must be an int64 tensor [B, P] with B, P >= 1")
     cache_b = model.layers[0].attention.kv_cache.k_cache.shape[0]
-    if prompt.shape[0] != cache_b:
+    if beams is not None:
+        _check_beams(prompt, prompt_lens, cache_b, *beams)
+    elif prompt.shape[0] != cache_b:
         raise LlxError(f"generate(): a batch of {prompt.shape[0]} prompts against a KV cache of batch {cache_b}: "
                        f"call model.build_cache(inference=True, batch_size={prompt.shape[0]})")
     lens = None
@@ -51,13 +59,15 @@ def _check(model, prompt: Tensor, max_new_tokens: int, eos_id, prefill_chunk, ch
             raise LlxError(f"prompt_lens {lens} must lie in [1, {prompt.shape[1]}] (prompt is right-padded to P = {prompt.shape[1]})")
     if draft is not None:
         _check_draft(model, prompt, max_new_tokens, lens, *draft)
+    n_audio = _check_audio(model, prompt, audio, prefill_chunk, draft) if audio is not None else 0
     if not prompt.is_cuda or model.tok_embeddings.weight.device != prompt.device:
         raise LlxError("generate() runs on the HIP device: model and prompt must be on the same GPU")
     if not (isinstance(max_new_tokens, int) and max_new_tokens >= 1):
         raise LlxError(f"max_new_tokens={max_new_tokens!r} must be an integer >= 1")
     longest = max(lens) if lens is not None else prompt.shape[1]
-    if longest + max_new_tokens > model.config.max_seq_len:
-        raise LlxError(f"prompt ({longest}) + max_new_tokens ({max_new_tokens}) exceeds max_seq_len ({model.config.max_seq_len})")
+    if n_audio + longest + max_new_tokens > model.config.max_seq_len:
+        raise LlxError(f"{f'audio ({n_audio} positions) + ' if audio is not None else ''}prompt ({longest}) + max_new_tokens ({max_new_tokens}) "
+                       f"exceeds max_seq_len ({model.config.max_seq_len})")
     if eos_id is not None and not (isinstance(eos_id, int) and 0 <= eos_id < model.config.vocab_size):
         raise LlxError(f"eos_id={eos_id!r} must be a token id in [0, {model.config.vocab_size})")
     if prefill_chunk is not None and not (isinstance(prefill_chunk, int) and prefill_chunk >= 1):
@@ -65,6 +75,54 @@ def _check(model, prompt: Tensor, max_new_tokens: int, eos_id, prefill_chunk, ch
     if not (isinstance(check_every, int) and check_every >= 1):
         raise LlxError(f"check_every={check_every!r} must be an integer >= 1")
     return lens
+
+
+def _check_beams(prompt: Tensor, prompt_lens, cache_b: int, W, length_penalty, temperature, top_k, top_p, draft_tokens) -> None:
+    """The conditions of generate(num_beams=W), W != 1: one prompt, a cache slot per beam, and none of the arguments that choose tokens
+    another way."""
+    if not (isinstance(W, int) and not isinstance(W, bool) and 2 <= W <= D.MAX_BATCH):
+        raise LlxError(f"num_beams={W!r} must be an integer in 1..{D.MAX_BATCH} (the beams of a step are the rows of one batched decode step)")
+    if prompt.shape[0] != 1 or prompt_lens is not None:
+        raise LlxError(f"num_beams={W} searches the continuations of one prompt: prompt [1, P] and no prompt_lens "
+                       f"(got {prompt.shape[0]} rows, prompt_lens {prompt_lens!r})")
+    if cache_b != W:
+        raise LlxError(f"num_beams={W} against a KV cache of batch {cache_b}: every beam has a cache slot, "
+                       f"call model.build_cache(inference=True, batch_size={W})")
+    if temperature != 0 or top_k != 0 or top_p != 1:
+        raise LlxError(f"num_beams={W} ranks hypotheses by their log-probability: temperature={temperature!r}, top_k={top_k!r} and "
+                       f"top_p={top_p!r} must stay 0, 0 and 1")
+    if draft_tokens != 0:
+        raise LlxError(f"num_beams={W} cannot be combined with draft_tokens={draft_tokens!r}: a draft step holds the rows of one sequence")
+    if not (isinstance(length_penalty, (int, float)) and not isinstance(length_penalty, bool) and length_penalty - length_penalty == 0):
+        raise LlxError(f"length_penalty={length_penalty!r} must be a finite number (final score = log-probability / length ** length_penalty)")
+
+
+def _check_audio(model, prompt: Tensor, audio, prefill_chunk, draft) -> int:
+    """The conditions of generate(audio=...); returns the number of positions the clips take in front of the prompt."""
+    from modelling.audio import LlamaAudio
+
+    if not isinstance(model, LlamaAudio):
+        raise LlxError(f"audio= needs a LlamaAudio (got {type(model).__name__})")
+    if not (isinstance(audio, Tensor) and audio.dtype is torch.float32 and audio.dim() == 2 and audio.shape[0] == prompt.shape[0]
+            and audio.shape[1] >= model.audio_config.hop_length):
+        raise LlxError(f"audio must be an fp32 tensor [B, samples] with B = {prompt.shape[0]} rows, one clip of at least "
+                       f"{model.audio_config.hop_length} samples per prompt")
+    if prefill_chunk is not None:
+        raise LlxError(f"prefill_chunk={prefill_chunk!r} with audio: the clip and the prompt are prefilled as one call")
+    if draft is not None:
+        raise LlxError(f"draft_tokens={draft[0]!r} with audio: drafting drives a text sequence")
+    if audio.device != prompt.device:
+        raise LlxError("generate(): audio and prompt must be on the same device")
+    return model.audio_positions(audio.shape[1])
+
+
+def _caller(model):
+    """call(tokens, input_pos): one call of the model on the inference path.  A LlamaAudio takes the clip first; decode steps have none."""
+    from modelling.audio import LlamaAudio
+
+    if isinstance(model, LlamaAudio):
+        return lambda tok, pos: model(None, tok, input_pos=pos)
+    return lambda tok, pos: model(tok, input_pos=pos)
 
 
 def _check_draft(model, prompt: Tensor, max_new_tokens, lens, k, g, temperature) -> None:
@@ -141,9 +199,29 @@ def prefill(model, prompt: Tensor, prompt_lens: Optional[Sequence[int]] = None, 
     return model._head(hidden.contiguous(), None)
 
 
-def _generate_batch(model, prompt: Tensor, n: int, lens: list, sampling: dict, eos_id, prefill_chunk, check_every: int) -> Tensor:
+def prefill_audio(model, audio: Tensor, prompt: Tensor, prompt_lens: Optional[Sequence[int]] = None) -> Tensor:
+    """prefill() for a LlamaAudio with clips: one model(audio, prompt, input_pos=arange(A + P)) call under the causal mask, A = the
+    positions of the clips; the text tokens sit at A .. A + P - 1.  Returns the logits [B, 1, V] of each sequence's last prompt token."""
+    if prompt_lens is not None:
+        prompt = prompt[:, : max(prompt_lens)]
+    B, P = prompt.shape
+    A = model.audio_positions(audio.shape[1])
+    logits = model(audio, prompt, input_pos=torch.arange(A + P, device=prompt.device))  # [B, P, V]: the audio positions are dropped
+    if prompt_lens is None:
+        return logits[:, -1:]
+    last = torch.tensor(prompt_lens, device=prompt.device, dtype=torch.int64) - 1
+    return logits.gather(1, last.view(B, 1, 1).expand(B, 1, logits.shape[2]))
+
+
+def _generate_batch(model, prompt: Tensor, n: int, lens: list, sampling: dict, eos_id, prefill_chunk, check_every: int, call,
+                    audio: Optional[Tensor] = None) -> Tensor:
     dev, B = prompt.device, prompt.shape[0]
-    logits = prefill(model, prompt, lens, prefill_chunk)
+    if audio is not None:
+        logits = prefill_audio(model, audio, prompt, lens)
+        A = model.audio_positions(audio.shape[1])
+        lens = [A + v for v in lens]  # from here on a length is the sequence's: clip and prompt
+    else:
+        logits = prefill(model, prompt, lens, prefill_chunk)
     cols, base, shifts = history_plan(lens, n)
     start = torch.tensor(lens, device=dev, dtype=torch.int64) - 1
     pos = start.clone()  # per row: the position of the logits row being sampled from = the draw counter; the sampler advances it
@@ -164,7 +242,7 @@ def _generate_batch(model, prompt: Tensor, n: int, lens: list, sampling: dict, e
         if k == n:
             break
         # a finished row feeds eos_id at its frozen position: it re-writes its own cache row there, nothing else
-        K.sample(model(tok, input_pos=pos[:, None])[:, 0], **kw)
+        K.sample(call(tok, pos[:, None])[:, 0], **kw)
     counts = pos - start if finished is not None else torch.full((B,), n, device=dev, dtype=torch.int64)
     return history_rows(history, shifts, counts, T, eos_id if eos_id is not None else 0)
 
@@ -199,7 +277,7 @@ def _draft_rows(model, k: int, dev) -> int:
     return k
 
 
-def _generate_draft(model, prompt: Tensor, logits: Tensor, n: int, k: int, g: int, eos_id, check_every: int, stats) -> Tensor:
+def _generate_draft(model, prompt: Tensor, logits: Tensor, n: int, k: int, g: int, eos_id, check_every: int, stats, call) -> Tensor:
     """The decode loop of generate(draft_tokens=k) after the prefill (`logits`: the prefill's last call).  Per step: one model call on the
     k + 1 rows of step_tok at step_pos, one sampler launch (the greedy pick of every row), one llx_lookup_step launch (accept, append,
     draft, the next step's rows) - nothing reads the host."""
@@ -224,7 +302,7 @@ def _generate_draft(model, prompt: Tensor, logits: Tensor, n: int, k: int, g: in
                 total, steps, accepted, fin = torch.cat((st, finished.to(torch.int64))).tolist()
                 if fin or total == P + n or s == n:
                     break
-            K.sample(model(step_tok[None], input_pos=step_pos)[0], temperature=0.0, pos=draw, out=picks)
+            K.sample(call(step_tok[None], step_pos)[0], temperature=0.0, pos=draw, out=picks)
             K.lookup_step(picks, seq, length, step_tok, step_pos, finished, counters, **kw)
     if stats is not None:
         stats.update(steps=steps, tokens=total - P, accepted=accepted, draft_tokens=k, launched=s - 1,
@@ -232,10 +310,59 @@ def _generate_draft(model, prompt: Tensor, logits: Tensor, n: int, k: int, g: in
     return seq[None, P:total]
 
 
+# ---- beam search (generate(num_beams=W)): the W beams of one prompt are the W rows of a batched decode step
+def _generate_beam(model, call, prompt: Tensor, audio, n: int, W: int, length_penalty: float, eos_id, prefill_chunk, check_every: int,
+                   stats) -> Tensor:
+    """The loop of generate(num_beams=W).  The prompt (and the clip) is prefilled in all W cache slots; per step: one model call on tok
+    [W, 1] at the shared position, then beam_rows (the shortlists), beam_merge (the walk and all bookkeeping) and kv_reorder_rows (slot b
+    takes over the keys and values of its parent) - nothing reads the host.  The beams' token k sits at position base + k - 1."""
+    dev = prompt.device
+    if audio is not None:
+        logits = prefill_audio(model, audio.expand(W, -1).contiguous(), prompt.expand(W, -1).contiguous())[:, 0]
+        base = model.audio_positions(audio.shape[1]) + prompt.shape[1]
+    else:
+        logits = prefill(model, prompt.expand(W, -1).contiguous(), None, prefill_chunk)[:, 0]
+        base = prompt.shape[1]
+    cand_score = torch.empty(W, W + 1, device=dev, dtype=torch.float32)
+    cand_token = torch.empty(W, W + 1, device=dev, dtype=torch.int32)
+    s = torch.zeros(W, device=dev, dtype=torch.float32)
+    parent = torch.zeros(W, device=dev, dtype=torch.int32)
+    tok = torch.zeros(W, 1, device=dev, dtype=torch.int64)
+    hist = torch.zeros(W, n, device=dev, dtype=torch.int64)
+    bank_tok = torch.zeros(W, n, device=dev, dtype=torch.int64)
+    bank_len = torch.zeros(W, device=dev, dtype=torch.int32)
+    bank_score = torch.zeros(W, device=dev, dtype=torch.float32)
+    meta = torch.zeros(3, device=dev, dtype=torch.int32)  # hypotheses in the bank, done, tokens generated
+    table = K.kv_cache_table(c for layer in model.layers for c in (layer.attention.kv_cache.k_cache, layer.attention.kv_cache.v_cache))
+    positions = torch.arange(base, base + n, device=dev)
+    state = (cand_score, cand_token, s, parent, tok, hist, bank_tok, bank_len, bank_score, meta)
+    kw = dict(n=n, eos_id=eos_id, length_penalty=length_penalty)
+    K.beam_rows(logits, cand_score, cand_token)
+    K.beam_merge(*state, init=True, **kw)  # all slots hold the same keys and values: nothing to move
+    for k in range(1, n + 1):
+        # without an eos_id nothing finishes early: the n-th merge sets done.  With one, one host read every check_every steps; a done
+        # state is frozen, the steps launched since then moved nothing
+        if k == n or (eos_id is not None and k % check_every == 0 and int(meta[1].item())):
+            break
+        K.beam_rows(call(tok, positions[k - 1 : k])[:, 0], cand_score, cand_token)
+        K.beam_merge(*state, **kw)
+        K.kv_reorder_rows(table, parent, base + k)
+    # the one read that ends the loop (token ids and lengths are exact in fp64)
+    count, _, steps, *rest = torch.cat((meta.double(), bank_len.double(), bank_score.double(), bank_tok.flatten().double())).tolist()
+    count = int(count)
+    lens, scores, toks = rest[:W], rest[W : 2 * W], rest[2 * W :]
+    order = sorted(range(count), key=lambda i: (-scores[i], i))
+    beams = [([int(t) for t in toks[i * n : i * n + int(lens[i])]], scores[i]) for i in order]
+    if stats is not None:
+        stats.update(steps=int(steps), tokens=len(beams[0][0]), accepted=0, draft_tokens=0, launched=k - 1, num_beams=W, beams=beams)
+    return torch.tensor(beams[0][0], dtype=torch.int64)[None].to(dev)
+
+
 @torch.no_grad()
 def generate(model, prompt: Tensor, max_new_tokens: int, *, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
              eos_id: Optional[int] = None, prefill_chunk: Optional[int] = None, check_every: int = 16, prompt_lens=None,
-             draft_tokens: int = 0, draft_ngram: int = 3, stats: Optional[dict] = None) -> Tensor:
+             draft_tokens: int = 0, draft_ngram: int = 3, stats: Optional[dict] = None, num_beams: int = 1, length_penalty: float = 1.0,
+             audio: Optional[Tensor] = None) -> Tensor:
     """Continue `prompt` (int64 [B, P], B = the batch the KV cache was built for) by up to `max_new_tokens` tokens -> int64 [B, n_new] on
     the prompt's device.  `prompt_lens` (B lengths in [1, P], a sequence or an int64 tensor, read once on the host before the first
     launch): the rows of `prompt` are right-padded prompts of these lengths; default: every row is P long.  For a batch the result is as
@@ -271,31 +398,55 @@ def generate(model, prompt: Tensor, max_new_tokens: int, *, temperature: float =
     `stats` (a dict) receives, from the one host read that ends the loop: "steps" (model calls that yielded tokens, the prefill's last row
     counted as one), "tokens" (= len(result)), "accepted" (draft tokens in the result: tokens - steps), "draft_tokens" (the k that ran)
     and "launched" (decode steps launched, the frozen ones included); with drafting also "state", the device tensors of the loop (seq,
-    len, step_tok, step_pos, finished, counters), not read.  Without drafting the numbers come from the loop itself, without a read."""
+    len, step_tok, step_pos, finished, counters), not read.  Without drafting the numbers come from the loop itself, without a read.
+
+    `num_beams` = W in 2..16 (one prompt [1, P], a cache built with batch_size=W, greedy arguments only; 1, the default, is everything
+    above): beam search by the rule of sampling.beam_step.  The W beams are the W rows of one batched decode step at a
+    shared position, so a step streams the weights once; choosing the next beams, the bookkeeping and moving every surviving beam's keys
+    and values to its cache slot are three launches (csrc/beam.hip), nothing is read by the host inside a step, and the done flag is
+    read once every `check_every` steps.  A hypothesis that ends in `eos_id` is ranked by log-probability / length ** `length_penalty`
+    (the eos counted); the search ends when W hypotheses have finished or after `max_new_tokens` tokens, when the live beams are ranked
+    the same way.  The result is the best hypothesis, int64 [1, T], ending at its eos inclusive; `stats` also receives "beams": every
+    hypothesis kept as (tokens, final score), best first.  The prompt is prefilled in all W slots.
+
+    `audio` (fp32 [B, samples], with a LlamaAudio; LlamaAudio.generate(audio, prompt, n) is the method form): the clips are prefilled
+    in front of the prompts as one call under the causal mask and take A = model.audio_positions(samples) positions, so the text sits at
+    A .. A + P - 1, A + P + max_new_tokens <= max_seq_len, and the draw counter of a sampled token is its position, A included.  The
+    decode steps feed text tokens only.  `prefill_chunk` and `draft_tokens` are refused with audio; without it a LlamaAudio generates
+    as a text model."""
     check_params(temperature, top_k, top_p, seed)
     lens = _check(model, prompt, max_new_tokens, eos_id, prefill_chunk, check_every, prompt_lens,
-                  (draft_tokens, draft_ngram, temperature) if draft_tokens != 0 else None)
+                  (draft_tokens, draft_ngram, temperature) if draft_tokens != 0 else None,
+                  (num_beams, length_penalty, temperature, top_k, top_p, draft_tokens) if num_beams != 1 else None, audio)
     D.prepare(model)
     dev, P, n = prompt.device, prompt.shape[1], max_new_tokens
+    call = _caller(model)
+    if num_beams != 1:
+        return _generate_beam(model, call, prompt, audio, n, num_beams, float(length_penalty), eos_id, prefill_chunk, check_every, stats)
     if prompt.shape[0] > 1 or (lens is not None and lens != [P]):
         return _generate_batch(model, prompt, n, lens if lens is not None else [P] * prompt.shape[0],
-                               dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed), eos_id, prefill_chunk, check_every)
-    chunk = P if prefill_chunk is None else prefill_chunk
-    positions = torch.arange(P, device=dev)
-    # forward rotates a call's tokens by rope[:L] whatever input_pos says (the reference's modelling/llama.py:207).  For one whole-prompt
-    # call that is each token's own position; a later chunk must see the same rows, or chunking - a memory measure - would change the
-    # result: the chunk runs with the table shifted to its first position.  Decode steps below keep rope[:1], as a hand loop does.
-    table = model.rope
-    try:
-        for s in range(0, P, chunk):
-            model.rope = table[s:]
-            logits = model(prompt[:, s : s + chunk], input_pos=positions[s : s + chunk])
-    finally:
-        model.rope = table
+                               dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed), eos_id, prefill_chunk, check_every, call, audio)
+    if audio is not None:
+        logits = prefill_audio(model, audio, prompt)
+        P += model.audio_positions(audio.shape[1])  # from here on P is the length of the sequence: clip and prompt
+    else:
+        chunk = P if prefill_chunk is None else prefill_chunk
+        positions = torch.arange(P, device=dev)
+        # forward rotates a call's tokens by rope[:L] whatever input_pos says (the reference's modelling/llama.py:207).  For one
+        # whole-prompt call that is each token's own position; a later chunk must see the same rows, or chunking - a memory measure -
+        # would change the result: the chunk runs with the table shifted to its first position.  Decode steps below keep rope[:1], as a
+        # hand loop does.
+        table = model.rope
+        try:
+            for s in range(0, P, chunk):
+                model.rope = table[s:]
+                logits = call(prompt[:, s : s + chunk], positions[s : s + chunk])
+        finally:
+            model.rope = table
     if draft_tokens != 0:
         draft_tokens = _draft_rows(model, draft_tokens, dev)
     if draft_tokens != 0:
-        return _generate_draft(model, prompt, logits, n, draft_tokens, draft_ngram, eos_id, check_every, stats)
+        return _generate_draft(model, prompt, logits, n, draft_tokens, draft_ngram, eos_id, check_every, stats, call)
     pos = torch.full((1,), P - 1, device=dev, dtype=torch.int64)  # position of the row being sampled from; the sampler advances it
     tok = torch.empty(1, 1, device=dev, dtype=torch.int64)
     history = torch.empty(1, n, device=dev, dtype=torch.int64)
@@ -313,7 +464,7 @@ def generate(model, prompt: Tensor, max_new_tokens: int, *, temperature: float =
                 break
         if k == n:
             break
-        K.sample(model(tok, input_pos=pos)[0], **kw)
+        K.sample(call(tok, pos)[0], **kw)
     if stats is not None:
         stats.update(steps=count, tokens=count, accepted=0, draft_tokens=0, launched=k - 1)
     return history[:, :count]

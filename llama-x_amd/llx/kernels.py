@@ -1133,6 +1133,80 @@ def lookup_step(picks: Tensor, seq: Tensor, length: Tensor, step_tok: Tensor, st
                                    L.stream()), "llx_lookup_step")
 
 
+# ------------------------------------------------------------------------------------------------- beam search (csrc/beam.hip)
+def _beam_arr(what: str, name: str, t: Tensor, dt, shape) -> None:
+    if t.dtype is not dt or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise L.LlxError(f"{what}: {name} must be a contiguous device {str(dt).removeprefix('torch.')} {list(shape)} (got {t.dtype} {tuple(t.shape)})")
+
+
+def beam_rows(logits: Tensor, cand_score: Tensor, cand_token: Tensor) -> None:
+    """The shortlist of every row of logits [W, V] (bf16 or fp32, last dim dense, any row stride and start offset; W in 2..16, V > W), in
+    one launch: cand_score (fp32 [W, W + 1]) and cand_token (int32 [W, W + 1]) receive the log-probabilities and indices of each row's
+    W + 1 best tokens by (logit descending, index ascending) - sampling.beam_shortlist."""
+    L.require_cuda(logits, cand_score, cand_token)
+    if logits.dim() != 2 or logits.dtype not in (BF16, torch.float32):
+        raise L.LlxError(f"beam_rows: logits must be bf16 or fp32 [W, V] (got {logits.dtype} {tuple(logits.shape)})")
+    if logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
+        logits = logits.contiguous()
+    W, V = logits.shape
+    _beam_arr("beam_rows", "cand_score", cand_score, torch.float32, (W, W + 1))
+    _beam_arr("beam_rows", "cand_token", cand_token, torch.int32, (W, W + 1))
+    L.check(_lib().llx_beam_rows(L.ptr(logits), 0 if logits.dtype is BF16 else 1, logits.stride(0), W, V, L.ptr(cand_score), L.ptr(cand_token),
+                                 L.stream()), "llx_beam_rows")
+
+
+def beam_merge(cand_score: Tensor, cand_token: Tensor, s: Tensor, parent: Tensor, tok: Tensor, hist: Tensor, bank_tok: Tensor, bank_len: Tensor,
+               bank_score: Tensor, meta: Tensor, *, n: int, eos_id: Optional[int] = None, length_penalty: float = 1.0, init: bool = False) -> None:
+    """One step of beam search on the shortlists of beam_rows, in one launch and without a host read (sampling.beam_step): the walk over
+    the W * (W + 1) candidates and the bookkeeping - parent (int32 [W]), tok (int64 [W] or [W, 1]: the next step's input), s (fp32 [W]),
+    hist (int64 [W, n]: permuted by parent, then appended to), the bank of finished hypotheses (bank_tok int64 [W, n], bank_len int32
+    [W], bank_score fp32 [W]) and meta (int32 [3]: hypotheses in the bank, done, tokens generated).  init: the first step after the
+    prefill (the state is not read; only row 0 takes part).  Once done is set a launch writes identity parents and nothing else."""
+    L.require_cuda(cand_score, cand_token, s, parent, tok, hist, bank_tok, bank_len, bank_score, meta)
+    W = s.numel()
+    for name, t, dt, shape in (("cand_score", cand_score, torch.float32, (W, W + 1)), ("cand_token", cand_token, torch.int32, (W, W + 1)),
+                               ("s", s, torch.float32, (W,)), ("parent", parent, torch.int32, (W,)), ("tok", tok.view(-1), torch.int64, (W,)),
+                               ("hist", hist, torch.int64, (W, n)), ("bank_tok", bank_tok, torch.int64, (W, n)),
+                               ("bank_len", bank_len, torch.int32, (W,)), ("bank_score", bank_score, torch.float32, (W,)),
+                               ("meta", meta, torch.int32, (3,))):
+        _beam_arr("beam_merge", name, t, dt, shape)
+    if not tok.is_contiguous():
+        raise L.LlxError("beam_merge: tok must be contiguous")
+    L.check(_lib().llx_beam_merge(L.ptr(cand_score), L.ptr(cand_token), L.ptr(s), L.ptr(parent), L.ptr(tok), L.ptr(hist), n, L.ptr(bank_tok), n,
+                                  L.ptr(bank_len), L.ptr(bank_score), L.ptr(meta), W, int(n), int(eos_id) if eos_id is not None else -1,
+                                  float(length_penalty), 1 if init else 0, L.stream()), "llx_beam_merge")
+
+
+def kv_cache_table(caches) -> Tensor:
+    """The device table of base pointers that kv_reorder_rows takes, for `caches` (bf16 [B, KVH, Smax, 128] tensors of one shape and one
+    set of strides, 16-byte aligned: every layer's k and v cache).  Build it once per generate() call; the table keeps the caches' shape
+    and strides and references to them."""
+    caches = list(caches)
+    c0 = caches[0]
+    for c in caches:
+        L.require_cuda(c)
+        if c.dtype is not BF16 or c.dim() != 4 or c.shape != c0.shape or c.stride() != c0.stride() or c.stride(3) != 1 or c.data_ptr() % 16:
+            raise L.LlxError("kv_cache_table: the caches must be bf16 [B, KVH, Smax, 128] tensors of one shape and one set of strides, "
+                             "16-byte aligned, last dim dense")
+    table = torch.tensor([c.data_ptr() for c in caches], dtype=torch.int64).to(c0.device)
+    table.caches = caches
+    return table
+
+
+def kv_reorder_rows(table: Tensor, parent: Tensor, length: int) -> None:
+    """cache[b, :, :length] <- cache[parent[b], :, :length] for b < W = len(parent) (device int32, 2..16) in place, in every cache of
+    `table` (kv_cache_table), in one launch.  A thread owns one 16-byte chunk of (head, position) in all W slots, loads the ones that
+    move and then stores them, so no slot is read after it was overwritten.  Slots with parent[b] == b, positions >= length and slots
+    >= W are not written."""
+    L.require_cuda(table, parent)
+    c0 = table.caches[0]
+    if parent.dtype is not torch.int32 or parent.dim() != 1 or not parent.is_contiguous() or parent.numel() > c0.shape[0]:
+        raise L.LlxError(f"kv_reorder_rows: parent must be a contiguous device int32 [W] with W <= the caches' batch {c0.shape[0]} "
+                         f"(got {parent.dtype} {tuple(parent.shape)})")
+    L.check(_lib().llx_kv_reorder_rows(L.ptr(table), table.numel(), c0.stride(0), c0.stride(1), c0.stride(2), L.ptr(parent), parent.numel(),
+                                       c0.shape[1], int(length), c0.shape[2], c0.shape[3], L.stream()), "llx_kv_reorder_rows")
+
+
 # ------------------------------------------------------------------------------------------------- cross entropy
 def head_compact_index(labels: Tensor) -> tuple[Tensor, Tensor, Tensor, Tensor]:
     """(idx, inv, labels_c, count) for the labelled rows (labels != -100) in order; everything stays on the device."""

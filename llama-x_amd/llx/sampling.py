@@ -72,3 +72,95 @@ def lookup_accept(fed: list, picks: list, k: int, eos_id, room: int) -> tuple:
     if eos_id is not None and eos_id >= 0 and eos_id in out:
         return out[: out.index(eos_id) + 1], True
     return out, False
+
+
+# ---- beam search: the host reference of csrc/beam.hip (generate(num_beams=W)); pure lists of floats and ints
+BEAM_DEAD = -1.0e30  # the score of a beam that does not exist yet (beams 1 .. W-1 before the first step): no sum of log-probabilities reaches it
+
+
+def beam_shortlist(z, W: int) -> list:
+    """The W + 1 best tokens of the logits row `z` as (log-probability, token), ordered by (logit descending, token index ascending);
+    logp[t] = (z[t] - zmax) - log sum exp(z - zmax).  W + 1 are enough: the walk of beam_step stops at W live picks and a row holds
+    one eos_id at most."""
+    import heapq
+    import math
+
+    zmax = max(z)
+    lse = math.log(math.fsum(math.exp(v - zmax) for v in z))
+    best = heapq.nsmallest(W + 1, range(len(z)), key=lambda t: (-z[t], t))
+    return [((z[t] - zmax) - lse, t) for t in best]
+
+
+def beam_state(W: int) -> dict:
+    """The state of one prompt before the first step: beam 0 alone is live."""
+    return dict(s=[0.0] + [BEAM_DEAD] * (W - 1), hist=[[] for _ in range(W)], bank=[], done=False, steps=0)
+
+
+def _beam_bank(st: dict, W: int, tokens: list, final: float, margins) -> None:
+    """A hypothesis enters the bank (slots in order of arrival) if there is room, or in place of the worst one - the lowest final score,
+    the lowest slot among equals - if it beats it."""
+    bank = st["bank"]
+    if len(bank) < W:
+        bank.append((list(tokens), final))
+        return
+    worst = min(range(W), key=lambda i: (bank[i][1], i))
+    if margins is not None:
+        margins.append(abs(final - bank[worst][1]))
+    if final > bank[worst][1]:
+        if margins is not None:
+            margins.extend(abs(bank[i][1] - bank[worst][1]) for i in range(W) if i != worst)
+        bank[worst] = (list(tokens), final)
+
+
+def beam_step(st: dict, rows, W: int, *, max_new_tokens: int, eos_id=None, length_penalty: float = 1.0, margins=None, used=None) -> list:
+    """One step of beam search on the W logits rows `rows` (row r: the logits after beam r's last token; before the first step all rows
+    are the prefill's): updates `st` (beam_state) and returns parent[0 .. W-1].
+
+    Every row gives its shortlist (beam_shortlist); all candidates are ordered by (score s[r] + logp descending, row ascending, rank in
+    the row's shortlist ascending) and walked: an eos_id becomes a finished hypothesis with the final score score / len ** length_penalty
+    (len counts the eos) and is offered to the bank; any other token becomes the next live beam j (parent[j] = r); the walk stops at W
+    live beams.  In the first step only row 0 takes part.  done is set when the bank holds W hypotheses or max_new_tokens tokens have
+    been generated; the live beams are then offered to the bank as they are, with s / steps ** length_penalty.  A step on a done state
+    returns the identity and changes nothing.
+
+    margins (a list) receives the gaps that decide: between consecutive walked candidates up to the first one left out (pairs of equal
+    logits of one row aside: their order is the index, exactly), and at the bank between a hypothesis and the worst entry, and between
+    the worst and the others when it is replaced.  used (a list) receives the highest shortlist rank the walk touched."""
+    if st["done"]:
+        return list(range(W))
+    n, init = st["steps"] + 1, st["steps"] == 0
+    cands = []
+    for r in range(1 if init else W):
+        for k, (lp, t) in enumerate(beam_shortlist(rows[r], W)):
+            cands.append((-(st["s"][r] + lp), r, k, t, rows[r][t]))
+    cands.sort(key=lambda c: c[:3])
+    parent, s, hist, top = [], [], [], 0
+    for i, (neg, r, k, t, z) in enumerate(cands):
+        if margins is not None and i > 0 and not (cands[i - 1][1] == r and cands[i - 1][4] == z):
+            margins.append(neg - cands[i - 1][0])  # (the scores are stored negated: the gap to the candidate in front)
+        if len(parent) == W:
+            break
+        top = max(top, k)
+        if eos_id is not None and t == eos_id:
+            _beam_bank(st, W, st["hist"][r] + [t], -neg / n ** length_penalty, margins)
+        else:
+            parent.append(r)
+            s.append(-neg)
+            hist.append(st["hist"][r] + [t])
+    assert len(parent) == W, "a row holds one eos_id at most: W + 1 candidates per row always give W live beams"
+    if used is not None:
+        used.append(top)
+    st.update(s=s, hist=hist, steps=n)
+    if len(st["bank"]) == W or n == max_new_tokens:
+        st["done"] = True
+        for j in range(W):
+            _beam_bank(st, W, hist[j], s[j] / n ** length_penalty, margins)
+    return parent
+
+
+def beam_ranked(st: dict, margins=None) -> list:
+    """The bank as [(tokens, final score)], best first (the lower slot among equal scores)."""
+    order = sorted(range(len(st["bank"])), key=lambda i: (-st["bank"][i][1], i))
+    if margins is not None:
+        margins.extend(st["bank"][a][1] - st["bank"][b][1] for a, b in zip(order, order[1:]))
+    return [st["bank"][i] for i in order]

@@ -40,9 +40,14 @@ class LlamaAudio(Llama):
             nn.GELU(),
         )
 
-    def build_cache(self, inference: bool = False):
-        super().build_cache(inference)
+    def build_cache(self, inference: bool = False, batch_size: int = 1):
+        super().build_cache(inference, batch_size)
         self.melspec = audio_ops.MelSpectrogram(**self.audio_config._asdict(), norm="slaney", mel_scale="slaney")
+
+    def audio_positions(self, samples: int) -> int:
+        """Sequence positions the front end makes of a clip of `samples` samples: the frames without the last one, halved by the second
+        convolution (k3, s2, p1)."""
+        return (samples // self.audio_config.hop_length - 1) // 2 + 1
 
     def _embed(self, tokens: Tensor, audio: Tensor | None = None) -> tuple[Tensor, int]:
         if audio is None:
@@ -52,7 +57,7 @@ class LlamaAudio(Llama):
 
     def forward(self, audio: Tensor | None, tokens: Tensor, *, input_pos: Tensor | None = None, labels: Tensor | None = None,
                 block_mask=None) -> Tensor:
-        mask = self.causal_mask[None, None, input_pos] if input_pos is not None else None  # inference path (generate)
+        mask = self._inference_mask(tokens.shape[0], input_pos)  # inference path (generate); input_pos [L] or [B, L] as in Llama
         x, n_audio = self._embed(tokens, audio)
         rope = self.rope[: x.shape[1]]
         x = self._run_layers(x, rope, mask=mask, input_pos=input_pos, block_mask=block_mask)
@@ -68,6 +73,13 @@ class LlamaAudio(Llama):
         if n_audio:
             x = x[:, n_audio:]  # remove audio embs
         return ops.head_logprobs(x, self.norm, self.output, labels, return_top1)
+
+    def generate(self, audio: Tensor | None, prompt: Tensor, max_new_tokens: int, **kwargs) -> Tensor:
+        """llx.generate.generate(self, prompt, max_new_tokens, audio=audio, ...): the clip(s) (fp32 [B, samples]) and the prompt are
+        prefilled as one [audio ; text] sequence, the decode steps feed text tokens only.  audio=None generates as a text model."""
+        from llx.generate import generate
+
+        return generate(self, prompt, max_new_tokens, audio=audio, **kwargs)
 
     @staticmethod
     def from_hf(model_id: str, **kwargs):

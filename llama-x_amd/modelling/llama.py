@@ -353,21 +353,24 @@ class Llama(nn.Module):
         """(hidden states [B, S, D], number of leading positions that are dropped before the head)."""
         return self.tok_embeddings(x), 0
 
+    def _inference_mask(self, batch: int, input_pos: Tensor | None) -> Tensor | None:
+        """The attention mask of a call of `batch` sequences at input_pos (None: not the inference path)."""
+        if input_pos is None:
+            return None
+        cache = self.layers[0].attention.kv_cache if len(self.layers) else None
+        if cache is not None and batch != cache.k_cache.shape[0]:
+            raise LlxError(f"batch of {batch} against a KV cache of batch {cache.k_cache.shape[0]}: "
+                           f"call build_cache(inference=True, batch_size={batch})")
+        if input_pos.dim() == 2:
+            # [B, L]: sequence b writes its keys and values at input_pos[b] and attends through causal_mask[input_pos[b]]
+            if input_pos.shape[0] != batch:
+                raise LlxError(f"input_pos {tuple(input_pos.shape)} must be [L] or [B, L] with B = {batch}")
+            return self.causal_mask[input_pos][:, None]  # [B, 1, L, Skv]
+        return self.causal_mask[None, None, input_pos]
+
     def _hidden(self, x: Tensor, input_pos: Tensor | None = None, block_mask=None) -> Tensor:
         """forward() up to the head: the hidden states [B, S, D] after the last layer."""
-        mask = None
-        if input_pos is not None:  # inference path (generate)
-            cache = self.layers[0].attention.kv_cache if len(self.layers) else None
-            if cache is not None and x.shape[0] != cache.k_cache.shape[0]:
-                raise LlxError(f"batch of {x.shape[0]} against a KV cache of batch {cache.k_cache.shape[0]}: "
-                               f"call build_cache(inference=True, batch_size={x.shape[0]})")
-            if input_pos.dim() == 2:
-                # [B, L]: sequence b writes its keys and values at input_pos[b] and attends through causal_mask[input_pos[b]]
-                if input_pos.shape[0] != x.shape[0]:
-                    raise LlxError(f"input_pos {tuple(input_pos.shape)} must be [L] or [B, L] with B = {x.shape[0]}")
-                mask = self.causal_mask[input_pos][:, None]  # [B, 1, L, Skv]
-            else:
-                mask = self.causal_mask[None, None, input_pos]
+        mask = self._inference_mask(x.shape[0], input_pos)
         x, _ = self._embed(x)
         rope = self.rope[: x.shape[1]]
         return self._run_layers(x, rope, mask=mask, input_pos=input_pos, block_mask=block_mask)
@@ -387,7 +390,8 @@ class Llama(nn.Module):
         """llx.generate.generate(self, ...): prefill + one forward and one on-device sampler launch per token (the reference has no
         generate(); its input_pos branch above is what this drives).  prompt [B, P] with B the cache's batch; prompt_lens=... for
         right-padded prompts of different lengths; draft_tokens=k (greedy, one sequence) feeds k prompt-lookup draft tokens with every
-        step and keeps the ones the model confirms: the same tokens in fewer weight passes."""
+        step and keeps the ones the model confirms: the same tokens in fewer weight passes; num_beams=W (one prompt, a cache of batch
+        W) is beam search with the beams as the rows of one batched step."""
         from llx.generate import generate
 
         return generate(self, prompt, max_new_tokens, **kwargs)
