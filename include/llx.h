@@ -440,6 +440,21 @@ int llx_sample_rows(const void* logits, int dtype, int64_t ld, int64_t R, int64_
                     uint64_t seed, int64_t* pos, int64_t* token_out, int64_t* history, int64_t hist_ld, int64_t hist_cap, int64_t hist_base,
                     int advance, int64_t eos_id, int32_t* finished, float* aux_u, float* aux_thresh, int32_t* aux_kept, llx_stream_t s);
 
+/* ---- llx_sample_rows with sampler penalties and the token's log-probability (llx/sampling.py rule 0); the arguments of
+ *      llx_sample_rows keep their meaning.  counts (nullable): DEVICE int32 [R, ldc], ldc >= V, counts[r][i] = how often token i has
+ *      occurred in row r's sequence.  Null: no penalties, whatever the three floats are.  Otherwise every element with a count c > 0 is
+ *      read as x = x > 0 ? x / repetition_penalty : x * repetition_penalty, then x - (presence_penalty + frequency_penalty * c), single
+ *      fp32 operations in that order; argmax, temperature, top_k, top_p, the draw and aux_thresh all see the penalised value; after the
+ *      draw counts[r][token] += 1 (a finished row touches neither counts nor logprob_history).  repetition_penalty finite and > 0 (1 =
+ *      off), the other two finite (0 = off).  logprob_history (nullable; needs history, whose row stride, cap and base it shares): fp32,
+ *      receives (l_tok - l_max) - log sum exp(l - l_max) over the RAW logits - no penalty, temperature 1, nothing filtered - at
+ *      [r, pos[r] - hist_base] when inside [0, cap). ---------------------------------------------------------------------------- */
+int llx_sample_rows_ext(const void* logits, int dtype, int64_t ld, int64_t R, int64_t V, float temperature, int64_t top_k, float top_p,
+                        uint64_t seed, int64_t* pos, int64_t* token_out, int64_t* history, int64_t hist_ld, int64_t hist_cap, int64_t hist_base,
+                        int advance, int64_t eos_id, int32_t* finished, float* aux_u, float* aux_thresh, int32_t* aux_kept, int32_t* counts,
+                        int64_t ldc, float repetition_penalty, float presence_penalty, float frequency_penalty, float* logprob_history,
+                        llx_stream_t s);
+
 /* ---- prompt-lookup drafting (generate(draft_tokens=k), llx/generate.py): the bookkeeping of one greedy speculative step, one workgroup,
  *      no host read.  The step fed step_tok [k + 1] = [last token, k draft tokens] at step_pos; picks int64 [k + 1] are the greedy picks of
  *      its k + 1 logits rows.  With a = the longest prefix with step_tok[1 + i] == picks[i], picks[0 .. a] are emitted - cut to the room

@@ -11,8 +11,14 @@
 //   3  without either filter: one plain sum for W
 //   4  draw: block prefix scan of the kept weights in index order, rounds of 1024 chunks, stops at the round that crosses u * W
 // Histograms are LDS atomics on integers (count u32, weight u64, smallest raw logit of the bin u32): deterministic.
+//
+// llx_sample_rows_ext (the EXT instances; the plain ones do not pay for it) adds rule 0 of llx/sampling.py in front: every
+// pass above reads the row through the PENALISED view - element i with counts[r][i] > 0 becomes x > 0 ? x / theta : x * theta, then
+// x - (alpha_p + alpha_f * c), single fp32 operations - the thread that writes the token also does counts[r][token] += 1, and one more
+// pass over the RAW row gives the token's log-probability (max and sum of exp in fp32, a fixed reduction shape).
 #include "common.h"
 #include "rowview.h"  // RowView, smp_key / smp_unkey
+#include <type_traits>
 
 #define SMP_THREADS 1024
 #define SMP_WAVES (SMP_THREADS / 64)
@@ -39,6 +45,46 @@ struct SampleArgs {
   float* aux_u;
   float* aux_thresh;
   int32_t* aux_kept;
+};
+
+struct SampleExtArgs : SampleArgs {
+  int32_t* counts;  // [R, ldc], indexed by token id; null = no penalties
+  int64_t ldc;
+  float rep, pres, freq;
+  float* logprob_history;  // the geometry of history
+};
+
+// The row through rule 0: a RowView whose load() penalises the elements that have occurred.  Counts are indexed by token id, which a
+// row's grid offset shifts against the chunks, so they are per-element dword loads (of a table that stays in L2 between the passes).
+template <typename T>
+struct PenRow : RowView<T> {
+  using RowView<T>::E;
+  const int32_t* cnt;
+  float rep, pres, freq;
+  __device__ PenRow(const void* p, int V_, const int32_t* cnt_, float rep_, float pres_, float freq_)
+      : RowView<T>(p, V_), cnt(cnt_), rep(rep_), pres(pres_), freq(freq_) {}
+  __device__ __forceinline__ uint32_t load_raw(int c, float (&v)[E]) const { return RowView<T>::load(c, v); }
+  __device__ __forceinline__ uint32_t load(int c, float (&v)[E]) const {
+#pragma clang fp contract(off)
+    const uint32_t m = RowView<T>::load(c, v);
+    if (cnt) {
+      const int i0 = c * E - this->off;
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        if ((m >> e) & 1) {
+          const int n = cnt[i0 + e];
+          if (n > 0) {
+            float x = v[e];
+            x = x > 0.f ? x / rep : x * rep;
+            float t = freq * (float)n;
+            t = pres + t;
+            v[e] = x - t;
+          }
+        }
+      }
+    }
+    return m;
+  }
 };
 
 __device__ __forceinline__ uint64_t smp_mix(uint64_t x) {
@@ -96,10 +142,10 @@ __device__ __forceinline__ void smp_scan(uint32_t& c, uint64_t& w, uint32_t& tc,
 //   by_weight = false: mass = count,  target = k        -> the k-th largest key (duplicates counted)
 //   by_weight = true:  mass = weight, target = top_p*W  -> the top-p threshold (W = the weight of all elements with key >= klo)
 // Returns the key; kept / wkept = count and weight of key >= that key; rawkey = key image of the smallest raw logit at that key.
-template <typename T>
-__device__ void smp_refine(const RowView<T>& row, float T_, float zmax, uint32_t klo, bool by_weight, uint32_t k, float top_p,
+template <typename Row>
+__device__ void smp_refine(const Row& row, float T_, float zmax, uint32_t klo, bool by_weight, uint32_t k, float top_p,
                            uint32_t& key_out, uint32_t& kept, uint64_t& wkept, uint32_t& rawkey, SmpShared& sh) {
-  constexpr int E = RowView<T>::E;
+  constexpr int E = Row::E;
   const int tid = threadIdx.x;
   uint32_t prefix = 0, pmask = 0;
   uint32_t cnt_above = 0;
@@ -164,8 +210,9 @@ __device__ void smp_refine(const RowView<T>& row, float T_, float zmax, uint32_t
   __syncthreads();
 }
 
-template <typename T>
-__global__ __launch_bounds__(SMP_THREADS) void sample_rows_kernel(SampleArgs a) {
+template <typename T, bool EXT>
+__global__ __launch_bounds__(SMP_THREADS) void sample_rows_kernel(std::conditional_t<EXT, SampleExtArgs, SampleArgs> a) {
+  using Row = std::conditional_t<EXT, PenRow<T>, RowView<T>>;
   constexpr int E = RowView<T>::E;
   __shared__ SmpShared sh;
   const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -174,7 +221,12 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_kernel(SampleArgs a) 
     return;
   }
   const int64_t pos = a.pos[r];
-  const RowView<T> row((const T*)a.logits + (int64_t)r * a.ld, a.V);
+  const Row row = [&] {
+    if constexpr (EXT)
+      return Row((const T*)a.logits + (int64_t)r * a.ld, a.V, a.counts ? a.counts + (int64_t)r * a.ldc : nullptr, a.rep, a.pres, a.freq);
+    else
+      return Row((const T*)a.logits + (int64_t)r * a.ld, a.V);
+  }();
   const uint64_t m24 = smp_mix(smp_mix(smp_mix(a.seed) ^ (uint64_t)pos) ^ (uint64_t)r) >> 40;
   const float u = (float)m24 * 5.9604644775390625e-08f;  // 2^-24: exact
 
@@ -230,11 +282,11 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_kernel(SampleArgs a) 
     kept = (uint32_t)a.V;
     bool have_w = false;
     if (a.top_k > 0 && a.top_k < (int64_t)a.V) {
-      smp_refine<T>(row, T_, zmax, 0u, false, (uint32_t)a.top_k, 1.f, klo, kept, W, rawkey, sh);
+      smp_refine(row, T_, zmax, 0u, false, (uint32_t)a.top_k, 1.f, klo, kept, W, rawkey, sh);
       have_w = true;
     }
     if (a.top_p < 1.f) {
-      smp_refine<T>(row, T_, zmax, klo, true, 0u, a.top_p, klo, kept, W, rawkey, sh);
+      smp_refine(row, T_, zmax, klo, true, 0u, a.top_p, klo, kept, W, rawkey, sh);
       have_w = true;
     }
     if (!have_w) {  // nothing filtered: W is the plain sum
@@ -296,6 +348,55 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_kernel(SampleArgs a) 
     if (token < 0) token = bai;  // W == 0 cannot happen (the maximum weighs 2^40); stay inside the row regardless
   }
 
+  if constexpr (EXT) {
+    // ---- the log-probability of the token on the RAW row: (l_tok - l_max) - log sum exp(l - l_max), reduced per thread, per wave, then
+    // over the 16 waves in order.  Only when its history slot exists.
+    const int64_t h = pos - a.hist_base;
+    if (a.logprob_history && h >= 0 && h < a.hist_cap) {
+      float lmax = bmx;  // without counts pass 0 read the raw row
+      if (a.counts) {
+        float m_ = -INFINITY;
+        for (int c = tid; c < row.nchunks; c += SMP_THREADS) {
+          float v[E];
+          row.load_raw(c, v);  // invalid elements read as -inf
+#pragma unroll
+          for (int e = 0; e < E; ++e) m_ = fmaxf(m_, v[e]);
+        }
+        m_ = wave_max(m_);
+        __syncthreads();
+        if (lane == 0) sh.red_f[wv] = m_;
+        __syncthreads();
+        lmax = sh.red_f[0];
+#pragma unroll
+        for (int i = 1; i < SMP_WAVES; ++i) lmax = fmaxf(lmax, sh.red_f[i]);
+      }
+      float s = 0.f;
+      for (int c = tid; c < row.nchunks; c += SMP_THREADS) {
+        float v[E];
+        const uint32_t m = row.load_raw(c, v);
+#pragma unroll
+        for (int e = 0; e < E; ++e)
+          if ((m >> e) & 1) s += (v[e] == lmax) ? 1.f : expf(v[e] - lmax);
+      }
+      s = wave_sum(s);
+      __syncthreads();
+      if (lane == 0) sh.red_f[wv] = s;
+      __syncthreads();
+      if (tid == 0) {
+        float tot = sh.red_f[0];
+#pragma unroll
+        for (int i = 1; i < SMP_WAVES; ++i) tot += sh.red_f[i];
+        const T raw = ((const T*)a.logits)[(int64_t)r * a.ld + token];
+        float lt;
+        if constexpr (sizeof(T) == 2) lt = bf2f(raw); else lt = raw;
+        const float d = (lt == lmax) ? 0.f : ((lt != lt) ? -INFINITY : lt - lmax);
+        a.logprob_history[(int64_t)r * a.hist_ld + h] = d - logf(tot);
+      }
+    }
+    // one workgroup owns the row and every read of the counts lies behind a barrier: a plain read-modify-write
+    if (tid == 0 && a.counts) a.counts[(int64_t)r * a.ldc + token] += 1;
+  }
+
   if (tid == 0) {
     a.token_out[r] = (int64_t)token;
     if (a.history) {
@@ -312,27 +413,63 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_kernel(SampleArgs a) 
 
 }  // namespace
 
+// the checks both entry points share; `name` begins every message
+static int smp_check(const char* name, const void* logits, int dtype, int64_t ld, int64_t R, int64_t V, float temperature, int64_t top_k, float top_p,
+                     const int64_t* pos, const int64_t* token_out, const int64_t* history, int64_t hist_ld, int64_t hist_cap) {
+  LLX_REQUIRE(logits && pos && token_out, "%s: null pointer (logits, pos and token_out are required)", name);
+  LLX_REQUIRE(dtype == 0 || dtype == 1, "%s: dtype=%d (0 = bf16, 1 = fp32)", name, dtype);
+  LLX_REQUIRE(R > 0 && R < (1ll << 31), "%s: R=%lld must be positive", name, (long long)R);
+  LLX_REQUIRE(V > 0 && V < (1ll << 30), "%s: V=%lld must be in [1, 2^30)", name, (long long)V);
+  LLX_REQUIRE(ld >= V, "%s: row stride %lld < V=%lld", name, (long long)ld, (long long)V);
+  LLX_REQUIRE(temperature >= 0.f, "%s: temperature=%g must be >= 0", name, (double)temperature);
+  LLX_REQUIRE(top_k >= 0, "%s: top_k=%lld must be >= 0 (0 = off)", name, (long long)top_k);
+  LLX_REQUIRE(top_p > 0.f && top_p <= 1.f, "%s: top_p=%g must be in (0, 1]", name, (double)top_p);
+  LLX_REQUIRE((uintptr_t)logits % (dtype ? 4 : 2) == 0, "%s: logits not aligned to their element size", name);
+  LLX_REQUIRE(!history || (hist_cap > 0 && hist_ld >= hist_cap), "%s: history needs cap > 0 and a row stride >= cap", name);
+  return LLX_OK;
+}
+
 // dtype: 0 = bf16, 1 = fp32.  history / finished / aux_* nullable; eos_id is read only with finished.
 extern "C" int llx_sample_rows(const void* logits, int dtype, int64_t ld, int64_t R, int64_t V, float temperature, int64_t top_k, float top_p,
                                uint64_t seed, int64_t* pos, int64_t* token_out, int64_t* history, int64_t hist_ld, int64_t hist_cap,
                                int64_t hist_base, int advance, int64_t eos_id, int32_t* finished, float* aux_u, float* aux_thresh,
                                int32_t* aux_kept, hipStream_t stream) {
-  LLX_REQUIRE(logits && pos && token_out, "llx_sample_rows: null pointer (logits, pos and token_out are required)");
-  LLX_REQUIRE(dtype == 0 || dtype == 1, "llx_sample_rows: dtype=%d (0 = bf16, 1 = fp32)", dtype);
-  LLX_REQUIRE(R > 0 && R < (1ll << 31), "llx_sample_rows: R=%lld must be positive", (long long)R);
-  LLX_REQUIRE(V > 0 && V < (1ll << 30), "llx_sample_rows: V=%lld must be in [1, 2^30)", (long long)V);
-  LLX_REQUIRE(ld >= V, "llx_sample_rows: row stride %lld < V=%lld", (long long)ld, (long long)V);
-  LLX_REQUIRE(temperature >= 0.f, "llx_sample_rows: temperature=%g must be >= 0", (double)temperature);
-  LLX_REQUIRE(top_k >= 0, "llx_sample_rows: top_k=%lld must be >= 0 (0 = off)", (long long)top_k);
-  LLX_REQUIRE(top_p > 0.f && top_p <= 1.f, "llx_sample_rows: top_p=%g must be in (0, 1]", (double)top_p);
-  LLX_REQUIRE((uintptr_t)logits % (dtype ? 4 : 2) == 0, "llx_sample_rows: logits not aligned to their element size");
-  LLX_REQUIRE(!history || (hist_cap > 0 && hist_ld >= hist_cap), "llx_sample_rows: history needs cap > 0 and a row stride >= cap");
+  if (int rc = smp_check("llx_sample_rows", logits, dtype, ld, R, V, temperature, top_k, top_p, pos, token_out, history, hist_ld, hist_cap)) return rc;
   SampleArgs a{logits, ld, (int)V, temperature, top_k, top_p, seed, pos, token_out, history, hist_ld, hist_cap, hist_base, advance, eos_id,
                finished, aux_u, aux_thresh, aux_kept};
   if (dtype == 0)
-    hipLaunchKernelGGL(sample_rows_kernel<bf16_t>, dim3((unsigned)R), dim3(SMP_THREADS), 0, stream, a);
+    hipLaunchKernelGGL((sample_rows_kernel<bf16_t, false>), dim3((unsigned)R), dim3(SMP_THREADS), 0, stream, a);
   else
-    hipLaunchKernelGGL(sample_rows_kernel<float>, dim3((unsigned)R), dim3(SMP_THREADS), 0, stream, a);
+    hipLaunchKernelGGL((sample_rows_kernel<float, false>), dim3((unsigned)R), dim3(SMP_THREADS), 0, stream, a);
   LLX_LAUNCH_CHECK("llx_sample_rows");
+  return LLX_OK;
+}
+
+// llx_sample_rows with rule 0 and the log-probability.  counts (nullable, int32 [R, ldc], ldc >= V): null = no penalties whatever the
+// three floats are; otherwise the row is read through the penalised view and counts[r][token] += 1 after the draw.  logprob_history
+// (nullable, fp32, the geometry of history, which it needs): the raw-logit log-probability of the token at history's slot.
+extern "C" int llx_sample_rows_ext(const void* logits, int dtype, int64_t ld, int64_t R, int64_t V, float temperature, int64_t top_k, float top_p,
+                                   uint64_t seed, int64_t* pos, int64_t* token_out, int64_t* history, int64_t hist_ld, int64_t hist_cap,
+                                   int64_t hist_base, int advance, int64_t eos_id, int32_t* finished, float* aux_u, float* aux_thresh,
+                                   int32_t* aux_kept, int32_t* counts, int64_t ldc, float repetition_penalty, float presence_penalty,
+                                   float frequency_penalty, float* logprob_history, hipStream_t stream) {
+  const char* name = "llx_sample_rows_ext";
+  if (int rc = smp_check(name, logits, dtype, ld, R, V, temperature, top_k, top_p, pos, token_out, history, hist_ld, hist_cap)) return rc;
+  LLX_REQUIRE(repetition_penalty > 0.f && repetition_penalty - repetition_penalty == 0.f,
+              "%s: repetition_penalty=%g must be finite and > 0 (1 = off)", name, (double)repetition_penalty);
+  LLX_REQUIRE(presence_penalty - presence_penalty == 0.f, "%s: presence_penalty=%g must be finite (0 = off)", name, (double)presence_penalty);
+  LLX_REQUIRE(frequency_penalty - frequency_penalty == 0.f, "%s: frequency_penalty=%g must be finite (0 = off)", name, (double)frequency_penalty);
+  LLX_REQUIRE((uintptr_t)counts % 4 == 0, "%s: counts not aligned to 4 bytes", name);
+  LLX_REQUIRE(!counts || ldc >= V, "%s: counts row stride ldc=%lld < V=%lld", name, (long long)ldc, (long long)V);
+  LLX_REQUIRE(!logprob_history || history, "%s: logprob_history shares the geometry of history, which is null", name);
+  LLX_REQUIRE((uintptr_t)logprob_history % 4 == 0, "%s: logprob_history not aligned to 4 bytes", name);
+  SampleExtArgs a{{logits, ld, (int)V, temperature, top_k, top_p, seed, pos, token_out, history, hist_ld, hist_cap, hist_base, advance, eos_id,
+                   finished, aux_u, aux_thresh, aux_kept},
+                  counts, ldc, repetition_penalty, presence_penalty, frequency_penalty, logprob_history};
+  if (dtype == 0)
+    hipLaunchKernelGGL((sample_rows_kernel<bf16_t, true>), dim3((unsigned)R), dim3(SMP_THREADS), 0, stream, a);
+  else
+    hipLaunchKernelGGL((sample_rows_kernel<float, true>), dim3((unsigned)R), dim3(SMP_THREADS), 0, stream, a);
+  LLX_LAUNCH_CHECK(name);
   return LLX_OK;
 }

@@ -122,6 +122,8 @@ SIGNATURES: dict[str, tuple] = {
     "llx_gemm_tn_bf16_rows": (c_int, [_P, _L, _P, _L, _P, _L, _L, _L, _L, _P, _P]),
     "llx_gemm_nt_bf16_rope": (c_int, [_P, _L, _P, _L, _P, _L, _L, _L, _L, _P, _L, _P, _L, _L, _P, _L, _L, _P]),
     "llx_sample_rows": (c_int, [_P, _I, _L, _L, _L, _F, _L, _F, c_uint64, _P, _P, _P, _L, _L, _L, _I, _L, _P, _P, _P, _P, _P]),
+    "llx_sample_rows_ext": (c_int, [_P, _I, _L, _L, _L, _F, _L, _F, c_uint64, _P, _P, _P, _L, _L, _L, _I, _L, _P, _P, _P, _P, _P, _L, _F, _F, _F,
+                                    _P, _P]),
     "llx_lookup_step": (c_int, [_P, _P, _L, _P, _P, _P, _P, _P, _L, _L, _I, _I, _L, _I, _P]),
     "llx_beam_rows": (c_int, [_P, _I, _L, _L, _L, _P, _P, _P]),
     "llx_beam_merge": (c_int, [_P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _L, _L, _L, _F, _I, _P]),

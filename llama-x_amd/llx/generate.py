@@ -24,7 +24,7 @@ from torch import Tensor
 from . import decode as D
 from . import kernels as K
 from ._lib import LlxError
-from .sampling import check_params
+from .sampling import check_params, check_penalties, penalties_on
 
 MAX_NGRAM = 8  # the longest n-gram a lookup draft matches (csrc/lookup.hip)
 
@@ -169,6 +169,20 @@ def history_rows(history: Tensor, shifts, counts: Tensor, T: int, pad: int) -> T
     return torch.where(j < counts.view(B, 1), got, torch.full_like(got, pad))
 
 
+def seed_counts(prompt: Tensor, lens: Optional[Sequence[int]], vocab_size: int, penalize_prompt: bool) -> Tensor:
+    """The sampler's count table (int32 [B, V], rule 0 of llx/sampling.py) before the first draw: zero, or with penalize_prompt the number
+    of times each token occurs in row b's own prompt - its first lens[b] columns (None: all); pads are not counted.  No host read."""
+    B, P = prompt.shape
+    table = torch.zeros(B, vocab_size, device=prompt.device, dtype=torch.int32)
+    if penalize_prompt:
+        if lens is None:
+            real = torch.ones(B, P, device=prompt.device, dtype=torch.int32)
+        else:
+            real = (torch.arange(P, device=prompt.device)[None] < torch.tensor(lens, device=prompt.device, dtype=torch.int64)[:, None]).to(torch.int32)
+        table.scatter_add_(1, prompt.clamp(0, vocab_size - 1), real)
+    return table
+
+
 @torch.no_grad()
 def prefill(model, prompt: Tensor, prompt_lens: Optional[Sequence[int]] = None, prefill_chunk: Optional[int] = None) -> Tensor:
     """Fill the KV cache from `prompt` (int64 [B, P], right-padded; B = the cache's batch) and return the logits [B, 1, V] of each
@@ -214,7 +228,9 @@ def prefill_audio(model, audio: Tensor, prompt: Tensor, prompt_lens: Optional[Se
 
 
 def _generate_batch(model, prompt: Tensor, n: int, lens: list, sampling: dict, eos_id, prefill_chunk, check_every: int, call,
-                    audio: Optional[Tensor] = None) -> Tensor:
+                    audio: Optional[Tensor] = None, table: Optional[Tensor] = None, return_logprobs: bool = False):
+    """The loop of a batch.  sampling: the sampler's keyword arguments, penalties included; table: its count table (None: no penalties),
+    seeded by the caller from each row's own text prompt; return_logprobs: also the fp32 log-probabilities, laid out like the tokens."""
     dev, B = prompt.device, prompt.shape[0]
     if audio is not None:
         logits = prefill_audio(model, audio, prompt, lens)
@@ -229,6 +245,10 @@ def _generate_batch(model, prompt: Tensor, n: int, lens: list, sampling: dict, e
     history = torch.zeros(B, cols, device=dev, dtype=torch.int64)
     finished = torch.zeros(B, device=dev, dtype=torch.int32) if eos_id is not None else None
     kw = dict(**sampling, pos=pos, out=tok.view(B), history=history, hist_base=base, advance=True, eos_id=eos_id, finished=finished)
+    if table is not None:
+        kw["counts"] = table
+    if return_logprobs:
+        kw["logprob_history"] = torch.zeros(B, cols, device=dev, dtype=torch.float32)
     K.sample(logits[:, 0], **kw)
     T = n
     for k in range(1, n + 1):
@@ -244,7 +264,8 @@ def _generate_batch(model, prompt: Tensor, n: int, lens: list, sampling: dict, e
         # a finished row feeds eos_id at its frozen position: it re-writes its own cache row there, nothing else
         K.sample(call(tok, pos[:, None])[:, 0], **kw)
     counts = pos - start if finished is not None else torch.full((B,), n, device=dev, dtype=torch.int64)
-    return history_rows(history, shifts, counts, T, eos_id if eos_id is not None else 0)
+    tokens = history_rows(history, shifts, counts, T, eos_id if eos_id is not None else 0)
+    return (tokens, history_rows(kw["logprob_history"], shifts, counts, T, 0.0)) if return_logprobs else tokens
 
 
 # ---- greedy decoding with prompt-lookup drafts (generate(draft_tokens=k)): several rows of one sequence per step
@@ -362,7 +383,8 @@ def _generate_beam(model, call, prompt: Tensor, audio, n: int, W: int, length_pe
 def generate(model, prompt: Tensor, max_new_tokens: int, *, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
              eos_id: Optional[int] = None, prefill_chunk: Optional[int] = None, check_every: int = 16, prompt_lens=None,
              draft_tokens: int = 0, draft_ngram: int = 3, stats: Optional[dict] = None, num_beams: int = 1, length_penalty: float = 1.0,
-             audio: Optional[Tensor] = None) -> Tensor:
+             audio: Optional[Tensor] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
+             penalize_prompt: bool = True, return_logprobs: bool = False):
     """Continue `prompt` (int64 [B, P], B = the batch the KV cache was built for) by up to `max_new_tokens` tokens -> int64 [B, n_new] on
     the prompt's device.  `prompt_lens` (B lengths in [1, P], a sequence or an int64 tensor, read once on the host before the first
     launch): the rows of `prompt` are right-padded prompts of these lengths; default: every row is P long.  For a batch the result is as
@@ -413,8 +435,32 @@ def generate(model, prompt: Tensor, max_new_tokens: int, *, temperature: float =
     in front of the prompts as one call under the causal mask and take A = model.audio_positions(samples) positions, so the text sits at
     A .. A + P - 1, A + P + max_new_tokens <= max_seq_len, and the draw counter of a sampled token is its position, A included.  The
     decode steps feed text tokens only.  `prefill_chunk` and `draft_tokens` are refused with audio; without it a LlamaAudio generates
-    as a text model."""
+    as a text model.
+
+    `repetition_penalty` (finite, > 0, 1 = off), `presence_penalty` and `frequency_penalty` (finite, 0 = off) shape the distribution a
+    token is chosen from - greedy included - by rule 0 of llx/sampling.py: with c the number of times a token has occurred in the row's
+    sequence so far, a logit x with c > 0 becomes x / repetition_penalty if x > 0 else x * repetition_penalty, then
+    x - (presence_penalty + frequency_penalty * c), in fp32, in front of temperature, top-k and top-p.  The counts live in an int32
+    [B, vocab] table on the device: with `penalize_prompt` (the default) it starts from each row's own prompt tokens (`prompt_lens`
+    honoured, pads and audio positions not counted), otherwise from zero; the sampler launch that picks a token adds one to its count, a
+    finished row's counts stay as they are, and nothing is read by the host.  `stats` also receives "counts": that table (not read), or
+    None when no penalty is on.
+
+    `return_logprobs=True` returns (tokens, logprobs), logprobs fp32 [B, n_new] aligned with the tokens: the log-probability of each
+    returned token under the model's RAW logits - log_softmax at temperature 1, no penalty, nothing filtered, the formula of
+    Llama.token_logprobs - computed by the sampler launch itself; positions after a row's `eos_id` hold 0.0.  That is the model's
+    probability of the token, comparable across sampling settings; it is the probability the token was drawn with only when
+    temperature == 1 and no filter and no penalty is on.  Penalties and `return_logprobs` are refused with `num_beams` != 1 (beams rank
+    by their own log-probabilities) and with `draft_tokens` != 0 (the rows of a draft step would each need the counts of another prefix)."""
     check_params(temperature, top_k, top_p, seed)
+    check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
+    penalised = penalties_on(repetition_penalty, presence_penalty, frequency_penalty)
+    for name, value, off in (("num_beams", num_beams, 1), ("draft_tokens", draft_tokens, 0)):
+        if value != off and penalised:
+            raise LlxError(f"{name}={value!r} cannot be combined with repetition_penalty={repetition_penalty!r}, presence_penalty="
+                           f"{presence_penalty!r}, frequency_penalty={frequency_penalty!r}: the penalties shape the draw of the plain loops only")
+        if value != off and return_logprobs:
+            raise LlxError(f"{name}={value!r} cannot be combined with return_logprobs=True: the sampler of the plain loops reports them")
     lens = _check(model, prompt, max_new_tokens, eos_id, prefill_chunk, check_every, prompt_lens,
                   (draft_tokens, draft_ngram, temperature) if draft_tokens != 0 else None,
                   (num_beams, length_penalty, temperature, top_k, top_p, draft_tokens) if num_beams != 1 else None, audio)
@@ -423,9 +469,16 @@ def generate(model, prompt: Tensor, max_new_tokens: int, *, temperature: float =
     call = _caller(model)
     if num_beams != 1:
         return _generate_beam(model, call, prompt, audio, n, num_beams, float(length_penalty), eos_id, prefill_chunk, check_every, stats)
+    sampling = dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
+    seen = None
+    if penalised:
+        sampling.update(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty)
+        seen = seed_counts(prompt, lens, model.config.vocab_size, penalize_prompt)
+    if stats is not None:
+        stats["counts"] = seen
     if prompt.shape[0] > 1 or (lens is not None and lens != [P]):
-        return _generate_batch(model, prompt, n, lens if lens is not None else [P] * prompt.shape[0],
-                               dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed), eos_id, prefill_chunk, check_every, call, audio)
+        return _generate_batch(model, prompt, n, lens if lens is not None else [P] * prompt.shape[0], sampling, eos_id, prefill_chunk,
+                               check_every, call, audio, seen, return_logprobs)
     if audio is not None:
         logits = prefill_audio(model, audio, prompt)
         P += model.audio_positions(audio.shape[1])  # from here on P is the length of the sequence: clip and prompt
@@ -451,8 +504,11 @@ def generate(model, prompt: Tensor, max_new_tokens: int, *, temperature: float =
     tok = torch.empty(1, 1, device=dev, dtype=torch.int64)
     history = torch.empty(1, n, device=dev, dtype=torch.int64)
     finished = torch.zeros(1, device=dev, dtype=torch.int32) if eos_id is not None else None
-    kw = dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, pos=pos, out=tok.view(1), history=history, hist_base=P - 1,
-              advance=True, eos_id=eos_id, finished=finished)
+    kw = dict(**sampling, pos=pos, out=tok.view(1), history=history, hist_base=P - 1, advance=True, eos_id=eos_id, finished=finished)
+    if seen is not None:
+        kw["counts"] = seen
+    if return_logprobs:
+        kw["logprob_history"] = torch.zeros(1, n, device=dev, dtype=torch.float32)
     K.sample(logits[0, -1:], **kw)
     count = n
     for k in range(1, n + 1):
@@ -467,4 +523,4 @@ def generate(model, prompt: Tensor, max_new_tokens: int, *, temperature: float =
         K.sample(call(tok, pos)[0], **kw)
     if stats is not None:
         stats.update(steps=count, tokens=count, accepted=0, draft_tokens=0, launched=k - 1)
-    return history[:, :count]
+    return (history[:, :count], kw["logprob_history"][:, :count]) if return_logprobs else history[:, :count]

@@ -1065,16 +1065,24 @@ def attn_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, mask: Tensor, exten
 # ------------------------------------------------------------------------------------------------- token sampler
 def sample(logits: Tensor, *, temperature: float, top_k: int = 0, top_p: float = 1.0, seed: int = 0, pos: Tensor, out: Optional[Tensor] = None,
            history: Optional[Tensor] = None, hist_base: int = 0, advance: bool = False, eos_id: Optional[int] = None,
-           finished: Optional[Tensor] = None, aux: bool = False):
+           finished: Optional[Tensor] = None, aux: bool = False, counts: Optional[Tensor] = None, repetition_penalty: float = 1.0,
+           presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logprob_history: Optional[Tensor] = None):
     """One token for each row of logits [R, V] or [1, R, V] (bf16 or fp32, last dim dense, any row stride and start offset), in one launch
     and without a host read: greedy at temperature 0, else temperature / top-k / top-p by the rules of llx/sampling.py.  pos (device int64
     [R]) is the counter of the random draw; advance stores pos + 1 back.  history (int64 [R, cap]) receives the token at pos - hist_base
     when that lies inside it.  eos_id with finished (device int32 [R]): finished rows repeat eos_id and touch nothing, a sampled eos_id
-    sets the flag.  Returns the tokens (int64 [R]), with aux=True (tokens, u fp32, threshold logit fp32, kept int32)."""
-    from .sampling import check_params
+    sets the flag.  Returns the tokens (int64 [R]), with aux=True (tokens, u fp32, threshold logit fp32, kept int32).
+
+    counts (device int32 [R, >= V], last dim dense): how often each token has occurred in the row's sequence.  With it the row is read
+    through the three penalties (rule 0 of llx/sampling.py; all of them at "off" change nothing) and the launch adds one at (r, token);
+    without it the penalties must be off.  logprob_history (fp32, the shape and strides of history, which it needs) receives the
+    token's log-probability on the raw logits where history receives the token.  A finished row touches neither.  With all five at
+    their defaults this is llx_sample_rows as before; otherwise llx_sample_rows_ext."""
+    from .sampling import check_params, check_penalties, penalties_on
 
     check_params(temperature, top_k, top_p, seed)
-    L.require_cuda(logits, pos, out, history, finished)
+    check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
+    L.require_cuda(logits, pos, out, history, finished, counts, logprob_history)
     if logits.dim() == 3:
         if logits.shape[0] != 1:
             raise L.LlxError(f"sample: logits [B, R, V] need B == 1 (got {tuple(logits.shape)})")
@@ -1104,6 +1112,28 @@ def sample(logits: Tensor, *, temperature: float, top_k: int = 0, top_p: float =
         au = torch.empty(R, device=logits.device, dtype=torch.float32)
         at = torch.empty(R, device=logits.device, dtype=torch.float32)
         ak = torch.empty(R, device=logits.device, dtype=torch.int32)
+    if counts is None and penalties_on(repetition_penalty, presence_penalty, frequency_penalty):
+        raise L.LlxError("sample: repetition_penalty / presence_penalty / frequency_penalty need the counts table")
+    if counts is not None or logprob_history is not None:
+        ldc = 0
+        if counts is not None:
+            if counts.dtype is not torch.int32 or counts.dim() != 2 or counts.shape[0] != R or counts.shape[1] < V or counts.stride(1) != 1 \
+                    or (R > 1 and counts.stride(0) < V):
+                raise L.LlxError(f"sample: counts must be a device int32 [{R}, >= {V}] with a dense last dim (got {counts.dtype} {tuple(counts.shape)})")
+            ldc = counts.stride(0) if R > 1 else counts.shape[1]
+        if logprob_history is not None:
+            if history is None:
+                raise L.LlxError("sample: logprob_history goes with history (they share one geometry)")
+            if logprob_history.dtype is not torch.float32 or logprob_history.shape != history.shape or logprob_history.stride() != history.stride():
+                raise L.LlxError(f"sample: logprob_history must be fp32 with the shape and strides of history {tuple(history.shape)} "
+                                 f"(got {logprob_history.dtype} {tuple(logprob_history.shape)})")
+        L.check(_lib().llx_sample_rows_ext(L.ptr(logits), 0 if logits.dtype is BF16 else 1, logits.stride(0) if R > 1 else V, R, V, float(temperature),
+                                           int(top_k), float(top_p), int(seed), L.ptr(pos), L.ptr(out), L.ptr(history), h_ld, h_cap, int(hist_base),
+                                           1 if advance else 0, int(eos_id) if eos_id is not None else -1, L.ptr(finished), L.ptr(au), L.ptr(at),
+                                           L.ptr(ak), L.ptr(counts), ldc, float(repetition_penalty), float(presence_penalty),
+                                           float(frequency_penalty), L.ptr(logprob_history), L.stream()), "llx_sample_rows_ext")
+        tokens = out.view(R)
+        return (tokens, au, at, ak) if aux else tokens
     L.check(_lib().llx_sample_rows(L.ptr(logits), 0 if logits.dtype is BF16 else 1, logits.stride(0) if R > 1 else V, R, V, float(temperature),
                                    int(top_k), float(top_p), int(seed), L.ptr(pos), L.ptr(out), L.ptr(history), h_ld, h_cap, int(hist_base),
                                    1 if advance else 0, int(eos_id) if eos_id is not None else -1, L.ptr(finished), L.ptr(au), L.ptr(at),

@@ -2,12 +2,23 @@
 
 Pure Python, no device needed.  The rules the kernel implements, all independent of any sort order and of how ties are arranged:
 
+0. penalties (llx_sample_rows_ext; off by default): with c_i the int32 count of how often token i has occurred in the row's sequence so
+   far and x_i the logit as fp32, an element with c_i == 0 keeps its bits; one with c_i > 0 becomes, every step a single IEEE fp32
+   operation in this order and none contracted into an FMA,
+     repetition_penalty theta (finite, > 0, 1 = off):  x = x / theta if x > 0 else x * theta   (a true divide, the HF rule; 0 and -inf stay)
+     presence_penalty a_p, frequency_penalty a_f (finite, 0 = off, negative allowed):  t = a_f * float(c);  t = a_p + t;  x = x - t.
+   Rules 1-6 and the reported threshold treat x as "the logit".  The launch that draws a token adds one to its count.
 1. temperature == 0: the argmax of the fp32 logits, lowest index among ties.
 2. otherwise z = logit / temperature in fp32; everything starts kept; a logit of -inf is never drawn.
 3. top_k > 0: with t the k-th largest z (duplicates counted), keep z >= t - ties at t all stay; top_k >= V is off.
 4. top_p < 1: with w = exp(z - z_max) over the kept set and W its sum, keep i iff the weight of {j: z_j > z_i} is < top_p * W.
 5. draw: walk the kept tokens by ascending index; the first whose running weight exceeds u * W (W over the final kept set).
 6. u = uniform(seed, pos, row) below: a multiple of 2^-24 in [0, 1), exact in fp32.
+
+The log-probability the sampler can report for the chosen token is defined on the RAW logits l - no penalties, temperature 1, nothing
+filtered: logp = (l_tok - l_max) - log sum_i exp(l_i - l_max), the formula of beam_shortlist and of Llama.token_logprobs.  It is the
+model's probability of the token, comparable across sampling settings; it equals the log-probability under the behaviour policy (the
+distribution the token was drawn from) only when temperature == 1 and no filter and no penalty is on.
 """
 from __future__ import annotations
 
@@ -40,6 +51,25 @@ def check_params(temperature: float, top_k: int, top_p: float, seed: int = 0) ->
         raise LlxError(f"top_p={top_p!r} must lie in (0, 1] (1 = off)")
     if not (isinstance(seed, int) and 0 <= seed <= _M64):
         raise LlxError(f"seed={seed!r} must be an unsigned 64-bit integer")
+
+
+def _finite(v) -> bool:
+    return isinstance(v, (int, float)) and not isinstance(v, bool) and v - v == 0
+
+
+def check_penalties(repetition_penalty: float, presence_penalty: float, frequency_penalty: float) -> None:
+    """Raise LlxError for penalties (rule 0) the kernel would reject (before anything is launched)."""
+    if not (_finite(repetition_penalty) and repetition_penalty > 0):
+        raise LlxError(f"repetition_penalty={repetition_penalty!r} must be a finite number > 0 (1 = off)")
+    if not _finite(presence_penalty):
+        raise LlxError(f"presence_penalty={presence_penalty!r} must be a finite number (0 = off)")
+    if not _finite(frequency_penalty):
+        raise LlxError(f"frequency_penalty={frequency_penalty!r} must be a finite number (0 = off)")
+
+
+def penalties_on(repetition_penalty: float, presence_penalty: float, frequency_penalty: float) -> bool:
+    """True if any of the three penalties would change a logit."""
+    return repetition_penalty != 1 or presence_penalty != 0 or frequency_penalty != 0
 
 
 # ---- prompt-lookup drafting: the host reference of csrc/lookup.hip (generate(draft_tokens=k)); pure lists of ints

@@ -391,7 +391,9 @@ class Llama(nn.Module):
         generate(); its input_pos branch above is what this drives).  prompt [B, P] with B the cache's batch; prompt_lens=... for
         right-padded prompts of different lengths; draft_tokens=k (greedy, one sequence) feeds k prompt-lookup draft tokens with every
         step and keeps the ones the model confirms: the same tokens in fewer weight passes; num_beams=W (one prompt, a cache of batch
-        W) is beam search with the beams as the rows of one batched step."""
+        W) is beam search with the beams as the rows of one batched step; repetition_penalty / presence_penalty / frequency_penalty
+        penalise the tokens a row has seen and return_logprobs=True also returns each token's log-probability, both inside the
+        sampler launch."""
         from llx.generate import generate
 
         return generate(self, prompt, max_new_tokens, **kwargs)
