@@ -1,7 +1,7 @@
 // Fused cross-entropy over bf16 logits: F.cross_entropy(logits.float(), labels) with ignore_index -100 and mean
 // reduction (modelling/llama.py:216-218, modelling/audio.py:74-76).  The fp32 copy of the [T, V] logits (2.1 GB at
 // T=4096, V=128256) is never materialised: one block streams a row twice (online max/sum, then gradient write).
-#include "common.h"
+#include "rowlse.h"
 
 #define CE_THREADS 512
 
@@ -43,25 +43,9 @@ __global__ __launch_bounds__(CE_THREADS) void ce_row_kernel(const bf16_t* logits
   }
   // the label's logit is read BEFORE anything is written: pass 2 of another wave overwrites it in place when dlogits == logits
   const float xl = (label >= 0 && label < V) ? bf2f(x[label]) : 0.f;
-  // pass 1: online (max, sum exp)
-  float m = -INFINITY, s = 0.f;
-  for (int c = threadIdx.x; c < nchunk; c += CE_THREADS) {
-    const u32x4_t v = *reinterpret_cast<const u32x4_t*>(x + c * 8);
-    float f[8];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { f[2 * e] = bflo(v[e]); f[2 * e + 1] = bfhi(v[e]); }
-    float cm = f[0];
-#pragma unroll
-    for (int e = 1; e < 8; ++e) cm = fmaxf(cm, f[e]);
-    const float mn = fmaxf(m, cm);
-    float add = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) add += __expf(f[e] - mn);
-    s = s * __expf(m - mn) + add;
-    m = mn;
-  }
-  const float gm = block_max(m, red);
-  s = block_sum(s * __expf(m - gm), red);
+  const RowLse r = row_lse_pass<false, CE_THREADS>(x, nchunk);  // pass 1: online (max, sum exp)
+  const float gm = block_max(r.m, red);
+  const float s = block_sum(r.s * __expf(r.m - gm), red);
   const float lse = gm + __logf(s);
   if (threadIdx.x == 0) row_loss[t] = lse - xl;
   if (!dlogits) return;
@@ -93,25 +77,40 @@ __global__ void ce_reduce_kernel(const float* __restrict__ row_loss, const float
 // workspace: (T + 2) floats: [0] 1/n_valid, [1] n_valid, [2..] per-row losses.  loss: 1 float (device).
 extern "C" int64_t llx_ce_workspace_bytes(int64_t T) { return (T + 2) * 4; }
 
-static int ce_fwd_bwd_impl(const void* logits, int64_t ld, void* dlogits, int64_t dld, const int64_t* labels, float* loss, void* workspace,
-                           int64_t T, int64_t V, const int32_t* rows_dyn, hipStream_t stream) {
-  LLX_REQUIRE(logits && labels && loss && workspace, "llx_ce_fwd_bwd: null pointer");
-  LLX_REQUIRE(V % 8 == 0 && ld % 8 == 0 && dld % 8 == 0, "llx_ce_fwd_bwd: V and row strides must be multiples of 8");
-  LLX_REQUIRE(T > 0 && V > 0 && V < (1 << 30), "llx_ce_fwd_bwd: bad sizes");
+static int ce_launched(const char* who, const char* step) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return LLX_OK;
+  llx_set_error("%s(%s): launch failed: %s", who, step, hipGetErrorString(e));
+  return LLX_ERR_LAUNCH;
+}
+
+// The launcher of the three entry points below (`who`: the entry's name in the messages): rows [row0, row0 + nrows) of a set of T rows,
+// `logits` / `dlogits` those rows, `labels` and `workspace` the whole set's; phase bit 0: count the labelled rows of the set first,
+// bit 1: reduce the per-row losses of the set into `loss` afterwards.
+static int ce_fwd_bwd_impl(const char* who, const void* logits, int64_t ld, void* dlogits, int64_t dld, const int64_t* labels, float* loss,
+                           void* workspace, int64_t T, int64_t V, int64_t row0, int64_t nrows, const int32_t* rows, int phase, hipStream_t stream) {
+  LLX_REQUIRE(logits && labels && loss && workspace, "%s: null pointer", who);
+  LLX_REQUIRE(V % 8 == 0 && ld % 8 == 0 && dld % 8 == 0, "%s: V and row strides must be multiples of 8", who);
+  LLX_REQUIRE(T > 0 && V > 0 && V < (1 << 30) && row0 >= 0 && nrows > 0 && row0 + nrows <= T, "%s: bad sizes", who);
+  LLX_REQUIRE(rows == nullptr || (uintptr_t)rows % 4 == 0, "%s: rows must be a device int32 pointer", who);
   float* ws = (float*)workspace;
-  hipLaunchKernelGGL(ce_count_kernel, dim3(1), dim3(1024), 0, stream, labels, ws, T);
-  LLX_LAUNCH_CHECK("llx_ce_fwd_bwd(count)");
-  hipLaunchKernelGGL(ce_row_kernel, dim3((unsigned)T), dim3(CE_THREADS), 0, stream, (const bf16_t*)logits, (bf16_t*)dlogits, ld, dld, labels,
-                     ws + 2, ws, (int)V, rows_dyn, (int64_t)0);
-  LLX_LAUNCH_CHECK("llx_ce_fwd_bwd(rows)");
-  hipLaunchKernelGGL(ce_reduce_kernel, dim3(1), dim3(1024), 0, stream, ws + 2, ws, loss, T);
-  LLX_LAUNCH_CHECK("llx_ce_fwd_bwd(reduce)");
+  if (phase & 1) {
+    hipLaunchKernelGGL(ce_count_kernel, dim3(1), dim3(1024), 0, stream, labels, ws, T);
+    if (int rc = ce_launched(who, "count")) return rc;
+  }
+  hipLaunchKernelGGL(ce_row_kernel, dim3((unsigned)nrows), dim3(CE_THREADS), 0, stream, (const bf16_t*)logits, (bf16_t*)dlogits, ld, dld, labels + row0,
+                     ws + 2 + row0, ws, (int)V, rows, row0);
+  if (int rc = ce_launched(who, "rows")) return rc;
+  if (phase & 2) {
+    hipLaunchKernelGGL(ce_reduce_kernel, dim3(1), dim3(1024), 0, stream, ws + 2, ws, loss, T);
+    if (int rc = ce_launched(who, "reduce")) return rc;
+  }
   return LLX_OK;
 }
 
 extern "C" int llx_ce_fwd_bwd(const void* logits, int64_t ld, void* dlogits, int64_t dld, const int64_t* labels, float* loss, void* workspace,
                               int64_t T, int64_t V, hipStream_t stream) {
-  return ce_fwd_bwd_impl(logits, ld, dlogits, dld, labels, loss, workspace, T, V, nullptr, stream);
+  return ce_fwd_bwd_impl("llx_ce_fwd_bwd", logits, ld, dlogits, dld, labels, loss, workspace, T, V, 0, T, nullptr, 3, stream);
 }
 
 // As llx_ce_fwd_bwd over COMPACTED rows (llx_head_compact_index): the labelled rows come first, *rows (device int32) is their number;
@@ -119,7 +118,7 @@ extern "C" int llx_ce_fwd_bwd(const void* logits, int64_t ld, void* dlogits, int
 extern "C" int llx_ce_fwd_bwd_rows(const void* logits, int64_t ld, void* dlogits, int64_t dld, const int64_t* labels, float* loss,
                                    void* workspace, int64_t T, int64_t V, const int32_t* rows, hipStream_t stream) {
   LLX_REQUIRE(rows && (uintptr_t)rows % 4 == 0, "llx_ce_fwd_bwd_rows: rows must be a device int32 pointer");
-  return ce_fwd_bwd_impl(logits, ld, dlogits, dld, labels, loss, workspace, T, V, rows, stream);
+  return ce_fwd_bwd_impl("llx_ce_fwd_bwd_rows", logits, ld, dlogits, dld, labels, loss, workspace, T, V, 0, T, rows, 3, stream);
 }
 
 // The same loss over a row set too large for one logits buffer (the GEMM's 32-bit tile offsets stop at 4 GiB = 16.7 k rows of a
@@ -128,23 +127,7 @@ extern "C" int llx_ce_fwd_bwd_rows(const void* logits, int64_t ld, void* dlogits
 // losses of the whole set into `loss`.  Every row sees the global 1 / n_valid, so the values are those of one call over all rows.
 extern "C" int llx_ce_fwd_bwd_part(const void* logits, int64_t ld, void* dlogits, int64_t dld, const int64_t* labels, float* loss, void* workspace,
                                    int64_t T, int64_t V, int64_t row0, int64_t nrows, const int32_t* rows, int phase, hipStream_t stream) {
-  LLX_REQUIRE(logits && labels && loss && workspace, "llx_ce_fwd_bwd_part: null pointer");
-  LLX_REQUIRE(V % 8 == 0 && ld % 8 == 0 && dld % 8 == 0, "llx_ce_fwd_bwd_part: V and row strides must be multiples of 8");
-  LLX_REQUIRE(T > 0 && V > 0 && V < (1 << 30) && row0 >= 0 && nrows > 0 && row0 + nrows <= T, "llx_ce_fwd_bwd_part: bad sizes");
-  LLX_REQUIRE(rows == nullptr || (uintptr_t)rows % 4 == 0, "llx_ce_fwd_bwd_part: rows must be a device int32 pointer");
-  float* ws = (float*)workspace;
-  if (phase & 1) {
-    hipLaunchKernelGGL(ce_count_kernel, dim3(1), dim3(1024), 0, stream, labels, ws, T);
-    LLX_LAUNCH_CHECK("llx_ce_fwd_bwd_part(count)");
-  }
-  hipLaunchKernelGGL(ce_row_kernel, dim3((unsigned)nrows), dim3(CE_THREADS), 0, stream, (const bf16_t*)logits, (bf16_t*)dlogits, ld, dld, labels + row0,
-                     ws + 2 + row0, ws, (int)V, rows, row0);
-  LLX_LAUNCH_CHECK("llx_ce_fwd_bwd_part(rows)");
-  if (phase & 2) {
-    hipLaunchKernelGGL(ce_reduce_kernel, dim3(1), dim3(1024), 0, stream, ws + 2, ws, loss, T);
-    LLX_LAUNCH_CHECK("llx_ce_fwd_bwd_part(reduce)");
-  }
-  return LLX_OK;
+  return ce_fwd_bwd_impl("llx_ce_fwd_bwd_part", logits, ld, dlogits, dld, labels, loss, workspace, T, V, row0, nrows, rows, phase, stream);
 }
 
 // ------------------------------------------------------------------------------------------ LM-head row compaction

@@ -88,6 +88,17 @@ __device__ __forceinline__ float block_max(float v, float* red) {
   for (int i = 1; i < nw; ++i) t = fmaxf(t, red[i]);
   return t;
 }
+__device__ __forceinline__ int block_min_i32(int v, int* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+  __syncthreads();
+  if (lane == 0) red[w] = v;
+  __syncthreads();
+  int t = red[0];
+  for (int k = 1; k < nw; ++k) t = min(t, red[k]);
+  return t;
+}
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

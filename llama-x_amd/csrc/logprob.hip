@@ -3,26 +3,12 @@
 // d logits in its forward because its upstream gradient is one scalar that can be applied afterwards; a per-row gradient cannot be
 // applied later without a second bf16 rounding, so here the forward keeps the logits and the backward makes the second pass over the
 // row in place, when g[t] is known: one rounding of d logits, and the traffic of forward + backward equals the loss path's.
-#include "common.h"
-
-#include <climits>
+#include "rowlse.h"
 
 #define LP_THREADS 512
 
-__device__ __forceinline__ int block_min_i32(int v, int* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-  __syncthreads();
-  if (lane == 0) red[w] = v;
-  __syncthreads();
-  int t = red[0];
-  for (int k = 1; k < nw; ++k) t = min(t, red[k]);
-  return t;
-}
-
-// One block per row: logp[t] = x[label] - lse[t], lse from the online (max, sum exp) pass of ce_row_kernel (same arithmetic, same order:
-// the values are those of its pass 1), top1[t] (nullable) = index of the largest logit, the lowest among ties.  Ignored rows
+// One block per row: logp[t] = x[label] - lse[t], lse from the online (max, sum exp) pass that ce_row_kernel runs too (rowlse.h: the
+// values are those of its pass 1), top1[t] (nullable) = index of the largest logit, the lowest among ties.  Ignored rows
 // (label == -100): logp = lse = 0, top1 = -1, logits not read.  Rows at or past rows_dyn[0] rounded up to 256: zeros, nothing read.
 __global__ __launch_bounds__(LP_THREADS) void logprob_row_fwd_kernel(const bf16_t* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
                                                                       float* __restrict__ logp, float* __restrict__ lse_out, int32_t* __restrict__ top1,
@@ -50,31 +36,9 @@ __global__ __launch_bounds__(LP_THREADS) void logprob_row_fwd_kernel(const bf16_
   const bf16_t* x = logits + t * ld;
   const int nchunk = V >> 3;
   const float xl = (label >= 0 && label < V) ? bf2f(x[label]) : 0.f;  // a label outside [0, V): as ce_row_kernel, its logit counts as 0
-  float m = -INFINITY, s = 0.f;
-  int arg = INT_MAX;  // index of this thread's first element equal to m
-  for (int c = threadIdx.x; c < nchunk; c += LP_THREADS) {
-    const u32x4_t v = *reinterpret_cast<const u32x4_t*>(x + c * 8);
-    float f[8];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { f[2 * e] = bflo(v[e]); f[2 * e + 1] = bfhi(v[e]); }
-    float cm = f[0];
-#pragma unroll
-    for (int e = 1; e < 8; ++e) cm = fmaxf(cm, f[e]);
-    if (cm > m) {  // strictly larger: a thread's chunks ascend, so its first maximum stays
-      int ce = 7;
-#pragma unroll
-      for (int e = 6; e >= 0; --e) ce = (f[e] == cm) ? e : ce;
-      arg = c * 8 + ce;
-    }
-    const float mn = fmaxf(m, cm);
-    float add = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) add += __expf(f[e] - mn);
-    s = s * __expf(m - mn) + add;
-    m = mn;
-  }
-  const float gm = block_max(m, red);
-  s = block_sum(s * __expf(m - gm), red);
+  const RowLse r = row_lse_pass<true, LP_THREADS>(x, nchunk);
+  const float gm = block_max(r.m, red);
+  const float s = block_sum(r.s * __expf(r.m - gm), red);
   const float ls = __logf(s);
   if (threadIdx.x == 0) {
     // x[label] - lse, taken as (x[label] - max) - log(sum): the first difference is exact for bf16 operands, so logp does not inherit the
@@ -83,7 +47,7 @@ __global__ __launch_bounds__(LP_THREADS) void logprob_row_fwd_kernel(const bf16_
     lse_out[t] = gm + ls;
   }
   if (top1) {
-    const int a = block_min_i32(m == gm ? arg : INT_MAX, redi);
+    const int a = block_min_i32(r.m == gm ? r.arg : INT_MAX, redi);
     if (threadIdx.x == 0) top1[t] = a == INT_MAX ? 0 : a;  // (a row without any finite maximum: index 0)
   }
 }

@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import os
 
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import torch
 from torch import Tensor, nn
@@ -849,14 +849,115 @@ class MLPBlockFn(Function):
 
 
 # =================================================================================================
-# final norm + LM head + cross-entropy (modelling/llama.py:216-218)
+# final norm + LM head + cross-entropy (modelling/llama.py:216-218), and the per-token terms of that mean:
+# -F.cross_entropy(..., reduction="none", ignore_index=-100).  HeadLossFn and HeadLogprobFn share the route, the row walk, the logits
+# GEMMs and the whole backward after d logits; each keeps its row kernel, what it saves, its upstream gradient and its refusals.
 # =================================================================================================
+class HeadRoute(NamedTuple):
+    plain_head: bool  # a plain head (no adapter, no bias, bf16), frozen: only d hidden is wanted from its backward
+    # a plain trainable head (the reference's default, train_metamathqa.py:177-180) under compaction: its weight gradient
+    # dW = d logits^T . norm(x) runs over the compacted rows too - the TN kernel reads the row count from device memory
+    plain_trainable: bool
+    compact: bool  # logits GEMM, row kernel and d-hidden GEMM over the labelled rows only
+    chunk: int  # rows per logits buffer when the rows are walked in chunks, else 0
+
+
+def _head_route(plan, weight_needs: bool, T: int, V: int) -> HeadRoute:
+    """How T rows go through a head of V entries (no device work).  None of the three flags: plan.forward / plan.backward over all rows.
+    T-chunked head: one [rows, V] logits buffer is limited by the GEMM's 32-bit tile offsets (4 GiB = 16.7 k rows of a 128 k vocabulary;
+    the reference's packed [1, bs * S] batches get there at bs >= 5): beyond that the rows are walked in chunks - one logits buffer, one
+    row-kernel launch set and (in backward) one d-hidden product per chunk.  Same per-row arithmetic: bit-identical to the unchunked
+    path (LLX_HEAD_CHUNK_ROWS forces chunking for tests)."""
+    plain = not plan.int8 and plan.rank == 0 and plan.bias is None and plan.dora_m is None
+    chunk = _HEAD_CHUNK_ROWS if (_HEAD_CHUNK_FORCED or T * V * 2 >= 2**32) else 0
+    return HeadRoute(plain and not weight_needs, plain and weight_needs and _HEAD_COMPACT, plain and _HEAD_COMPACT, chunk if T > chunk else 0)
+
+
+def _head_rows(xn: Tensor, labels: Tensor, route: HeadRoute):
+    """(rows_in, labels_in, idx, inv, cnt): the rows the head runs over and their labels.  Labelled-row compaction (default;
+    LLX_HEAD_COMPACT=0 turns it off): F.cross_entropy(ignore_index=-100) gives a position whose label is -100 no loss term and a zero
+    gradient row (modelling/llama.py:216-218), so a plain head runs over the labelled rows only - gathered in order on the device, the
+    count read by the kernels from device memory (no host sync, capturable), d hidden scattered back with zero rows in between.  Same
+    per-row arithmetic: every value is bit-identical to the uncompacted path; a batch with a masked prompt saves that share of the head."""
+    if not route.compact:
+        return xn, labels.reshape(-1).contiguous(), None, None, None
+    idx, inv, labels_c, cnt = K.head_compact_index(labels)
+    return K.gather_rows(xn, idx, cnt), labels_c, idx, inv, cnt
+
+
+def _head_logits(plan: LinearPlan, rows_in: Tensor, route: HeadRoute, cnt: Optional[Tensor]):
+    """The bf16 logits of the one buffer, or of each chunk [r0, r1) of the row walk: yields (r0, r1, logits, cnt_c, t, m_expect) with
+    cnt_c the labelled rows inside the buffer (device int32, compacted rows only), t what plan.forward saved, m_expect the row count
+    for the accounting of a traced eager step (one buffer only: the one host read of the head)."""
+    T = rows_in.shape[0]
+    step = route.chunk or T
+    for r0 in range(0, T, step):
+        r1 = min(T, r0 + step)
+        if not route.compact:
+            logits, t = plan.forward(rows_in[r0:r1])
+            yield r0, r1, logits, None, t, None
+            continue
+        m_expect = None
+        if route.chunk:
+            cnt_c = torch.clamp(cnt - r0, min=0, max=r1 - r0).to(torch.int32)
+        else:
+            cnt_c = cnt
+            m_expect = float(cnt.item()) if K.GEMM_TRACE is not None else None
+        logits = torch.empty(r1 - r0, plan.N, device=rows_in.device, dtype=BF16)
+        K.gemm_nt(rows_in[r0:r1], plan.weight.detach(), out=logits, m_valid=cnt_c, m_expect=m_expect)
+        yield r0, r1, logits, cnt_c, None, m_expect
+
+
+def _head_dhidden(route: HeadRoute, plan: LinearPlan, dlogits, cnt, inv: Optional[Tensor], scalar: Optional[Tensor], m_expect) -> Tensor:
+    """d hidden = scalar * d logits . W of a plain head, at the positions of all rows.  [T, D] is ONE round of 256 tiles whatever the row
+    count, with a contraction over the whole vocabulary - cut in K ranges computed side by side, so that fewer rows (12 x 16 tiles at
+    3071 labelled rows) still fill the chip with full rounds of short tiles.  Every route uses the same split, so they stay
+    bit-identical to each other.  Chunked rows: dlogits and cnt are tuples with one entry per chunk - a product per chunk into one
+    buffer, then one scatter / scale over all rows."""
+    wt = weight_t(plan.weight)
+    split = wt.shape[1] % (64 * _HEAD_SPLITK) == 0
+    if route.chunk:
+        dxc = torch.empty(sum(dl.shape[0] for dl in dlogits), wt.shape[0], device=wt.device, dtype=BF16)
+        for i, (dl, cnt_c) in enumerate(zip(dlogits, cnt)):
+            part = K.gemm_nt_splitk(dl, wt, _HEAD_SPLITK, m_valid=cnt_c) if split else K.gemm_nt(dl, wt, m_valid=cnt_c)
+            dxc[i * route.chunk : i * route.chunk + dl.shape[0]].copy_(part)
+    elif split:  # (scatter and scalar ride in the combine of the K ranges)
+        return K.gemm_nt_splitk(dlogits, wt, _HEAD_SPLITK, m_valid=cnt, inv=inv, dev_scalar=scalar, m_expect=m_expect)
+    else:
+        dxc = K.gemm_nt(dlogits, wt, m_valid=cnt, m_expect=m_expect)
+    if inv is not None:
+        return K.scatter_rows(dxc, inv, scalar)
+    return dxc if scalar is None else K.scale(dxc, dev_scalar=scalar)
+
+
+def _head_backward(ctx, n_lead: int, saved, dlogits, inv, cnt, t, scalar: Optional[Tensor]):
+    """Everything after d logits, for a head Function whose first n_lead inputs are (x, norm_w, <non-tensors>) and the rest
+    plan.tensors(): scalar (device fp32, or None) multiplies every gradient."""
+    route, plan = ctx.route, ctx.plan
+    x, norm_w, x2, xn, rstd = saved
+    needs = ctx.needs_input_grad[n_lead:]
+    need_dxn = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+    if route.plain_head or route.plain_trainable:
+        dx = dnw = gw = None
+        if need_dxn:
+            dx, dnw = _norm_epilogue(_head_dhidden(route, plan, dlogits, cnt, inv, scalar, ctx.m_expect), x2, norm_w, rstd, ctx.needs_input_grad[1])
+        if route.plain_trainable:  # dW over the labelled rows (xn holds their gathered, normed activations)
+            gw = K.gemm_tn(dlogits, xn, m_valid=cnt, m_expect=ctx.m_expect)
+            gw = gw if scalar is None else K.scale(gw, dev_scalar=scalar)
+        grads = [gw] + [None] * (len(needs) - 1) if needs else []
+    else:
+        dxn, grads = plan.backward(dlogits, xn, t, needs, need_dx=need_dxn)
+        if scalar is not None:
+            grads = [None if g is None else K.scale(g, dev_scalar=scalar) for g in grads]
+            if dxn is not None:
+                K.scale(dxn, dev_scalar=scalar, out=dxn)
+        dx, dnw = _norm_epilogue(dxn, x2, norm_w, rstd, ctx.needs_input_grad[1])
+    return (dx.view(x.shape) if dx is not None else None, dnw, *([None] * (n_lead - 2)), *grads)
+
+
 class HeadLossFn(Function):
-    """Labelled-row compaction (default; LLX_HEAD_COMPACT=0 turns it off): F.cross_entropy(ignore_index=-100) gives a position whose
-    label is -100 no loss term and a zero gradient row (modelling/llama.py:216-218), so with a frozen plain head the logits GEMM, the
-    loss and the d-hidden GEMM run over the labelled rows only - gathered in order on the device, the count read by the kernels from
-    device memory (no host sync, capturable), d hidden scattered back with zero rows in between.  Same per-row arithmetic, same loss
-    terms: every gradient is bit-identical to the uncompacted path; an SFT batch with a masked prompt saves that share of the head."""
+    """Mean cross-entropy of the labelled rows.  Its upstream gradient is one scalar that can be applied afterwards, so the row kernel
+    writes d logits over the logits in the forward and the backward multiplies by the device scalar."""
 
     @staticmethod
     def forward(ctx, x: Tensor, norm_w: Tensor, labels: Tensor, eps: float, plan: LinearPlan, *tensors):
@@ -864,119 +965,39 @@ class HeadLossFn(Function):
         x2 = K._rows2d(x.contiguous())
         xn, rstd = K.rmsnorm_fwd(x2, norm_w.detach(), eps)
         need_grad = any(ctx.needs_input_grad)
-        ctx.plan, ctx.eps = plan, eps
-        # a plain head (no adapter, no bias, bf16).  Frozen: only d hidden is wanted from its backward.  Trainable (the reference's default,
-        # train_metamathqa.py:177-180): its weight gradient dW = d logits^T . norm(x) runs over the compacted rows too - the TN kernel reads
-        # the row count from device memory.
-        plain = not plan.int8 and plan.rank == 0 and plan.bias is None and plan.dora_m is None
-        ctx.plain_head = plain and not any(ctx.needs_input_grad[5:])
-        ctx.plain_trainable = plain and not ctx.plain_head and _HEAD_COMPACT
-        ctx.compact = _HEAD_COMPACT and plain
-        ctx.m_expect = None
         T, V = x2.shape[0], plan.N
-        # T-chunked head: one [rows, V] logits buffer is limited by the GEMM's 32-bit tile offsets (4 GiB = 16.7 k rows of a 128 k
-        # vocabulary; the reference's packed [1, bs * S] batches get there at bs >= 5): beyond that the rows are walked in chunks - one
-        # logits buffer, one CE launch set and (in backward) one d-hidden product per chunk, the loss normalised by the global count of
-        # labelled rows.  Same per-row arithmetic: bit-identical to the unchunked path (LLX_HEAD_CHUNK_ROWS forces chunking for tests).
-        chunk = _HEAD_CHUNK_ROWS if (_HEAD_CHUNK_FORCED or T * V * 2 >= 2**32) else 0
-        if chunk and T > chunk:
-            if not ctx.plain_head:
-                raise LlxError(f"LM head over {T} rows x {V} vocabulary entries exceeds one logits buffer (4 GiB) and a trainable / adapted / "
-                               "quantised head is not chunked: freeze the plain head or lower the number of positions per step")
-            inv = cnt = None
-            rows_in, labels_in = xn, labels.reshape(-1).contiguous()
-            if ctx.compact:
-                idx, inv, labels_in, cnt = K.head_compact_index(labels)
-                rows_in = K.gather_rows(xn, idx, cnt)
-            w = plan.weight.detach()
+        ctx.plan, ctx.eps, ctx.m_expect = plan, eps, None
+        route = ctx.route = _head_route(plan, any(ctx.needs_input_grad[5:]), T, V)
+        if route.chunk and not route.plain_head:
+            raise LlxError(f"LM head over {T} rows x {V} vocabulary entries exceeds one logits buffer (4 GiB) and a trainable / adapted / "
+                           "quantised head is not chunked: freeze the plain head or lower the number of positions per step")
+        rows_in, labels_in, _, inv, cnt = _head_rows(xn, labels, route)
+        if route.chunk:  # one CE launch set per chunk, the loss normalised by the global count of labelled rows
             ws = torch.empty(T + 2, device=x.device, dtype=torch.float32)
             loss = torch.empty((), device=x.device, dtype=torch.float32)
-            parts = []
-            for r0 in range(0, T, chunk):
-                r1 = min(T, r0 + chunk)
-                cnt_c = torch.clamp(cnt - r0, min=0, max=r1 - r0).to(torch.int32) if cnt is not None else None  # labelled rows inside this chunk
-                lg = torch.empty(r1 - r0, V, device=x.device, dtype=BF16)
-                K.gemm_nt(rows_in[r0:r1], w, out=lg, m_valid=cnt_c)
-                parts.append((K.ce_chunk(lg, labels_in, ws, loss, r0, need_grad, cnt, r0 == 0, r1 == T), cnt_c))
-            ctx.chunk = chunk
-            _save(ctx, x, norm_w, x2, None, rstd, tuple(p[0] for p in parts), (inv, cnt, tuple(p[1] for p in parts)))
+            parts = [(K.ce_chunk(lg, labels_in, ws, loss, r0, need_grad, cnt, r0 == 0, r1 == T), cnt_c)
+                     for r0, r1, lg, cnt_c, _, _ in _head_logits(plan, rows_in, route, cnt)]
+            _save(ctx, x, norm_w, x2, None, rstd, tuple(p[0] for p in parts), inv, tuple(p[1] for p in parts), None)
             return loss
-        ctx.chunk = 0
-        if ctx.compact:
-            idx, inv, labels_c, cnt = K.head_compact_index(labels)
-            xc = K.gather_rows(xn, idx, cnt)
-            w = plan.weight.detach()
-            logits = torch.empty(xc.shape[0], w.shape[0], device=x.device, dtype=BF16)
-            ctx.m_expect = float(cnt.item()) if K.GEMM_TRACE is not None else None  # accounting of the traced eager step only
-            K.gemm_nt(xc, w, out=logits, m_valid=cnt, m_expect=ctx.m_expect)
-            loss, dlogits = K.ce_fwd_bwd(logits, labels_c, write_grad=need_grad, rows=cnt)
-            _save(ctx, x, norm_w, x2, xc if ctx.plain_trainable else None, rstd, dlogits, (inv, cnt))
-            return loss
-        logits, t = plan.forward(xn)
-        loss, dlogits = K.ce_fwd_bwd(logits, labels, write_grad=need_grad)
-        _save(ctx, x, norm_w, x2, xn, rstd, dlogits, t)
+        ((_, _, logits, _, t, m_expect),) = _head_logits(plan, rows_in, route, cnt)
+        ctx.m_expect = m_expect
+        loss, dlogits = K.ce_fwd_bwd(logits, labels_in, write_grad=need_grad, rows=cnt)
+        _save(ctx, x, norm_w, x2, rows_in if (route.plain_trainable or not route.compact) else None, rstd, dlogits, inv, cnt, t)
         return loss
 
     @staticmethod
     def backward(ctx, gout: Tensor):
-        plan: LinearPlan = ctx.plan
-        x, norm_w, x2, xn, rstd, dlogits, t = _load(ctx)
-        needs = ctx.needs_input_grad[5:]
+        x, norm_w, x2, xn, rstd, dlogits, inv, cnt, t = _load(ctx)
         g32 = gout.detach().to(torch.float32).reshape(1)
-        if ctx.plain_head or ctx.plain_trainable:
-            # d hidden = d logits . W: [T, D] is ONE round of 256 tiles whatever the row count, with a contraction over the whole
-            # vocabulary - cut in K ranges computed side by side, so that fewer rows (12 x 16 tiles at 3071 labelled rows) still fill
-            # the chip with full rounds of short tiles.  The compacted and the uncompacted path use the same split, so they stay
-            # bit-identical to each other.
-            if ctx.chunk:  # chunked rows (see forward): d hidden chunk by chunk, then one scatter / scale over all rows
-                inv, cnt, cnts = t
-                dx = dnw = None
-                if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-                    wt = weight_t(plan.weight)
-                    T = x2.shape[0]
-                    split = wt.shape[1] % (64 * _HEAD_SPLITK) == 0
-                    dxc = torch.empty(T, wt.shape[0], device=x.device, dtype=BF16)
-                    for i, (dl, cnt_c) in enumerate(zip(dlogits, cnts)):
-                        r0 = i * ctx.chunk
-                        part = K.gemm_nt_splitk(dl, wt, _HEAD_SPLITK, m_valid=cnt_c) if split else K.gemm_nt(dl, wt, m_valid=cnt_c)
-                        dxc[r0 : r0 + dl.shape[0]].copy_(part)
-                    dxn = K.scatter_rows(dxc, inv, g32) if inv is not None else K.scale(dxc, dev_scalar=g32)
-                    dx, dnw = _norm_epilogue(dxn, x2, norm_w, rstd, ctx.needs_input_grad[1])
-                return (dx.view(x.shape) if dx is not None else None, dnw, None, None, None, *([None] * len(needs)))
-            inv, cnt = t if ctx.compact else (None, None)
-            dx = dnw = None
-            if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-                wt = weight_t(plan.weight)
-                if wt.shape[1] % (64 * _HEAD_SPLITK) == 0:
-                    dxn = K.gemm_nt_splitk(dlogits, wt, _HEAD_SPLITK, m_valid=cnt, inv=inv, dev_scalar=g32, m_expect=ctx.m_expect)
-                elif ctx.compact:
-                    dxn = K.scatter_rows(K.gemm_nt(dlogits, wt, m_valid=cnt, m_expect=ctx.m_expect), inv, g32)
-                else:
-                    dxn = K.scale(K.gemm_nt(dlogits, wt), dev_scalar=g32)
-                dx, dnw = _norm_epilogue(dxn, x2, norm_w, rstd, ctx.needs_input_grad[1])
-            gw = None
-            if ctx.plain_trainable:  # dW over the labelled rows (xn holds their gathered, normed activations), scaled by the incoming gradient
-                gw = K.scale(K.gemm_tn(dlogits, xn, m_valid=cnt, m_expect=ctx.m_expect), dev_scalar=g32)
-            return (dx.view(x.shape) if dx is not None else None, dnw, None, None, None, *([gw] + [None] * (len(needs) - 1) if needs else []))
-        dxn, grads = plan.backward(dlogits, xn, t, needs, need_dx=ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
-        grads = [None if g is None else K.scale(g, dev_scalar=g32) for g in grads]
-        if dxn is not None:
-            K.scale(dxn, dev_scalar=g32, out=dxn)
-        dx, dnw = _norm_epilogue(dxn, x2, norm_w, rstd, ctx.needs_input_grad[1])
-        return (dx.view(x.shape) if dx is not None else None, dnw, None, None, None, *grads)
+        return _head_backward(ctx, 5, (x, norm_w, x2, xn, rstd), dlogits, inv, cnt, t, g32)
 
 
-# =================================================================================================
-# final norm + LM head + per-token log-probabilities: -F.cross_entropy(..., reduction="none", ignore_index=-100)
-# =================================================================================================
 class HeadLogprobFn(Function):
-    """HeadLossFn's sibling for the per-row terms of its mean: fp32 [T] log-probabilities of the labels (0 at ignored positions), with the
-    row argmax as a second, non-differentiable output with want_top1.  Same routes: a plain head runs over the compacted labelled
-    rows (gather -> row-limited GEMM -> row kernel -> scatter through `inv`), any other head through its plan.  The upstream gradient is
-    per row, so - unlike the loss path, whose one scalar can be applied after the fact - d logits is not written in the forward: the
-    forward keeps the logits in the buffer where the loss path keeps d logits, and the backward turns them into d logits in place once
-    g is known (one bf16 rounding, the same traffic over forward + backward).  Without gradients nothing is saved, and a row set beyond
-    one logits buffer is walked in chunks (one GEMM and one row-kernel launch each; same per-row arithmetic, bit-identical)."""
+    """fp32 [T] log-probabilities of the labels (0 at ignored positions), with the row argmax as a second, non-differentiable output
+    with want_top1.  The upstream gradient is per row, so - unlike the loss, whose one scalar can be applied after the fact - d logits
+    is not written in the forward: the forward keeps the logits in the buffer where the loss keeps d logits, and the backward turns
+    them into d logits in place once g is known (one bf16 rounding, the same traffic over forward + backward).  Without gradients
+    nothing is saved, and a row set beyond one logits buffer is walked in chunks."""
 
     @staticmethod
     def forward(ctx, x: Tensor, norm_w: Tensor, labels: Tensor, eps: float, plan: LinearPlan, want_top1: bool, *tensors):
@@ -984,56 +1005,27 @@ class HeadLogprobFn(Function):
         x2 = K._rows2d(x.contiguous())
         xn, rstd = K.rmsnorm_fwd(x2, norm_w.detach(), eps)
         need_grad = any(ctx.needs_input_grad) and not getattr(plan, "no_grad", False)  # (needs_input_grad does not see the caller's no_grad)
-        ctx.plan = plan
-        plain = not plan.int8 and plan.rank == 0 and plan.bias is None and plan.dora_m is None
-        ctx.plain_head = plain and not any(ctx.needs_input_grad[6:])
-        ctx.plain_trainable = plain and not ctx.plain_head and _HEAD_COMPACT
-        ctx.compact = _HEAD_COMPACT and plain
-        ctx.m_expect = None
         T, V = x2.shape[0], plan.N
+        ctx.plan = plan
+        route = ctx.route = _head_route(plan, any(ctx.needs_input_grad[6:]), T, V)
         if need_grad and V % 64 != 0:  # (as the loss path: its d-hidden GEMM contracts over the vocabulary; said here, not in the middle of backward)
             raise LlxError(f"token log-probabilities with gradients need a vocabulary that is a multiple of 64 (got {V}): the d-hidden GEMM "
                            "contracts over it in 64-column steps - score under torch.no_grad() or pad the vocabulary")
-        chunk = _HEAD_CHUNK_ROWS if (_HEAD_CHUNK_FORCED or T * V * 2 >= 2**32) else 0
-        if chunk and T > chunk and need_grad:
+        if route.chunk and need_grad:
             raise LlxError(f"LM head over {T} rows x {V} vocabulary entries exceeds one logits buffer (4 GiB) and token log-probabilities "
                            "with gradients are not chunked: score under torch.no_grad() or lower the number of positions per step")
-        labels_in = labels.reshape(-1).contiguous()
-        idx = inv = cnt = None
-        rows_in = xn
-        if ctx.compact:
-            idx, inv, labels_in, cnt = K.head_compact_index(labels)
-            rows_in = K.gather_rows(xn, idx, cnt)
-        if chunk and T > chunk:
-            parts = []
-            for r0 in range(0, T, chunk):
-                r1 = min(T, r0 + chunk)
-                if ctx.compact:
-                    cnt_c = torch.clamp(cnt - r0, min=0, max=r1 - r0).to(torch.int32)  # labelled rows inside this chunk
-                    lg = torch.empty(r1 - r0, V, device=x.device, dtype=BF16)
-                    K.gemm_nt(rows_in[r0:r1], plan.weight.detach(), out=lg, m_valid=cnt_c)
-                else:
-                    cnt_c = None
-                    lg, _ = plan.forward(rows_in[r0:r1])
-                parts.append(K.logprob_rows_fwd(lg, labels_in[r0:r1], rows=cnt_c, want_top1=want_top1))
+        rows_in, labels_in, idx, inv, cnt = _head_rows(xn, labels, route)
+        parts = []
+        for r0, r1, logits, cnt_c, t, m_expect in _head_logits(plan, rows_in, route, cnt):
+            parts.append(K.logprob_rows_fwd(logits, labels_in[r0:r1], rows=cnt_c, want_top1=want_top1))
+        ctx.m_expect = m_expect
+        logp, lse, top1 = parts[0]
+        if route.chunk:
             logp = torch.cat([p[0] for p in parts])
             top1 = torch.cat([p[2] for p in parts]) if want_top1 else None
-            return HeadLogprobFn._finish(ctx, logp, top1, inv)
-        t = None
-        if ctx.compact:
-            logits = torch.empty(T, V, device=x.device, dtype=BF16)
-            ctx.m_expect = float(cnt.item()) if K.GEMM_TRACE is not None else None  # accounting of the traced eager step only
-            K.gemm_nt(rows_in, plan.weight.detach(), out=logits, m_valid=cnt, m_expect=ctx.m_expect)
-        else:
-            logits, t = plan.forward(xn)
-        logp, lse, top1 = K.logprob_rows_fwd(logits, labels_in, rows=cnt, want_top1=want_top1)
         if need_grad:
-            keep_rows = rows_in if (ctx.plain_trainable or not (ctx.plain_head or ctx.plain_trainable)) else None
-            _save(ctx, x, norm_w, x2, keep_rows, rstd, logits, lse, labels_in, (idx, inv, cnt), t)
-        return HeadLogprobFn._finish(ctx, logp, top1, inv)
-
-    @staticmethod
-    def _finish(ctx, logp: Tensor, top1: Optional[Tensor], inv: Optional[Tensor]):
+            keep_rows = rows_in if (route.plain_trainable or not (route.plain_head or route.plain_trainable)) else None
+            _save(ctx, x, norm_w, x2, keep_rows, rstd, logits, lse, labels_in, idx, inv, cnt, t)
         if inv is not None:  # compacted rows back to their positions: [T] vectors, zeros / -1 at the ignored positions
             logp, top1 = K.logprob_map_rows(inv, logp, 0.0, top1, -1)
         if top1 is None:
@@ -1043,35 +1035,16 @@ class HeadLogprobFn(Function):
 
     @staticmethod
     def backward(ctx, g: Tensor, *_):
-        plan: LinearPlan = ctx.plan
         if getattr(ctx, "consumed", False):
             raise LlxError("token log-probabilities: a second backward through the same forward - the saved logits were turned into "
                            "d logits in place by the first one; run the forward again")
         ctx.consumed = True
-        x, norm_w, x2, xn, rstd, logits, lse, labels_in, (idx, inv, cnt), t = _load(ctx)
-        needs = ctx.needs_input_grad[6:]
+        x, norm_w, x2, xn, rstd, logits, lse, labels_in, idx, inv, cnt, t = _load(ctx)
         g32 = g.detach().to(torch.float32).reshape(-1).contiguous()
         if idx is not None:  # the upstream gradient of the j-th labelled row (rows past the count are ignored rows: any value)
             g32, _ = K.logprob_map_rows(idx, g32)
         dlogits = K.logprob_rows_bwd(logits, labels_in, lse, g32, rows=cnt)  # in place: the saved logits become d logits
-        need_dxn = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        if ctx.plain_head or ctx.plain_trainable:
-            # d hidden through the calls of HeadLossFn.backward without its scalar (the same K split: bit-identical products)
-            dx = dnw = None
-            if need_dxn:
-                wt = weight_t(plan.weight)
-                if wt.shape[1] % (64 * _HEAD_SPLITK) == 0:
-                    dxn = K.gemm_nt_splitk(dlogits, wt, _HEAD_SPLITK, m_valid=cnt, inv=inv, m_expect=ctx.m_expect)
-                elif ctx.compact:
-                    dxn = K.scatter_rows(K.gemm_nt(dlogits, wt, m_valid=cnt, m_expect=ctx.m_expect), inv)
-                else:
-                    dxn = K.gemm_nt(dlogits, wt)
-                dx, dnw = _norm_epilogue(dxn, x2, norm_w, rstd, ctx.needs_input_grad[1])
-            gw = K.gemm_tn(dlogits, xn, m_valid=cnt, m_expect=ctx.m_expect) if ctx.plain_trainable else None
-            return (dx.view(x.shape) if dx is not None else None, dnw, None, None, None, None, *([gw] + [None] * (len(needs) - 1) if needs else []))
-        dxn, grads = plan.backward(dlogits, xn, t, needs, need_dx=need_dxn)
-        dx, dnw = _norm_epilogue(dxn, x2, norm_w, rstd, ctx.needs_input_grad[1])
-        return (dx.view(x.shape) if dx is not None else None, dnw, None, None, None, None, *grads)
+        return _head_backward(ctx, 6, (x, norm_w, x2, xn, rstd), dlogits, inv, cnt, t, None)
 
 
 def _check_labels(labels, shape, device, what: str) -> None:

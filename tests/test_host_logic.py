@@ -403,6 +403,56 @@ def test_group_plan_block_diagonal_descriptors():
     assert g._kranges() is None and g._tn_segs() is None
 
 
+def test_head_route_table(monkeypatch):
+    """llx.ops._head_route, the one route decision of HeadLossFn and HeadLogprobFn: which heads run over the compacted labelled rows,
+    which through plan.forward / plan.backward, and when the rows are walked in chunks."""
+    from types import SimpleNamespace
+
+    from llx import ops
+
+    def plan(**kw):
+        return SimpleNamespace(**{"int8": False, "rank": 0, "bias": None, "dora_m": None, **kw})
+
+    def flags(r):
+        return (r.plain_head, r.plain_trainable, r.compact)
+
+    T, V = 300, 1024
+    monkeypatch.setattr(ops, "_HEAD_CHUNK_FORCED", False)
+    monkeypatch.setattr(ops, "_HEAD_CHUNK_ROWS", 8192)
+    for compact in (True, False):
+        monkeypatch.setattr(ops, "_HEAD_COMPACT", compact)
+        # plain head, frozen: only d hidden is wanted, with or without compaction
+        assert flags(ops._head_route(plan(), False, T, V)) == (True, False, compact)
+        # plain head with a weight gradient: over the compacted rows, or - compaction off - the generic plan route
+        assert flags(ops._head_route(plan(), True, T, V)) == ((False, True, True) if compact else (False, False, False))
+        # adapted / quantised / biased heads: the generic route, whatever the globals
+        for other in (plan(rank=16), plan(int8=True), plan(bias=torch.zeros(1)), plan(rank=8, dora_m=torch.zeros(1))):
+            for weight_needs in (False, True):
+                assert flags(ops._head_route(other, weight_needs, T, V)) == (False, False, False)
+    # chunks: only when forced or when [T, V] bf16 logits reach 4 GiB, and only when there are more rows than one chunk holds
+    assert ops._head_route(plan(), False, T, V).chunk == 0
+    assert ops._head_route(plan(), False, 8193, V).chunk == 0
+    Vbig = 128256
+    Tlim = -(-(2**32) // (2 * Vbig))  # the first T with T * V * 2 >= 2^32
+    assert Tlim > 8192 and (Tlim - 1) * Vbig * 2 < 2**32
+    assert ops._head_route(plan(), False, Tlim - 1, Vbig).chunk == 0
+    assert ops._head_route(plan(), False, Tlim, Vbig).chunk == 8192
+    assert ops._head_route(plan(rank=16), True, Tlim, Vbig).chunk == 8192  # the route only reports it: the refusals are the Functions'
+    assert ops._head_route(plan(), False, 2**16, 2**15).chunk == 8192  # T * V * 2 == 2^32 exactly counts as chunked
+    assert ops._head_route(plan(), False, 2**16 - 1, 2**15).chunk == 0
+    monkeypatch.setattr(ops, "_HEAD_CHUNK_ROWS", 2**17)
+    assert ops._head_route(plan(), False, 2**17, 2**15).chunk == 0  # beyond 4 GiB but not more rows than a chunk: one buffer
+    assert ops._head_route(plan(), False, 2**17 + 1, 2**15).chunk == 2**17
+    monkeypatch.setattr(ops, "_HEAD_CHUNK_FORCED", True)
+    monkeypatch.setattr(ops, "_HEAD_CHUNK_ROWS", 256)
+    assert ops._head_route(plan(), False, 256, V).chunk == 0
+    assert ops._head_route(plan(), False, 257, V).chunk == 256
+    r = ops._head_route(plan(), False, T, V)
+    assert r.chunk == 256 and r == ops._head_route(plan(), False, T, V)
+    with pytest.raises(AttributeError):
+        r.chunk = 0  # immutable
+
+
 def test_cached_is_keyed_by_version_and_device_of_every_source():
     """llx.ops._cached / _cached_multi: miss, hit (build not called again), rebuild after an in-place update of a source tensor, and a
     value without a ``.device`` (the tuple modelling/llama.py caches for a dense mask) surviving a second look-up."""
