@@ -351,6 +351,26 @@ int llx_logprob_rows_bwd(const void* logits, int64_t ld, void* dlogits, int64_t 
 int llx_logprob_map_rows(const int32_t* map, const float* src_f, float* dst_f, float fill_f, const int32_t* src_i /* nullable */,
                          int32_t* dst_i /* nullable */, int32_t fill_i, int64_t T, llx_stream_t s);
 
+/* ---- the k likeliest tokens of a row as log-probabilities (csrc/topk.hip), 1 <= k <= 8, bf16 logits [R, V] with row stride ld,
+ *      V % 8 == 0: ids[r, j] (int32) / logp[r, j] (fp32), j < k, descending by value, equal values by ascending index (the tie rule of
+ *      top1 and of the greedy sampler; -0.0 == +0.0; -inf last, by index; a NaN ranks as -inf), so ids[r, 0] is the top1 of
+ *      llx_logprob_rows_fwd.  logp = x - lse[r] with lse given (fp32 [R]); with lse null the kernel forms it as llx_logprob_rows_fwd
+ *      does, logp = (x - max) - log(sum).  label_logp (nullable; with labels and lse): the alternative that is the row's label gets
+ *      label_logp[r].  One read of the row for the selection; no atomics: repeat launches are bit-identical.
+ *      scoring (labels given): row r writes at ids / logp + r * ld_out; rows with label -100 and rows at or past *rows (nullable)
+ *        rounded up to 256 are not read and get ids = -1, logp = 0.
+ *      generation (pos given; finished nullable; the geometry of the sampler's history): row r writes [k] values at
+ *        r * ld_out + (pos[r] - hist_base) * k when that column lies in [0, hist_cap) and finished[r] is not set, else nothing;
+ *        pos and finished are only read - launched before the sampler of the step it sees the column the sampler then fills.
+ *      neither: every row is ranked and written at r * ld_out. -------------------------------------------------------------------- */
+int llx_topk_logprobs_rows(const void* logits, int64_t ld, int64_t R, int64_t V, int k, const float* lse /* nullable */,
+                           const float* label_logp /* nullable */, const int64_t* labels /* nullable */, const int32_t* rows /* nullable */,
+                           const int64_t* pos /* nullable */, int64_t hist_base, const int32_t* finished /* nullable */, int32_t* ids,
+                           float* logp, int64_t ld_out, int64_t hist_cap, llx_stream_t s);
+/* the [T, k] results of the compacted rows back to their positions: dst[i, :] = map[i] >= 0 ? src[map[i], :] : (-1, 0.0) */
+int llx_topk_map_rows(const int32_t* map, const int32_t* src_ids, const float* src_logp, int32_t* dst_ids, float* dst_logp, int64_t T, int k,
+                      llx_stream_t s);
+
 /* ---- LoRA skinny contractions (modelling/lora.py:43 and its autograd): T = X.W^T -> [M,64] zero padded;
  *      G = s * U^T.Y with fp32 split partials (deterministic). --------------------------------------------------- */
 int llx_skinny_nt(const void* X, int64_t ldx, const void* W, int64_t ldw, void* out, int64_t M, int64_t K, int64_t R,

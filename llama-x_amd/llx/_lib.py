@@ -99,6 +99,8 @@ SIGNATURES: dict[str, tuple] = {
     "llx_logprob_rows_fwd": (c_int, [_P, _L, _P, _P, _P, _P, _L, _L, _P, _P]),
     "llx_logprob_rows_bwd": (c_int, [_P, _L, _P, _L, _P, _P, _P, _L, _L, _P, _P]),
     "llx_logprob_map_rows": (c_int, [_P, _P, _P, _F, _P, _P, _I, _L, _P]),
+    "llx_topk_logprobs_rows": (c_int, [_P, _L, _L, _L, _I, _P, _P, _P, _P, _P, _L, _P, _P, _P, _L, _L, _P]),
+    "llx_topk_map_rows": (c_int, [_P, _P, _P, _P, _P, _L, _I, _P]),
     "llx_head_compact_index": (c_int, [_P, _P, _P, _P, _P, _L, _P]),
     "llx_gather_rows": (c_int, [_P, _L, _P, _P, _P, _L, _L, _L, _P]),
     "llx_scatter_rows": (c_int, [_P, _L, _P, _P, _P, _L, _L, _L, _P]),

@@ -169,6 +169,31 @@ def history_rows(history: Tensor, shifts, counts: Tensor, T: int, pad: int) -> T
     return torch.where(j < counts.view(B, 1), got, torch.full_like(got, pad))
 
 
+def history_rows_k(history: Tensor, shifts, counts: Tensor, T: int, pad) -> Tensor:
+    """history_rows for a [B, cols, k] buffer (the top-k alternatives): [B, T, k], the shift and the cut along the columns."""
+    B, _, k = history.shape
+    j = torch.arange(T, device=history.device)
+    sh = torch.as_tensor(shifts, device=history.device, dtype=torch.int64).view(B, 1)
+    got = history.gather(1, (sh + j).clamp_(max=history.shape[1] - 1)[:, :, None].expand(B, T, k))
+    return torch.where((j < counts.view(B, 1))[:, :, None], got, torch.full_like(got, pad))
+
+
+class _TopLogprobs:
+    """The buffers of generate(top_logprobs=k): ids int32 / logp fp32 [B, cols, k] in the geometry of the sampler's history, prefilled
+    with -1 / 0.0, and the one extra launch of a step - BEFORE the step's sampler launch, so that it reads the position counter and
+    the finished flags the sampler is about to use and writes the column the sampler then fills."""
+
+    def __init__(self, k: int, B: int, cols: int, dev):
+        self.k = k
+        self.ids = torch.full((B, cols, k), -1, device=dev, dtype=torch.int32)
+        self.logp = torch.zeros(B, cols, k, device=dev, dtype=torch.float32)
+
+    def step(self, logits: Tensor, kw: dict) -> None:
+        if logits.dtype is not torch.bfloat16:
+            raise LlxError(f"generate: top_logprobs ranks bf16 logits (the model returned {logits.dtype})")
+        K.topk_logprobs_rows(logits, self.k, pos=kw["pos"], hist_base=kw["hist_base"], finished=kw["finished"], ids=self.ids, logp=self.logp)
+
+
 def seed_counts(prompt: Tensor, lens: Optional[Sequence[int]], vocab_size: int, penalize_prompt: bool) -> Tensor:
     """The sampler's count table (int32 [B, V], rule 0 of llx/sampling.py) before the first draw: zero, or with penalize_prompt the number
     of times each token occurs in row b's own prompt - its first lens[b] columns (None: all); pads are not counted.  No host read."""
@@ -228,9 +253,10 @@ def prefill_audio(model, audio: Tensor, prompt: Tensor, prompt_lens: Optional[Se
 
 
 def _generate_batch(model, prompt: Tensor, n: int, lens: list, sampling: dict, eos_id, prefill_chunk, check_every: int, call,
-                    audio: Optional[Tensor] = None, table: Optional[Tensor] = None, return_logprobs: bool = False):
+                    audio: Optional[Tensor] = None, table: Optional[Tensor] = None, return_logprobs: bool = False, top_logprobs: int = 0):
     """The loop of a batch.  sampling: the sampler's keyword arguments, penalties included; table: its count table (None: no penalties),
-    seeded by the caller from each row's own text prompt; return_logprobs: also the fp32 log-probabilities, laid out like the tokens."""
+    seeded by the caller from each row's own text prompt; return_logprobs: also the fp32 log-probabilities, laid out like the tokens;
+    top_logprobs = k > 0: also the k likeliest tokens and their log-probabilities [B, T, k]."""
     dev, B = prompt.device, prompt.shape[0]
     if audio is not None:
         logits = prefill_audio(model, audio, prompt, lens)
@@ -249,6 +275,9 @@ def _generate_batch(model, prompt: Tensor, n: int, lens: list, sampling: dict, e
         kw["counts"] = table
     if return_logprobs:
         kw["logprob_history"] = torch.zeros(B, cols, device=dev, dtype=torch.float32)
+    top = _TopLogprobs(top_logprobs, B, cols, dev) if top_logprobs else None
+    if top is not None:
+        top.step(logits[:, 0], kw)
     K.sample(logits[:, 0], **kw)
     T = n
     for k in range(1, n + 1):
@@ -262,9 +291,15 @@ def _generate_batch(model, prompt: Tensor, n: int, lens: list, sampling: dict, e
         if k == n:
             break
         # a finished row feeds eos_id at its frozen position: it re-writes its own cache row there, nothing else
-        K.sample(call(tok, pos[:, None])[:, 0], **kw)
+        logits = call(tok, pos[:, None])[:, 0]
+        if top is not None:
+            top.step(logits, kw)
+        K.sample(logits, **kw)
     counts = pos - start if finished is not None else torch.full((B,), n, device=dev, dtype=torch.int64)
     tokens = history_rows(history, shifts, counts, T, eos_id if eos_id is not None else 0)
+    if top is not None:
+        return (tokens, history_rows(kw["logprob_history"], shifts, counts, T, 0.0), history_rows_k(top.ids, shifts, counts, T, -1),
+                history_rows_k(top.logp, shifts, counts, T, 0.0))
     return (tokens, history_rows(kw["logprob_history"], shifts, counts, T, 0.0)) if return_logprobs else tokens
 
 
@@ -384,7 +419,7 @@ def generate(model, prompt: Tensor, max_new_tokens: int, *, temperature: float =
              eos_id: Optional[int] = None, prefill_chunk: Optional[int] = None, check_every: int = 16, prompt_lens=None,
              draft_tokens: int = 0, draft_ngram: int = 3, stats: Optional[dict] = None, num_beams: int = 1, length_penalty: float = 1.0,
              audio: Optional[Tensor] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
-             penalize_prompt: bool = True, return_logprobs: bool = False):
+             penalize_prompt: bool = True, return_logprobs: bool = False, top_logprobs: int = 0):
     """Continue `prompt` (int64 [B, P], B = the batch the KV cache was built for) by up to `max_new_tokens` tokens -> int64 [B, n_new] on
     the prompt's device.  `prompt_lens` (B lengths in [1, P], a sequence or an int64 tensor, read once on the host before the first
     launch): the rows of `prompt` are right-padded prompts of these lengths; default: every row is P long.  For a batch the result is as
@@ -451,9 +486,20 @@ def generate(model, prompt: Tensor, max_new_tokens: int, *, temperature: float =
     Llama.token_logprobs - computed by the sampler launch itself; positions after a row's `eos_id` hold 0.0.  That is the model's
     probability of the token, comparable across sampling settings; it is the probability the token was drawn with only when
     temperature == 1 and no filter and no penalty is on.  Penalties and `return_logprobs` are refused with `num_beams` != 1 (beams rank
-    by their own log-probabilities) and with `draft_tokens` != 0 (the rows of a draft step would each need the counts of another prefix)."""
+    by their own log-probabilities) and with `draft_tokens` != 0 (the rows of a draft step would each need the counts of another prefix).
+
+    `top_logprobs` = k in 1..8 (with `return_logprobs=True`; refused where that is) returns (tokens, logprobs, top_ids, top_logp): int32 /
+    fp32 [B, n_new, k], the k likeliest tokens at every returned position and their log-probabilities under the same RAW logits,
+    descending, equal logits by ascending index (csrc/topk.hip) - whatever the sampling settings, so a greedy token is top_ids[..., 0]
+    and a sampled or penalised one need not be among them.  One extra launch per step, in front of the sampler's, nothing read by the
+    host; positions after a row's `eos_id` hold -1 / 0.0.  The row's lse is formed in another order than the sampler's, so the entry of
+    the returned token agrees with `logprobs` to about 1e-6, not bit for bit."""
     check_params(temperature, top_k, top_p, seed)
     check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
+    if isinstance(top_logprobs, bool) or not isinstance(top_logprobs, int) or not 0 <= top_logprobs <= K.TOPK_MAX:
+        raise LlxError(f"top_logprobs={top_logprobs!r} must be an integer in 0..{K.TOPK_MAX}")
+    if top_logprobs and not return_logprobs:
+        raise LlxError(f"top_logprobs={top_logprobs!r} needs return_logprobs=True: the alternatives come with the tokens' log-probabilities")
     penalised = penalties_on(repetition_penalty, presence_penalty, frequency_penalty)
     for name, value, off in (("num_beams", num_beams, 1), ("draft_tokens", draft_tokens, 0)):
         if value != off and penalised:
@@ -478,7 +524,7 @@ def generate(model, prompt: Tensor, max_new_tokens: int, *, temperature: float =
         stats["counts"] = seen
     if prompt.shape[0] > 1 or (lens is not None and lens != [P]):
         return _generate_batch(model, prompt, n, lens if lens is not None else [P] * prompt.shape[0], sampling, eos_id, prefill_chunk,
-                               check_every, call, audio, seen, return_logprobs)
+                               check_every, call, audio, seen, return_logprobs, top_logprobs)
     if audio is not None:
         logits = prefill_audio(model, audio, prompt)
         P += model.audio_positions(audio.shape[1])  # from here on P is the length of the sequence: clip and prompt
@@ -509,6 +555,9 @@ def generate(model, prompt: Tensor, max_new_tokens: int, *, temperature: float =
         kw["counts"] = seen
     if return_logprobs:
         kw["logprob_history"] = torch.zeros(1, n, device=dev, dtype=torch.float32)
+    top = _TopLogprobs(top_logprobs, 1, n, dev) if top_logprobs else None
+    if top is not None:
+        top.step(logits[0, -1:], kw)
     K.sample(logits[0, -1:], **kw)
     count = n
     for k in range(1, n + 1):
@@ -520,7 +569,12 @@ def generate(model, prompt: Tensor, max_new_tokens: int, *, temperature: float =
                 break
         if k == n:
             break
-        K.sample(call(tok, pos)[0], **kw)
+        logits = call(tok, pos)[0]
+        if top is not None:
+            top.step(logits, kw)
+        K.sample(logits, **kw)
     if stats is not None:
         stats.update(steps=count, tokens=count, accepted=0, draft_tokens=0, launched=k - 1)
+    if top is not None:
+        return history[:, :count], kw["logprob_history"][:, :count], top.ids[:, :count], top.logp[:, :count]
     return (history[:, :count], kw["logprob_history"][:, :count]) if return_logprobs else history[:, :count]

@@ -1361,6 +1361,74 @@ def logprob_map_rows(index: Tensor, src: Tensor, fill: float = 0.0, src_i: Optio
     return dst, dst_i
 
 
+TOPK_MAX = 8  # csrc/topk.hip
+
+
+def topk_logprobs_rows(logits: Tensor, k: int, *, lse: Optional[Tensor] = None, label_logp: Optional[Tensor] = None,
+                       labels: Optional[Tensor] = None, rows: Optional[Tensor] = None, pos: Optional[Tensor] = None, hist_base: int = 0,
+                       finished: Optional[Tensor] = None, ids: Optional[Tensor] = None, logp: Optional[Tensor] = None):
+    """The k (1..TOPK_MAX) largest of every row of bf16 `logits` [R, V] as (ids int32, logp fp32), descending by value, equal values by
+    ascending index (the order of csrc/topk.hip: -inf last, a NaN as -inf), ids[:, 0] the top1 of logprob_rows_fwd.  logp = x - lse[r]
+    with lse (fp32 [R]), else the kernel forms the row's lse itself; label_logp (fp32 [R], with labels and lse): the alternative that is
+    the row's label gets that value.  The logits are only read.
+    scoring (labels int64 [R]; rows as logprob_rows_fwd): -> [R, k] each, -1 / 0.0 on rows with label -100 and past the row limit.
+    generation (pos int64 [R], hist_base, finished int32 [R] or None; ids / logp given, [R, cap, k] contiguous): row r writes
+    [r, pos[r] - hist_base, :] when that column exists and finished[r] is not set; pos and finished are only read.
+    neither: -> [R, k] of every row."""
+    _chk_bf16(logits)
+    L.require_cuda(lse, label_logp, labels, rows, pos, finished, ids, logp)
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= TOPK_MAX:
+        raise L.LlxError(f"topk_logprobs_rows: k must be an int in 1..{TOPK_MAX} (got {k!r})")
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise L.LlxError(f"topk_logprobs_rows: logits must be bf16 [R, V] with a dense last dim (got {tuple(logits.shape)})")
+    R, V = logits.shape
+    dev = logits.device
+    for name, t in (("lse", lse), ("label_logp", label_logp)):
+        if t is not None and (t.dtype is not torch.float32 or t.shape != (R,) or not t.is_contiguous() or t.device != dev):
+            raise L.LlxError(f"topk_logprobs_rows: {name} must be a contiguous fp32 [{R}] on the logits' device")
+    for name, t in (("labels", labels), ("pos", pos)):
+        if t is not None and (t.dtype is not torch.int64 or t.shape != (R,) or not t.is_contiguous() or t.device != dev):
+            raise L.LlxError(f"topk_logprobs_rows: {name} must be a contiguous int64 [{R}] on the logits' device")
+    if finished is not None and (finished.dtype is not torch.int32 or finished.shape != (R,) or not finished.is_contiguous() or finished.device != dev):
+        raise L.LlxError(f"topk_logprobs_rows: finished must be a contiguous int32 [{R}] on the logits' device")
+    assert rows is None or (rows.dtype is torch.int32 and rows.numel() == 1 and rows.device == dev)
+    cap = 0
+    if pos is not None:
+        if ids is None or logp is None:
+            raise L.LlxError("topk_logprobs_rows: generation writes into the caller's ids / logp [R, cap, k] buffers")
+        if ids.dim() != 3 or ids.shape[0] != R or ids.shape[2] != k or ids.shape[1] < 1:
+            raise L.LlxError(f"topk_logprobs_rows: ids / logp must be [{R}, cap, {k}] (got {tuple(ids.shape)})")
+        cap = ids.shape[1]
+    else:
+        if ids is None:
+            ids = torch.empty(R, k, device=dev, dtype=torch.int32)
+        if logp is None:
+            logp = torch.empty(R, k, device=dev, dtype=torch.float32)
+        if ids.shape != (R, k):
+            raise L.LlxError(f"topk_logprobs_rows: ids / logp must be [{R}, {k}] (got {tuple(ids.shape)})")
+    if ids.dtype is not torch.int32 or logp.dtype is not torch.float32 or logp.shape != ids.shape or not ids.is_contiguous() \
+            or not logp.is_contiguous() or ids.device != dev or logp.device != dev:
+        raise L.LlxError("topk_logprobs_rows: ids must be int32 and logp fp32, of one shape, contiguous, on the logits' device")
+    L.check(_lib().llx_topk_logprobs_rows(L.ptr(logits), logits.stride(0) if R > 1 else V, R, V, k, L.ptr(lse), L.ptr(label_logp), L.ptr(labels),
+                                          L.ptr(rows), L.ptr(pos), int(hist_base), L.ptr(finished), L.ptr(ids), L.ptr(logp),
+                                          cap * k if pos is not None else k, cap, L.stream()), "llx_topk_logprobs_rows")
+    return ids, logp
+
+
+def topk_map_rows(index: Tensor, src_ids: Tensor, src_logp: Tensor):
+    """dst[i, :] = src[index[i], :] where index[i] >= 0, (-1, 0.0) elsewhere, for the int32 / fp32 [T, k] pair of topk_logprobs_rows over
+    compacted head rows (index = inv of head_compact_index) -> (ids, logp) at the positions."""
+    L.require_cuda(index, src_ids, src_logp)
+    T = index.numel()
+    assert index.dtype is torch.int32 and index.is_contiguous()
+    assert src_ids.dtype is torch.int32 and src_ids.dim() == 2 and src_ids.shape[0] == T and src_ids.is_contiguous()
+    assert src_logp.dtype is torch.float32 and src_logp.shape == src_ids.shape and src_logp.is_contiguous()
+    dst_ids, dst_logp = torch.empty_like(src_ids), torch.empty_like(src_logp)
+    L.check(_lib().llx_topk_map_rows(L.ptr(index), L.ptr(src_ids), L.ptr(src_logp), L.ptr(dst_ids), L.ptr(dst_logp), T, src_ids.shape[1], L.stream()),
+            "llx_topk_map_rows")
+    return dst_ids, dst_logp
+
+
 # ------------------------------------------------------------------------------------------------- skinny (LoRA)
 def skinny_nt(x: Tensor, w: Tensor, kranges: Optional[Sequence[int]] = None, colscale: Optional[Tensor] = None):
     """[M,K] @ [R,K]^T -> [M,64] bf16, zero beyond column R.

@@ -997,17 +997,18 @@ class HeadLogprobFn(Function):
     with want_top1.  The upstream gradient is per row, so - unlike the loss, whose one scalar can be applied after the fact - d logits
     is not written in the forward: the forward keeps the logits in the buffer where the loss keeps d logits, and the backward turns
     them into d logits in place once g is known (one bf16 rounding, the same traffic over forward + backward).  Without gradients
-    nothing is saved, and a row set beyond one logits buffer is walked in chunks."""
+    nothing is saved, and a row set beyond one logits buffer is walked in chunks.  top_k > 0: two more non-differentiable outputs,
+    int32 / fp32 [T, top_k], from one more launch per logits buffer (csrc/topk.hip) right after the forward kernel's."""
 
     @staticmethod
-    def forward(ctx, x: Tensor, norm_w: Tensor, labels: Tensor, eps: float, plan: LinearPlan, want_top1: bool, *tensors):
+    def forward(ctx, x: Tensor, norm_w: Tensor, labels: Tensor, eps: float, plan: LinearPlan, want_top1: bool, top_k: int, *tensors):
         K.L.require_cuda(x, labels)
         x2 = K._rows2d(x.contiguous())
         xn, rstd = K.rmsnorm_fwd(x2, norm_w.detach(), eps)
         need_grad = any(ctx.needs_input_grad) and not getattr(plan, "no_grad", False)  # (needs_input_grad does not see the caller's no_grad)
         T, V = x2.shape[0], plan.N
         ctx.plan = plan
-        route = ctx.route = _head_route(plan, any(ctx.needs_input_grad[6:]), T, V)
+        route = ctx.route = _head_route(plan, any(ctx.needs_input_grad[7:]), T, V)
         if need_grad and V % 64 != 0:  # (as the loss path: its d-hidden GEMM contracts over the vocabulary; said here, not in the middle of backward)
             raise LlxError(f"token log-probabilities with gradients need a vocabulary that is a multiple of 64 (got {V}): the d-hidden GEMM "
                            "contracts over it in 64-column steps - score under torch.no_grad() or pad the vocabulary")
@@ -1017,21 +1018,29 @@ class HeadLogprobFn(Function):
         rows_in, labels_in, idx, inv, cnt = _head_rows(xn, labels, route)
         parts = []
         for r0, r1, logits, cnt_c, t, m_expect in _head_logits(plan, rows_in, route, cnt):
-            parts.append(K.logprob_rows_fwd(logits, labels_in[r0:r1], rows=cnt_c, want_top1=want_top1))
+            part = K.logprob_rows_fwd(logits, labels_in[r0:r1], rows=cnt_c, want_top1=want_top1)
+            if top_k:  # here, while the buffer still holds the logits: the alternatives of the chunk's rows, the label's entry = its logp
+                part += K.topk_logprobs_rows(logits, top_k, lse=part[1], label_logp=part[0], labels=labels_in[r0:r1], rows=cnt_c)
+            parts.append(part)
         ctx.m_expect = m_expect
-        logp, lse, top1 = parts[0]
+        logp, lse, top1 = parts[0][:3]
+        top = parts[0][3:]
         if route.chunk:
             logp = torch.cat([p[0] for p in parts])
             top1 = torch.cat([p[2] for p in parts]) if want_top1 else None
+            top = (torch.cat([p[3] for p in parts]), torch.cat([p[4] for p in parts])) if top_k else ()
         if need_grad:
             keep_rows = rows_in if (route.plain_trainable or not (route.plain_head or route.plain_trainable)) else None
             _save(ctx, x, norm_w, x2, keep_rows, rstd, logits, lse, labels_in, idx, inv, cnt, t)
         if inv is not None:  # compacted rows back to their positions: [T] vectors, zeros / -1 at the ignored positions
             logp, top1 = K.logprob_map_rows(inv, logp, 0.0, top1, -1)
-        if top1 is None:
+            if top_k:
+                top = K.topk_map_rows(inv, *top)
+        extra = (() if top1 is None else (top1,)) + tuple(top)
+        if not extra:
             return logp
-        ctx.mark_non_differentiable(top1)
-        return logp, top1
+        ctx.mark_non_differentiable(*extra)
+        return (logp, *extra)
 
     @staticmethod
     def backward(ctx, g: Tensor, *_):
@@ -1044,7 +1053,7 @@ class HeadLogprobFn(Function):
         if idx is not None:  # the upstream gradient of the j-th labelled row (rows past the count are ignored rows: any value)
             g32, _ = K.logprob_map_rows(idx, g32)
         dlogits = K.logprob_rows_bwd(logits, labels_in, lse, g32, rows=cnt)  # in place: the saved logits become d logits
-        return _head_backward(ctx, 6, (x, norm_w, x2, xn, rstd), dlogits, inv, cnt, t, None)
+        return _head_backward(ctx, 7, (x, norm_w, x2, xn, rstd), dlogits, inv, cnt, t, None)
 
 
 def _check_labels(labels, shape, device, what: str) -> None:
@@ -1056,13 +1065,26 @@ def _check_labels(labels, shape, device, what: str) -> None:
         raise LlxError(f"{what}: labels live on {labels.device}, the hidden states on {device}: both must be on the same GPU")
 
 
-def head_logprobs(x: Tensor, norm: nn.Module, output: nn.Linear, labels: Tensor, return_top1: bool = False):
+def _check_top_k(k, what: str) -> None:
+    if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= K.TOPK_MAX:
+        raise LlxError(f"{what} must be an int in 0..{K.TOPK_MAX} (got {k!r})")
+
+
+def head_logprobs(x: Tensor, norm: nn.Module, output: nn.Linear, labels: Tensor, return_top1: bool = False, top_k: int = 0):
     """fp32 log-probabilities [*labels.shape] of `labels` under output(norm(x)), 0 at labels == -100; with return_top1 also the int32
-    argmax of every labelled position (-1 at the others)."""
+    argmax of every labelled position (-1 at the others); with top_k = k in 1..K.TOPK_MAX also, last, top_ids (int32) and top_logp
+    (fp32) [*labels.shape, k]: the k likeliest tokens of every labelled position and their log-probabilities in the order of
+    csrc/topk.hip (descending, equal logits by ascending index), -1 / 0.0 at the others, detached."""
     _check_labels(labels, x.shape[:-1], x.device, "token_logprobs")
+    _check_top_k(top_k, "token_logprobs: top_k")
     plan = LinearPlan(output)
     plan.no_grad = not torch.is_grad_enabled()  # (inside Function.forward grad mode is always off: noted here)
-    out = HeadLogprobFn.apply(x, norm.weight, labels, norm.eps, plan, bool(return_top1), *plan.tensors())
+    out = HeadLogprobFn.apply(x, norm.weight, labels, norm.eps, plan, bool(return_top1), top_k, *plan.tensors())
+    if not return_top1 and not top_k:
+        return out.view(labels.shape)
+    res = [out[0].view(labels.shape)]
     if return_top1:
-        return out[0].view(labels.shape), out[1].view(labels.shape)
-    return out.view(labels.shape)
+        res.append(out[1].view(labels.shape))
+    if top_k:
+        res += [out[-2].view(*labels.shape, top_k), out[-1].view(*labels.shape, top_k)]
+    return tuple(res)

@@ -65,14 +65,16 @@ class LlamaAudio(Llama):
             x = x[:, n_audio:]  # remove audio embs
         return self._head(x, labels)
 
-    def token_logprobs(self, audio: Tensor | None, tokens: Tensor, labels: Tensor, *, block_mask=None, return_top1: bool = False):
+    def token_logprobs(self, audio: Tensor | None, tokens: Tensor, labels: Tensor, *, block_mask=None, return_top1: bool = False,
+                       top_k: int = 0):
         """Llama.token_logprobs over the text positions ([B, St]): as in forward, the audio prefix is dropped before the head."""
         ops._check_labels(labels, tokens.shape, tokens.device, "token_logprobs")
+        ops._check_top_k(top_k, "token_logprobs: top_k")
         x, n_audio = self._embed(tokens, audio)
         x = self._run_layers(x, self.rope[: x.shape[1]], mask=None, input_pos=None, block_mask=block_mask)
         if n_audio:
             x = x[:, n_audio:]  # remove audio embs
-        return ops.head_logprobs(x, self.norm, self.output, labels, return_top1)
+        return ops.head_logprobs(x, self.norm, self.output, labels, return_top1, top_k)
 
     def generate(self, audio: Tensor | None, prompt: Tensor, max_new_tokens: int, **kwargs) -> Tensor:
         """llx.generate.generate(self, prompt, max_new_tokens, audio=audio, ...): the clip(s) (fp32 [B, samples]) and the prompt are

@@ -378,13 +378,17 @@ class Llama(nn.Module):
     def forward(self, x: Tensor, *, input_pos: Tensor | None = None, block_mask=None, labels: Tensor | None = None) -> Tensor:
         return self._head(self._hidden(x, input_pos, block_mask), labels)
 
-    def token_logprobs(self, tokens: Tensor, labels: Tensor, *, block_mask=None, return_top1: bool = False):
+    def token_logprobs(self, tokens: Tensor, labels: Tensor, *, block_mask=None, return_top1: bool = False, top_k: int = 0):
         """fp32 [B, S] log-probabilities of ``labels`` under the model, ``-F.cross_entropy(logits.float(), labels, reduction="none",
         ignore_index=-100)`` - the per-token terms of the mean that ``forward(labels=...)`` returns - without materialising the logits
         in fp32, 0.0 where labels == -100, differentiable.  return_top1: also the int32 [B, S] argmax of every labelled position
-        (-1 at the others): token accuracy from the same pass.  Train and eval mode; not the KV-cache path (no input_pos)."""
+        (-1 at the others): token accuracy from the same pass.  top_k = k in 1..8: also, last, ``top_ids`` (int32) and ``top_logp``
+        (fp32) [B, S, k], the k likeliest tokens of every labelled position and their log-probabilities, descending, equal logits by
+        ascending index (``top_ids[..., 0]`` is top1), -1 / 0.0 at the others, detached; an alternative that is the label carries
+        the label's logp bit for bit.  Train and eval mode; not the KV-cache path (no input_pos)."""
         ops._check_labels(labels, tokens.shape, tokens.device, "token_logprobs")
-        return ops.head_logprobs(self._hidden(tokens, None, block_mask), self.norm, self.output, labels, return_top1)
+        ops._check_top_k(top_k, "token_logprobs: top_k")
+        return ops.head_logprobs(self._hidden(tokens, None, block_mask), self.norm, self.output, labels, return_top1, top_k)
 
     def generate(self, prompt: Tensor, max_new_tokens: int, **kwargs) -> Tensor:
         """llx.generate.generate(self, ...): prefill + one forward and one on-device sampler launch per token (the reference has no

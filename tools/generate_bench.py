@@ -5,7 +5,8 @@ Setup: Llama-3.1-8B dimensions, random weights, prompt 512, 128 new tokens, temp
 alternate, `--repeats` times each after one untimed pass of both; the median is reported.  Both are timed end to end (prefill + the new
 tokens, wall clock between device synchronisations); the prefill alone is timed as well, and ms/token is (total - prefill) / new tokens.
 The sampler launch alone (device events, `--sampler-steps` launches back to back on one row of real logits) is timed against the
-torch chain it replaces on the same logits (the chain without its .item()).
+torch chain it replaces on the same logits (the chain without its .item()).  generate(return_logprobs=True) with and without
+top_logprobs=8 alternate in the same repeats: what the one extra launch per token (llx_topk_logprobs_rows) costs in ms/token.
 
     python tools/generate_bench.py [--prompt 512] [--new 128] [--repeats 3] [--layers 32] [--out profiles/generate_bench.json]
 """
@@ -115,14 +116,19 @@ def main():
     def run_generate():
         return generate(model, prompt, n, temperature=TEMPERATURE, top_k=TOP_K, top_p=TOP_P, seed=SEED)
 
+    def run_logprobs(k):
+        return generate(model, prompt, n, temperature=TEMPERATURE, top_k=TOP_K, top_p=TOP_P, seed=SEED, return_logprobs=True, top_logprobs=k)
+
     def run_prefill():
         with torch.no_grad():
             return model(prompt, input_pos=torch.arange(P, device=dev))
 
-    run_generate(), host_loop(model, prompt, n), run_prefill()  # untimed pass of everything
-    ms = {"generate": [], "host_loop": [], "prefill": []}
+    run_generate(), host_loop(model, prompt, n), run_prefill(), run_logprobs(0), run_logprobs(8)  # untimed pass of everything
+    ms = {"generate": [], "host_loop": [], "prefill": [], "generate_logprobs": [], "generate_top_logprobs_8": []}
     for _ in range(args.repeats):
         ms["generate"].append(timed(run_generate)[0])
+        ms["generate_logprobs"].append(timed(lambda: run_logprobs(0))[0])
+        ms["generate_top_logprobs_8"].append(timed(lambda: run_logprobs(8))[0])
         ms["host_loop"].append(timed(lambda: host_loop(model, prompt, n))[0])
         ms["prefill"].append(timed(run_prefill)[0])
 
@@ -153,9 +159,10 @@ def main():
     res = {"workload": f"Llama-3.1-8B dimensions ({args.layers} layers), random weights, batch 1, prompt {P}, {n} new tokens, "
                        f"temperature {TEMPERATURE}, top_k {TOP_K}, top_p {TOP_P}; medians of {args.repeats} alternating repeats",
            "prefill_ms": round(pre, 3)}
-    for name in ("generate", "host_loop"):
+    for name in ("generate", "host_loop", "generate_logprobs", "generate_top_logprobs_8"):
         tot = median(ms[name])
         res[name] = {"total_ms": round(tot, 3), "ms_per_token": round((tot - pre) / n, 4), "all_total_ms": [round(x, 3) for x in ms[name]]}
+    res["top_logprobs_8_extra_ms_per_token"] = round(res["generate_top_logprobs_8"]["ms_per_token"] - res["generate_logprobs"]["ms_per_token"], 4)
     res["sampler_kernel_us"] = round(median(samp) * 1e3, 2)
     res["torch_chain_us"] = round(median(chain) * 1e3, 2)
     res["generate_not_slower_than_host_loop"] = res["generate"]["total_ms"] <= res["host_loop"]["total_ms"]

@@ -6,6 +6,10 @@ frozen bf16 head), every row labelled and again with 25 % of the rows labelled (
   (c) torch     head logits through the package (norm, GEMM over all rows), then torch.log_softmax(logits.float(), -1).gather - the
                 route a user had before; with its peak memory (torch.cuda.max_memory_allocated over the arm, above the resident set)
   (d) logp_fb / loss_fb   (a) and (b) with their backward for the frozen plain head (d hidden through the norm)
+  (e) logp_top8   (a) with top_k=8: one more launch per logits buffer (llx_topk_logprobs_rows) and the [T, 8] map back
+      torch_top8  (c)'s logits, then torch.log_softmax(logits.float(), -1).topk(8): the only route to the alternatives before
+      k_rows_fwd / k_topk8   the two row kernels alone on one prebuilt [T, V] logits buffer, every row labelled: what the extra pass of
+                  (e) costs against a second llx_logprob_rows_fwd launch over the same rows
 
 The arms alternate in one process; a window is `--iters` back-to-back calls between two HIP events; per arm the median, min and max of
 `--windows` windows.  The condition recorded: (a) not slower than (b), and (d) logp_fb not slower than loss_fb, by more than the larger
@@ -35,6 +39,7 @@ def main():
     a = ap.parse_args()
     import torch
 
+    from llx import kernels as K
     from llx import ops
     from modelling.llama import Linear, RMSNorm
 
@@ -53,6 +58,11 @@ def main():
     def plan_args():
         plan = ops.LinearPlan(out)
         return norm.eps, plan, *plan.tensors()
+
+    with torch.no_grad():
+        kbuf = out(norm(x))  # the kernels' own arms: one [T, V] bf16 logits buffer, built once
+    klb = torch.randint(0, V, (T,), device=dev, generator=g)
+    klse = K.logprob_rows_fwd(kbuf, klb)[1]
 
     def arms(lb):
         def logp():
@@ -76,7 +86,22 @@ def main():
             xg = x.detach().requires_grad_()
             ops.HeadLossFn.apply(xg, norm.weight, lb, *plan_args()).backward()
 
-        return {"logp": logp, "loss": loss, "torch": torch_route, "logp_fb": logp_fb, "loss_fb": loss_fb}
+        def logp_top8():
+            with torch.no_grad():
+                return ops.head_logprobs(x, norm, out, lb, top_k=8)
+
+        def torch_top8():
+            with torch.no_grad():
+                return torch.log_softmax(out(norm(x)).float(), -1).topk(8)
+
+        def k_rows_fwd():
+            return K.logprob_rows_fwd(kbuf, klb)
+
+        def k_topk8():
+            return K.topk_logprobs_rows(kbuf, 8, lse=klse, labels=klb)
+
+        return {"logp": logp, "loss": loss, "torch": torch_route, "logp_fb": logp_fb, "loss_fb": loss_fb, "logp_top8": logp_top8,
+                "torch_top8": torch_top8, "k_rows_fwd": k_rows_fwd, "k_topk8": k_topk8}
 
     rec = {"shape": {"T": T, "D": D, "V": V, "head": "plain bf16, frozen"}, "windows": a.windows, "iters_per_window": a.iters, "unit": "ms", "cases": {}}
     for name, frac in (("all_rows_labelled", 1.0), ("quarter_labelled", 0.25)):
@@ -105,6 +130,9 @@ def main():
             spread = max(case[new]["max"] - case[new]["min"], case[old]["max"] - case[old]["min"])
             case[f"{new}_minus_{old}"] = {"ms": round(case[new]["median"] - case[old]["median"], 3), "allowed_ms": round(spread, 3),
                                           "holds": case[new]["median"] - case[old]["median"] <= spread}
+        # recorded, no bar: the top-k arm against the plain scoring call, and its kernel against a second row-kernel launch
+        case["logp_top8_minus_logp"] = {"ms": round(case["logp_top8"]["median"] - case["logp"]["median"], 3)}
+        case["k_topk8_minus_k_rows_fwd"] = {"ms": round(case["k_topk8"]["median"] - case["k_rows_fwd"]["median"], 3)}
         rec["cases"][name] = case
     print(json.dumps(rec))
     if a.out:
