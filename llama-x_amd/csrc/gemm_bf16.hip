@@ -46,7 +46,10 @@ struct GemmArgs {
 typedef __attribute__((address_space(3))) void lds_void;
 typedef const __attribute__((address_space(1))) void gbl_void;
 
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
+// x Phi(x) with Phi = 0.5 erfc(-x / sqrt 2): the same function as 0.5 x (1 + erf(x / sqrt 2)), but 1 + erff cancels for negative x (at
+// x = -5 the sum is 9.6 ulp of 1, from -6 on it is 0 and the output -0 where the value is -6e-9 ... -8e-38); erfcf keeps its relative
+// accuracy down the tail, so the output stays within one bf16 neighbour of the float64 value everywhere
+__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * erfcf(x * -0.70710678118654752440f); }
 
 // I8 = true: A/B are int8 (K counted in int8 elements, 128 per tile row = the same 128-byte rows), MFMA is
 // v_mfma_i32_16x16x64_i8 with int32 accumulators, epilogue EPI_ROWCOLSCALE (torchao::int8_mm_dequant).
