@@ -1040,6 +1040,12 @@ _DECODE_WS: dict = {}
 _DECODE_WGS = 512  # workgroups the decode attention aims for (nsplit * B * KVH)
 
 
+def _decode_nsplit(B: int, KVH: int, Skv: int) -> int:
+    """Key ranges per (batch, kv head) of attn_decode: workgroups = nsplit * B * KVH, two or more per CU keep more rows in flight; at
+    least 32 keys per range, at most 128 ranges."""
+    return max(1, min(-(-Skv // 32), -(-_DECODE_WGS // (B * KVH)), 128))
+
+
 def attn_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, mask: Tensor, extent: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
     """SDPA over the cache for a few query tokens: q [B, H, M, 128] (any strides, last dim dense), caches [B, KVH, Skv, 128], bool mask
     broadcastable to [B, H, M, Skv] -> o [B, H, M, 128] stored as [B, M, H*128] (the layout wo reads).  M * H / KVH <= 16."""
@@ -1050,7 +1056,7 @@ def attn_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, mask: Tensor, exten
     norm = _mask_norm(mask, B, M, Skv, H)
     assert mask.dtype is torch.bool and norm is not None and k_cache.stride() == v_cache.stride()
     m, m_sb, m_sh = norm
-    nsplit = max(1, min(-(-Skv // 32), -(-_DECODE_WGS // (B * KVH)), 128))  # workgroups = nsplit * B * KVH: two or more per CU keep more rows in flight
+    nsplit = _decode_nsplit(B, KVH, Skv)
     nbytes = _lib().llx_attn_decode_workspace_bytes(B, H, M, nsplit)
     ws = _workspace(_DECODE_WS, q.device, nbytes)
     if out is None:
