@@ -222,6 +222,28 @@ int llx_gemv_bf16_dora(const void* w0, int64_t ldw0, int64_t n0, const void* w1,
                        int64_t c_ss, const int64_t* input_pos, const void* bext0, const void* bext1, const void* bext2, int64_t rank0, int64_t rank1,
                        int64_t rank2, const void* t, int64_t ldt, float lora_scale, const void* colscale0, const void* colscale1,
                        const void* colscale2, llx_stream_t s);
+/* ---- OCP MXFP4 weight-only linears (subclasses/mxfp4.py).  A weight [N, K], K % 32 == 0, is packed uint8 [N, K/2] (byte j =
+ * element 2j in bits 0-3, element 2j+1 in bits 4-7; code = sign << 3 | e2m1, magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6) and scale uint8
+ * [N, K/32] (biased exponent b of a block of 32 consecutive k of a row; block scale 2^(b - 127)).
+ * Quantise, in fp32: amax = max |x| of the block; b = 127 when amax == 0, else e = clamp(floor(log2 amax) - 2, -125, 125), b = e + 127;
+ * |x| * 2^-e rounded to the nearest magnitude, ties to the code with mantissa bit 0, above 6 saturated; the sign bit is the input's.
+ * x: bf16 (is_f32 = 0) or fp32 (1), row stride ldx elements (rows 16-byte aligned); packed and scale contiguous.  Non-finite input is
+ * the caller's to refuse. */
+int llx_quantize_mxfp4(const void* x, int64_t ldx, int is_f32, int64_t N, int64_t K, void* packed, void* scale, llx_stream_t s);
+/* The bf16 image magnitude * 2^(b - 127) (exact; never a denormal for the scales the quantiser emits): out [N, K] (ldo % 8 == 0), or with
+ * transpose out [K, N] (ldo >= N).  ldw / lds: row strides of packed (bytes, % 16) and scale (bytes). */
+int llx_dequantize_mxfp4(const void* packed, int64_t ldw, const void* scale, int64_t lds, int64_t N, int64_t K, void* out, int64_t ldo,
+                         int transpose, llx_stream_t s);
+/* llx_gemv_bf16 on MXFP4 weights: W_s = packed rows (ldw_s in bytes, % 16), scale_s / lds_s = their scale bytes and row stride, for every
+ * present segment; K % 32 == 0; M in 1..4 (3 and 4 rows: two passes over the weights).  Norm, segments, epilogues and LoRA operands as
+ * llx_gemv_bf16, and its rounding points: out = epilogue(bf16(x . dq(W)^T + lora_scale * t . bext[row])), fp32 sums, the adapter joins
+ * the base in fp32 - an MXFP4 linear behaves as a bf16 linear whose weight is the dequantised image. */
+int llx_gemv_mxfp4(const void* w0, int64_t ldw0, int64_t n0, const void* w1, int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2, int64_t n2,
+                   const void* x, int64_t ldx, int64_t M, int64_t K, const void* norm_w, float eps, int epilogue, void* out, int64_t ldo,
+                   const void* res, int64_t ldr, const float* rope, int64_t n_q, int64_t n_k, void* k_cache, void* v_cache, int64_t c_sh,
+                   int64_t c_ss, const int64_t* input_pos, const void* bext0, const void* bext1, const void* bext2, int64_t rank0, int64_t rank1,
+                   int64_t rank2, const void* t, int64_t ldt, float lora_scale, const void* scale0, int64_t lds0, const void* scale1,
+                   int64_t lds1, const void* scale2, int64_t lds2, llx_stream_t s);
 /* *extent (device int) = 1 + the largest key index any of the `rows` bool mask rows (row stride in bytes) allows; 0 if none: the
  * mask of the cached path is data (rows of a tril matrix gathered at input_pos, :194,:205), its extent sizes the decode key ranges. */
 int llx_mask_extent(const void* mask, int64_t row_stride, int64_t rows, int64_t Skv, int* extent, llx_stream_t s);

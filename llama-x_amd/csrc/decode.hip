@@ -23,12 +23,8 @@
 #include <type_traits>
 
 // ------------------------------------------------------------------------------------------------- weight-streaming GEMV
-// (the weight kinds WK_* and the per-row scale pointers of the int8 kinds are wstream.h's)
-struct GemvArgs : StreamArgs {  // QKV: table row m and cache position pos[m] for activation row m, caches of batch 1
-  // LoRA (modelling/lora.py:43): out += scale * (t . Bext[row]) with t = x . A^T computed by a previous launch of this kernel
-  const bf16_t* bext[3]; int64_t ldb[3]; int t_off[3]; int rank[3];
-  const bf16_t* t; int64_t ldt; float lora_scale;
-};
+// (the weight kinds WK_*, the per-row scale pointers of the int8 kinds, GemvArgs with its LoRA operands, dot8 and wave_sum_valu are
+// wstream.h's: the MXFP4 GEMV of mxfp4.hip is built from the same pieces)
 
 // 16 int8 weights (sign-extended to fp32: one v_cvt_f32_i32 with a byte selector each) against 16 fp32 activations, chained onto s
 __device__ __forceinline__ float dot16_i8(const u32x4_t& w, const float (&xf)[16], float s) {
@@ -40,35 +36,6 @@ __device__ __forceinline__ float dot16_i8(const u32x4_t& w, const float (&xf)[16
   return s;
 }
 
-__device__ __forceinline__ float dot8(const u32x4_t& w, const float (&xf)[8]) {
-  float s = bflo(w[0]) * xf[0];
-  s = __builtin_fmaf(bfhi(w[0]), xf[1], s);
-  s = __builtin_fmaf(bflo(w[1]), xf[2], s);
-  s = __builtin_fmaf(bfhi(w[1]), xf[3], s);
-  s = __builtin_fmaf(bflo(w[2]), xf[4], s);
-  s = __builtin_fmaf(bfhi(w[2]), xf[5], s);
-  s = __builtin_fmaf(bflo(w[3]), xf[6], s);
-  s = __builtin_fmaf(bfhi(w[3]), xf[7], s);
-  return s;
-}
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_f32(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-// Sum over the 64 lanes, every lane gets it, all in the vector pipe: DPP inside the rows of 16 (quad swaps, half mirror, mirror), then
-// v_permlane16_swap / v_permlane32_swap pair the rows (common.h's wave_sum takes six trips through the LDS crossbar; other sum order).
-__device__ __forceinline__ float wave_sum_valu(float v) {
-  v += dpp_f32<0xB1>(v);
-  v += dpp_f32<0x4E>(v);
-  v += dpp_f32<0x141>(v);
-  v += dpp_f32<0x140>(v);
-  // (__uint_as_float on the elements, not __builtin_bit_cast: hipcc 7.2 reads element 0 for BOTH halves of the pair through bit_cast)
-  const auto s16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = __uint_as_float(s16[0]) + __uint_as_float(s16[1]);
-  const auto s32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(s32[0]) + __uint_as_float(s32[1]);
-}
 // the same butterfly on int32 (the dynamic int8 kind: integer sums are exact in any order)
 template <int CTRL>
 __device__ __forceinline__ int dpp_i32(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
@@ -427,17 +394,9 @@ static int gemv_run(const char* fn, int wk, bool dora, const void* ws0, const vo
     const int rc1 = stream_check_fill_scales(fn, a, dora ? "DoRA" : "int8", ws0, ws1, ws2, n1, n2);
     if (rc1 != LLX_OK) return rc1;
   }
-  const bool lora = bext0 || bext1 || bext2;
-  LLX_REQUIRE(!lora || (t && ldt % 8 == 0 && (uintptr_t)t % 16 == 0 && rank0 % 8 == 0 && rank1 % 8 == 0 && rank2 % 8 == 0 && rank0 <= 512 && rank1 <= 512 &&
-                        rank2 <= 512 && ((uintptr_t)bext0 | (uintptr_t)bext1 | (uintptr_t)bext2) % 16 == 0),
-              "%s: bad LoRA operands (ranks must be multiples of 8, at most 512)", fn);
+  const int rc2 = gemv_check_fill_lora(fn, a, n1, bext0, bext1, bext2, rank0, rank1, rank2, t, ldt, lora_scale);
+  if (rc2 != LLX_OK) return rc2;
   const int64_t N = a.N;
-  a.bext[0] = (const bf16_t*)bext0; a.bext[1] = (const bf16_t*)bext1; a.bext[2] = (const bf16_t*)bext2;
-  a.ldb[0] = rank0; a.ldb[1] = rank1; a.ldb[2] = rank2;
-  a.rank[0] = (int)rank0; a.rank[1] = (int)rank1; a.rank[2] = (int)rank2;
-  a.t_off[0] = 0; a.t_off[1] = (int)rank0; a.t_off[2] = (int)(rank0 + rank1);
-  a.t = (const bf16_t*)t; a.ldt = ldt; a.lora_scale = lora_scale;
-  if (n1 == 0 && lora) { a.bext[1] = a.bext[2] = a.bext[0]; a.ldb[1] = a.ldb[2] = a.ldb[0]; a.rank[1] = a.rank[2] = a.rank[0]; a.t_off[1] = a.t_off[2] = 0; }
   // rows per wave: 2 (steps of 2048 elements per row: half the dependent steps of the 4-row form on every product of the decode step and
   // twice the waves where N <= 4096 would fill only half of the 2048 slots: 3.51 -> 3.39 ms per token; one row per wave: 3.43);
   // LLX_GEMV_RPW=4: the 4-row form

@@ -27,6 +27,43 @@ struct StreamArgs {
   const int64_t* pos;                                   //      the cache position of every activation row
 };
 
+// ---- the GEMV (gemv_kernel of decode.hip, gemv_mx4_kernel of mxfp4.hip): its operand block and the pieces both kernels are made of
+struct GemvArgs : StreamArgs {  // QKV: table row m and cache position pos[m] for activation row m, caches of batch 1
+  // LoRA (modelling/lora.py:43): out += scale * (t . Bext[row]) with t = x . A^T computed by a previous launch of this kernel
+  const bf16_t* bext[3]; int64_t ldb[3]; int t_off[3]; int rank[3];
+  const bf16_t* t; int64_t ldt; float lora_scale;
+};
+
+__device__ __forceinline__ float dot8(const u32x4_t& w, const float (&xf)[8]) {
+  float s = bflo(w[0]) * xf[0];
+  s = __builtin_fmaf(bfhi(w[0]), xf[1], s);
+  s = __builtin_fmaf(bflo(w[1]), xf[2], s);
+  s = __builtin_fmaf(bfhi(w[1]), xf[3], s);
+  s = __builtin_fmaf(bflo(w[2]), xf[4], s);
+  s = __builtin_fmaf(bfhi(w[2]), xf[5], s);
+  s = __builtin_fmaf(bflo(w[3]), xf[6], s);
+  s = __builtin_fmaf(bfhi(w[3]), xf[7], s);
+  return s;
+}
+
+template <int CTRL>
+__device__ __forceinline__ float dpp_f32(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
+}
+// Sum over the 64 lanes, every lane gets it, all in the vector pipe: DPP inside the rows of 16 (quad swaps, half mirror, mirror), then
+// v_permlane16_swap / v_permlane32_swap pair the rows (common.h's wave_sum takes six trips through the LDS crossbar; other sum order).
+__device__ __forceinline__ float wave_sum_valu(float v) {
+  v += dpp_f32<0xB1>(v);
+  v += dpp_f32<0x4E>(v);
+  v += dpp_f32<0x141>(v);
+  v += dpp_f32<0x140>(v);
+  // (__uint_as_float on the elements, not __builtin_bit_cast: hipcc 7.2 reads element 0 for BOTH halves of the pair through bit_cast)
+  const auto s16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  v = __uint_as_float(s16[0]) + __uint_as_float(s16[1]);
+  const auto s32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return __uint_as_float(s32[0]) + __uint_as_float(s32[1]);
+}
+
 // ---- norm on load: the pieces of x <- bf16(x * rstd * norm_w) on 8 packed bf16 elements
 __device__ __forceinline__ float sumsq8(const u32x4_t& v, float ss) {
 #pragma unroll
@@ -140,5 +177,21 @@ static inline int stream_check_fill_scales(const char* fn, StreamArgs& a, const 
   LLX_REQUIRE(ws0 && (ws1 || n1 == 0) && (ws2 || n2 == 0), "%s: null scale (every %s weight needs its per-row scales)", fn, what);
   LLX_REQUIRE(((uintptr_t)ws0 | (uintptr_t)ws1 | (uintptr_t)ws2) % 2 == 0, "%s: scale pointers must be 2-byte aligned", fn);
   a.wscale[0] = (const bf16_t*)ws0; a.wscale[1] = (const bf16_t*)(ws1 ? ws1 : ws0); a.wscale[2] = (const bf16_t*)(ws2 ? ws2 : ws0);
+  return LLX_OK;
+}
+
+// ---- host: the LoRA operands of a GEMV (nullable bext_s [n_s, rank_s], t [M, sum rank] bf16, offsets into t by segment), after stream_check_fill
+static inline int gemv_check_fill_lora(const char* fn, GemvArgs& a, int64_t n1, const void* bext0, const void* bext1, const void* bext2, int64_t rank0,
+                                       int64_t rank1, int64_t rank2, const void* t, int64_t ldt, float lora_scale) {
+  const bool lora = bext0 || bext1 || bext2;
+  LLX_REQUIRE(!lora || (t && ldt % 8 == 0 && (uintptr_t)t % 16 == 0 && rank0 % 8 == 0 && rank1 % 8 == 0 && rank2 % 8 == 0 && rank0 <= 512 && rank1 <= 512 &&
+                        rank2 <= 512 && ((uintptr_t)bext0 | (uintptr_t)bext1 | (uintptr_t)bext2) % 16 == 0),
+              "%s: bad LoRA operands (ranks must be multiples of 8, at most 512)", fn);
+  a.bext[0] = (const bf16_t*)bext0; a.bext[1] = (const bf16_t*)bext1; a.bext[2] = (const bf16_t*)bext2;
+  a.ldb[0] = rank0; a.ldb[1] = rank1; a.ldb[2] = rank2;
+  a.rank[0] = (int)rank0; a.rank[1] = (int)rank1; a.rank[2] = (int)rank2;
+  a.t_off[0] = 0; a.t_off[1] = (int)rank0; a.t_off[2] = (int)(rank0 + rank1);
+  a.t = (const bf16_t*)t; a.ldt = ldt; a.lora_scale = lora_scale;
+  if (n1 == 0 && lora) { a.bext[1] = a.bext[2] = a.bext[0]; a.ldb[1] = a.ldb[2] = a.ldb[0]; a.rank[1] = a.rank[2] = a.rank[0]; a.t_off[1] = a.t_off[2] = 0; }
   return LLX_OK;
 }

@@ -41,7 +41,11 @@ SIGNATURES: dict[str, tuple] = {
                             _P, _P, _P, _L, _L, _L, _P, _L, _F, _P, _P, _P, _I, _P]),
     "llx_gemv_bf16_dora": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _F, _I, _P, _L, _P, _L, _P, _L, _L, _P, _P, _L, _L, _P,
                                    _P, _P, _P, _L, _L, _L, _P, _L, _F, _P, _P, _P, _P]),
-    "llx_mask_extent": (c_int, [_P, _L, _L, _L, _P, _P]),
+    "llx_quantize_mxfp4": (c_int, [_P, _L, _I, _L, _L, _P, _P, _P]),
+    "llx_dequantize_mxfp4": (c_int, [_P, _L, _P, _L, _L, _L, _P, _L, _I, _P]),
+    "llx_gemv_mxfp4": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _F, _I, _P, _L, _P, _L, _P, _L, _L, _P, _P, _L, _L, _P,
+                               _P, _P, _P, _L, _L, _L, _P, _L, _F, _P, _L, _P, _L, _P, _L, _P]),
+    "llx_mask_extent":(c_int, [_P, _L, _L, _L, _P, _P]),
     "llx_kv_scatter": (c_int, [_P, _P, _L, _L, _L, _P, _P, _L, _L, _L, _P, _L, _L, _L, _L, _L, _P]),
     "llx_kv_scatter_rows": (c_int, [_P, _P, _L, _L, _L, _P, _P, _L, _L, _L, _P, _L, _L, _L, _L, _L, _L, _P]),
     "llx_gemm_rows16_workspace_bytes": (c_int64, [_L, _L, _L, _I]),

@@ -5,7 +5,9 @@ Reference semantics: the cached branch of Attention.forward (modelling/llama.py:
 stays for every call this path does not take (more than 4 tokens, more than 16 query rows per kv head, biases, adapters of rank
 above 64 or not a multiple of 8, a fused group that mixes DoRA and other members, DoRA on an int8 weight).
 Int8LinearWeight linears (weight-only or dynamic, subclasses/int8.py:106-121) stream their int8 rows (llx_gemv_i8): no bf16 image of
-the matrix is built or read.
+the matrix is built or read.  MXFP4LinearWeight linears (subclasses/mxfp4.py) stream their packed rows and scale bytes
+(llx_gemv_mxfp4) with the rounding points of the bf16 GEMV on the dequantised image; they have no batched stream yet, so a batch of
+B > 1 sequences stays on the generic path.
 
 A batch of 2 <= B <= 16 sequences with one token each (x [B, 1, D], a cache of batch B) takes the same steps per layer with the MFMA
 weight stream in place of the GEMV: the weights are read once for all B rows (a product whose K is split adds a small combine
@@ -46,14 +48,15 @@ MAX_BATCH = 16  # sequences per batched decode step on the MFMA weight stream (o
 BATCHED = True  # False: x [B, 1, D] with B > 1 takes the generic inference path (the tests' reference arm)
 
 
-KIND_BF16, KIND_I8W, KIND_I8D = "bf16", "int8-weight-only", "int8-dynamic"
+KIND_BF16, KIND_I8W, KIND_I8D, KIND_MX4 = "bf16", "int8-weight-only", "int8-dynamic", "mxfp4"
 
 
 def _plain(m: nn.Linear) -> Optional[str]:
-    """The kind of a linear this path streams, or None: bf16 weight or Int8LinearWeight (bf16 scale; weight-only or dynamic), no bias,
-    optionally a LoRA adapter (rank a multiple of 8), or - bf16 weights only - a DoRA adapter (rank a multiple of 8 up to 64, the
-    ranks dora_scale_cached builds; bf16 factors and magnitude vector)."""
+    """The kind of a linear this path streams, or None: bf16 weight, Int8LinearWeight (bf16 scale; weight-only or dynamic) or
+    MXFP4LinearWeight, no bias, optionally a LoRA adapter (rank a multiple of 8), or - bf16 weights only - a DoRA adapter (rank a
+    multiple of 8 up to 64, the ranks dora_scale_cached builds; bf16 factors and magnitude vector)."""
     from subclasses.int8 import Int8LinearWeight
+    from subclasses.mxfp4 import MXFP4LinearWeight
 
     if m.bias is not None or m.weight.dtype is not BF16:
         return None
@@ -61,8 +64,10 @@ def _plain(m: nn.Linear) -> Optional[str]:
     if not (rank == 0 or (rank % 8 == 0 and m.lora_a.dtype is BF16)):
         return None
     if _dora(m) and not (rank <= 64 and m.lora_b.dtype is BF16 and m.m.dtype is BF16 and tuple(m.m.shape) == (m.out_features,)
-                         and not isinstance(m.weight, Int8LinearWeight)):
+                         and not isinstance(m.weight, (Int8LinearWeight, MXFP4LinearWeight))):
         return None
+    if isinstance(m.weight, MXFP4LinearWeight):  # (reports bf16: recognised before the bf16 fall-through)
+        return KIND_MX4
     if isinstance(m.weight, Int8LinearWeight):
         if m.weight.scale.dtype is not BF16 or m.in_features % 16 != 0:
             return None
@@ -77,11 +82,13 @@ def _dora(m: nn.Linear) -> bool:
 
 def _w(mods) -> dict:
     """The weight operands of one gemv call: (ws, wscale, dynamic) of a group of linears of one kind; bf16 DoRA members add their cached
-    row factors (colscale)."""
+    row factors (colscale), MXFP4 members hand over their packed rows and scale bytes (mxscale)."""
     if _plain(mods[0]) == KIND_BF16:
         if _dora(mods[0]):  # (layer_ok: all members or none)
             return dict(ws=[m.weight.detach() for m in mods], colscale=[ops.dora_scale_cached(m) for m in mods])
         return dict(ws=[m.weight.detach() for m in mods])
+    if _plain(mods[0]) == KIND_MX4:
+        return dict(ws=[m.weight.packed for m in mods], mxscale=[m.weight.scale for m in mods])
     return dict(ws=[m.weight.int_data for m in mods], wscale=[m.weight.scale for m in mods], dynamic=bool(mods[0].weight.dynamic_int8_act))
 
 

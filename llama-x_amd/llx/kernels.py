@@ -855,12 +855,14 @@ def _workspace(cache: dict, device, nbytes: int, floor: int = 0) -> Tensor:
     return ws
 
 
-def _stream_operands(ws, x: Tensor, norm, epilogue: int, out: Optional[Tensor], res: Optional[Tensor], qkv: Optional[tuple], batched: bool):
+def _stream_operands(ws, x: Tensor, norm, epilogue: int, out: Optional[Tensor], res: Optional[Tensor], qkv: Optional[tuple], batched: bool,
+                     wcols: Optional[int] = None):
     """What gemv and gemm_rows16 share (the StreamArgs of csrc/wstream.h): the checks on the common operands, the output tensor and the
     leading arguments of the C entry points, w0 .. v_cache.  Returns (arguments, out, N, k_cache, pos).  batched: the q|k|v mode of
-    gemm_rows16 (table row 0 for every row, row m into cache[m]); else row m takes table row m and the cache has batch 1."""
+    gemm_rows16 (table row 0 for every row, row m into cache[m]); else row m takes table row m and the cache has batch 1.  wcols: the
+    stored columns of a weight row where they are not K (packed MXFP4 rows: K / 2 bytes)."""
     M, Kd = x.shape
-    assert 1 <= len(ws) <= 3 and all(w.dim() == 2 and w.shape[1] == Kd and w.stride(1) == 1 for w in ws) and x.stride(1) == 1
+    assert 1 <= len(ws) <= 3 and all(w.dim() == 2 and w.shape[1] == (wcols or Kd) and w.stride(1) == 1 for w in ws) and x.stride(1) == 1
     ns = [w.shape[0] for w in ws] + [0] * (3 - len(ws))
     N = sum(ns)
     wp = [L.ptr(w) for w in ws] + [None] * (3 - len(ws))
@@ -885,16 +887,89 @@ def _stream_operands(ws, x: Tensor, norm, epilogue: int, out: Optional[Tensor], 
     return args, out, N, kc, pos
 
 
+def _gemv_operands(ws, x: Tensor, norm, epilogue: int, out, res, qkv, lora, wcols: Optional[int] = None):
+    """The arguments every GEMV entry point begins with (those of llx_gemv_bf16 before the stream), and the output tensor."""
+    args, out, _, kc, pos = _stream_operands(ws, x, norm, epilogue, out, res, qkv, batched=False, wcols=wcols)
+    args += [kc.stride(1), kc.stride(2)] if kc is not None else [0, 0]
+    bs, ranks, t, ldt, lscale = [None] * 3, [0] * 3, None, 0, 0.0
+    if lora is not None:
+        b_list, t, lscale = lora
+        assert len(b_list) == len(ws) and t.dtype is BF16 and t.shape[0] == x.shape[0] and t.stride(1) == 1
+        for i, b in enumerate(b_list):
+            assert b.dtype is BF16 and b.is_contiguous() and b.shape[0] == ws[i].shape[0]
+            bs[i], ranks[i] = b, b.shape[1]
+        assert t.shape[1] == sum(ranks)
+        ldt = t.stride(0)
+    args += [L.ptr(pos), L.ptr(bs[0]), L.ptr(bs[1]), L.ptr(bs[2]), ranks[0], ranks[1], ranks[2], L.ptr(t), ldt, float(lscale)]
+    return args, out
+
+
+def _gemv_mxfp4(ws, scales, x: Tensor, norm, epilogue: int, out, res, qkv, lora, alone: bool) -> Tensor:
+    """gemv on packed MXFP4 rows (llx_gemv_mxfp4)."""
+    if not alone:
+        raise L.LlxError("gemv: mxscale (MXFP4 weights) excludes wscale, dynamic and colscale")
+    Kd = x.shape[1]
+    if Kd % 32 != 0:
+        raise L.LlxError(f"gemv: K={Kd} must be a multiple of 32 for MXFP4 weights")
+    if len(scales) != len(ws) or not all(w.dtype is torch.uint8 and sc.dtype is torch.uint8 and sc.dim() == 2 and sc.shape == (w.shape[0], Kd // 32)
+                                         and sc.stride(1) == 1 for w, sc in zip(ws, scales)):
+        raise L.LlxError("gemv: MXFP4 weights are uint8 [n_s, K/2] rows with one uint8 [n_s, K/32] scale tensor each")
+    _chk_bf16(x)
+    L.require_cuda(*ws, *scales)
+    args, out = _gemv_operands(ws, x, norm, epilogue, out, res, qkv, lora, wcols=Kd // 2)
+    sp = [v for sc in scales for v in (L.ptr(sc), sc.stride(0))] + [None, 0] * (3 - len(ws))
+    L.check(_lib().llx_gemv_mxfp4(*args, *sp, L.stream()), "llx_gemv_mxfp4")
+    return out
+
+
+def quantize_mxfp4(x: Tensor) -> tuple[Tensor, Tensor]:
+    """x [N, K] bf16 or fp32 (K % 32 == 0, unit column stride) -> (packed uint8 [N, K/2], scale uint8 [N, K/32]): OCP MXFP4, the rule of
+    csrc/mxfp4.hip (llx_quantize_mxfp4).  Finite input is the caller's to check."""
+    L.require_cuda(x)
+    assert x.dim() == 2 and x.dtype in (BF16, torch.float32)
+    N, Kd = x.shape
+    if Kd % 32 != 0:
+        raise L.LlxError(f"quantize_mxfp4: K={Kd} must be a multiple of 32")
+    per16 = 4 if x.dtype is torch.float32 else 8
+    if x.stride(1) != 1 or x.stride(0) % per16 != 0 or x.data_ptr() % 16 != 0:
+        x = x.contiguous()
+    packed = torch.empty(N, Kd // 2, device=x.device, dtype=torch.uint8)
+    scale = torch.empty(N, Kd // 32, device=x.device, dtype=torch.uint8)
+    L.check(_lib().llx_quantize_mxfp4(L.ptr(x), x.stride(0), int(x.dtype is torch.float32), N, Kd, L.ptr(packed), L.ptr(scale), L.stream()),
+            "llx_quantize_mxfp4")
+    return packed, scale
+
+
+def dequantize_mxfp4(packed: Tensor, scale: Tensor, *, transpose: bool = False, out: Optional[Tensor] = None) -> Tensor:
+    """The bf16 image [N, K] of packed MXFP4 rows (exact), or with transpose [K, N]; out: a row-strided view to fill (llx_dequantize_mxfp4)."""
+    L.require_cuda(packed, scale)
+    assert packed.dim() == 2 and scale.dim() == 2 and packed.dtype is torch.uint8 and scale.dtype is torch.uint8
+    assert packed.stride(1) == 1 and scale.stride(1) == 1
+    N, Kd = packed.shape[0], packed.shape[1] * 2
+    assert scale.shape == (N, Kd // 32) and Kd % 32 == 0
+    shape = (Kd, N) if transpose else (N, Kd)
+    if out is None:
+        out = torch.empty(shape, device=packed.device, dtype=BF16)
+    assert out.shape == shape and out.dtype is BF16 and out.stride(1) == 1
+    L.check(_lib().llx_dequantize_mxfp4(L.ptr(packed), packed.stride(0), L.ptr(scale), scale.stride(0), N, Kd, L.ptr(out), out.stride(0),
+                                        int(transpose), L.stream()), "llx_dequantize_mxfp4")
+    return out
+
+
 def gemv(ws: Sequence[Tensor], x: Tensor, *, norm: Optional[tuple[Tensor, float]] = None, epilogue: int = GV_NONE, out: Optional[Tensor] = None,
          res: Optional[Tensor] = None, qkv: Optional[tuple] = None, lora: Optional[tuple] = None, wscale: Optional[Sequence[Tensor]] = None,
-         dynamic: bool = False, colscale: Optional[Sequence[Tensor]] = None) -> Tensor:
+         dynamic: bool = False, colscale: Optional[Sequence[Tensor]] = None, mxscale: Optional[Sequence[Tensor]] = None) -> Tensor:
     """out = epilogue([rmsnorm(x) | x] @ cat(ws)^T) for M = x.shape[0] <= 4 rows: every CU streams weight rows (llx_gemv_bf16).
     ws: 1-3 weights [n_s, K]; norm = (weight, eps); res [M, N] for GV_RESIDUAL; qkv = (rope_table, n_q, n_k, k_cache, v_cache, input_pos)
     for GV_QKV (caches [1, KVH, Smax, 128]; returns q [M, n_q]); GV_SWIGLU returns h [M, n_0]; lora = (b factors, t [M, sum r], scale).
     int8 ws (the int_data of Int8LinearWeights, all members of the call) with wscale = their bf16 per-row scales run llx_gemv_i8:
     weight-only arithmetic, or with dynamic=True the rows of x quantised on chip and integer dot products (subclasses/int8.py:106-121).
     colscale (bf16 weights only): one contiguous bf16 [n_s] factor per weight, DoRA's cached m / ||W + s B A||_row (ops.dora_scale_cached);
-    the linear's bf16 output is multiplied by it and rounded before the epilogue (llx_gemv_bf16_dora)."""
+    the linear's bf16 output is multiplied by it and rounded before the epilogue (llx_gemv_bf16_dora).
+    mxscale: ws are the packed uint8 [n_s, K/2] rows of MXFP4LinearWeights (all members of the call) and mxscale their uint8 [n_s, K/32]
+    scale bytes (llx_gemv_mxfp4): the rounding points of the bf16 call on the dequantised image; K = x.shape[1] % 32 == 0."""
+    if mxscale is not None:
+        return _gemv_mxfp4(ws, mxscale, x, norm, epilogue, out, res, qkv, lora, wscale is None and not dynamic and colscale is None)
     i8 = [w.dtype is torch.int8 for w in ws]
     if colscale is not None:
         if any(i8):
@@ -914,18 +989,7 @@ def gemv(ws: Sequence[Tensor], x: Tensor, *, norm: Optional[tuple[Tensor, float]
     else:
         assert wscale is None and not dynamic, "wscale / dynamic belong to int8 weights"
         _chk_bf16(x, *ws)
-    args, out, _, kc, pos = _stream_operands(ws, x, norm, epilogue, out, res, qkv, batched=False)
-    args += [kc.stride(1), kc.stride(2)] if kc is not None else [0, 0]
-    bs, ranks, t, ldt, lscale = [None] * 3, [0] * 3, None, 0, 0.0
-    if lora is not None:
-        b_list, t, lscale = lora
-        assert len(b_list) == len(ws) and t.dtype is BF16 and t.shape[0] == x.shape[0] and t.stride(1) == 1
-        for i, b in enumerate(b_list):
-            assert b.dtype is BF16 and b.is_contiguous() and b.shape[0] == ws[i].shape[0]
-            bs[i], ranks[i] = b, b.shape[1]
-        assert t.shape[1] == sum(ranks)
-        ldt = t.stride(0)
-    args += [L.ptr(pos), L.ptr(bs[0]), L.ptr(bs[1]), L.ptr(bs[2]), ranks[0], ranks[1], ranks[2], L.ptr(t), ldt, float(lscale)]
+    args, out = _gemv_operands(ws, x, norm, epilogue, out, res, qkv, lora)
     if any(i8):
         sp = [L.ptr(sc) for sc in wscale] + [None] * (3 - len(ws))
         L.check(_lib().llx_gemv_i8(*args, sp[0], sp[1], sp[2], int(bool(dynamic)), L.stream()), "llx_gemv_i8")

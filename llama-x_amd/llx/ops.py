@@ -58,12 +58,14 @@ class LinearPlan:
     * plain:      F.linear(x, W, b)                                              (modelling/llama.py:118-120 ...)
     * LoRA:       F.linear(x, W, b) + x @ A^T @ B^T * (alpha/r)                  (modelling/lora.py:40-44)
     * int8 W:     _Int8Linear (weight-only or dynamic-activation)                (subclasses/int8.py:106-130)
+    * MXFP4 W:    the plain / LoRA plan on a transient bf16 image of the weight  (subclasses/mxfp4.py)
 
     ``tensors()`` lists the tensors autograd must see; ``backward`` returns their gradients in that order.
     """
 
     def __init__(self, m: nn.Linear):
         from subclasses.int8 import Int8LinearWeight  # local import: subclasses imports llx too
+        from subclasses.mxfp4 import MXFP4LinearWeight
 
         self.N, self.K = m.out_features, m.in_features
         self.weight = m.weight
@@ -75,10 +77,15 @@ class LinearPlan:
         self.dora_m = getattr(m, "m", None) if self.rank > 0 else None  # DoRALinear's magnitude vector (modelling/lora.py:51)
         self.int8 = isinstance(self.weight, Int8LinearWeight)
         self.dynamic = bool(self.int8 and self.weight.dynamic_int8_act)
+        # MXFP4 weight-only: the bf16 plan on a transient image of the weight (w_image / wt_image), which is never cached - the memory
+        # is the point of the format; frozen like int8 (no weight gradient)
+        self.mx4 = isinstance(self.weight, MXFP4LinearWeight)
         self.no_grad = False  # set by linear(): the call runs with grad disabled
         if self.dora_m is not None and self.int8:
             # the reference cannot run this combination either: (weight + delta).norm() has no Int8LinearWeight dispatch (subclasses/int8.py:102)
             raise LlxError("DoRA on an Int8LinearWeight is not supported (nor by the reference: no dispatch for weight + delta)")
+        if self.dora_m is not None and self.mx4:
+            raise LlxError("DoRA on an MXFP4LinearWeight is not supported (as on int8: no dispatch for weight + delta)")
         if self.rank > 64:
             raise LlxError(f"LoRA rank {self.rank} > 64 is not supported by the skinny kernels")
         if self.rank > 0 and self.lora_a.dtype is not BF16:
@@ -87,7 +94,7 @@ class LinearPlan:
     # ---- autograd-visible tensors
     def tensors(self) -> list[Tensor]:
         ts = []
-        if not self.int8:
+        if not self.int8 and not self.mx4:
             ts.append(self.weight)
         if self.bias is not None:
             ts.append(self.bias)
@@ -96,6 +103,13 @@ class LinearPlan:
         if self.dora_m is not None:
             ts.append(self.dora_m)
         return ts
+
+    # ---- the bf16 operand images of the base weight: the weight itself and its cached transpose, or - MXFP4 - transient images
+    def w_image(self) -> Tensor:
+        return K.dequantize_mxfp4(self.weight.packed, self.weight.scale) if self.mx4 else self.weight.detach()
+
+    def wt_image(self) -> Tensor:
+        return K.dequantize_mxfp4(self.weight.packed, self.weight.scale, transpose=True) if self.mx4 else weight_t(self.weight)
 
     # ---- forward: y = linear(x) [+ residual]; returns (y, saved) where saved is the LoRA intermediate t = x @ A^T
     # (DoRA: the tuple (t, z, c, inv_norm) - un-scaled output, column scale m / ||W + sBA||, 1 / norm)
@@ -129,7 +143,7 @@ class LinearPlan:
             if residual is not None:
                 y = K.add(y, residual, out=out)
             return y, t
-        w = self.weight.detach()
+        w = self.w_image()
         if self.bias is not None:
             if residual is not None:
                 raise LlxError("bias + residual epilogue is not supported")
@@ -155,7 +169,7 @@ class LinearPlan:
         if self.rank > 0:
             u = K.skinny_nt(dy, K.transpose(self.lora_b.detach()))  # dy @ B  -> [M,64]
         # --- parameter gradients, in tensors() order
-        if not self.int8:
+        if not self.int8 and not self.mx4:
             grads.append(K.gemm_tn(dy, x) if next(ni) else None)
         if self.bias is not None:
             grads.append(K.colsum(dy_out) if next(ni) else None)  # the bias is added after the DoRA rescale
@@ -186,7 +200,7 @@ class LinearPlan:
                 wt = int8_weight_t(self.weight)
             else:
                 g = dy
-                wt = weight_t(self.weight)
+                wt = self.wt_image()
             if dx_accum:
                 dx = K.gemm_nt(g, wt, out=dx_out, a2=u, b2=b2, epilogue=K.EPI_RESIDUAL, e=dx_out, k2_eff=self.rank)
             else:
@@ -252,14 +266,14 @@ class GroupPlan:
         self.ranks = [m.rank for m in self.members]
         self.R = sum(self.ranks)
         self.r_off = [sum(self.ranks[:i]) for i in range(len(self.ranks))]
-        same_kind = all((m.int8, m.dynamic) == (m0.int8, m0.dynamic) for m in self.members)
+        same_kind = all((m.int8, m.dynamic, m.mx4) == (m0.int8, m0.dynamic, m0.mx4) for m in self.members)
         same_scale = len({m.scale for m in self.members if m.rank > 0}) <= 1
         lora_all_or_none = all(r > 0 for r in self.ranks) or self.R == 0
         dora_all_or_none = len({m.dora_m is not None for m in self.members}) == 1
         self.dora = all(m.dora_m is not None for m in self.members)
         self.fused = (same_kind and same_scale and lora_all_or_none and dora_all_or_none and self.R <= 64
                       and all(m.bias is None for m in self.members) and all(m.K == self.K for m in self.members))
-        self.int8, self.dynamic = m0.int8, m0.dynamic
+        self.int8, self.dynamic, self.mx4 = m0.int8, m0.dynamic, m0.mx4
         self.packed = None  # (a_cat, b2, bT, a2t) when prepack() built the LoRA operand images of several groups in one launch
         self.scale = next((m.scale for m in self.members if m.rank > 0), 1.0)
         # true contraction length of the (block-diagonal, zero-padded) LoRA K-extension: forward sum_i N_i r_i / N, dgrad R
@@ -272,7 +286,16 @@ class GroupPlan:
     def _weights(self):
         return [(m.weight.int_data if m.int8 else m.weight) for m in self.members]
 
+    def _mx4_image(self, transpose: bool) -> Tensor:
+        """MXFP4 members: their bf16 images side by side, [sum N, K] or transposed [K, sum N] - built per call and dropped after it."""
+        out = torch.empty((self.K, self.N) if transpose else (self.N, self.K), device=self.members[0].weight.device, dtype=BF16)
+        for m, o, n in zip(self.members, self.n_off, self.Ns):
+            K.dequantize_mxfp4(m.weight.packed, m.weight.scale, transpose=transpose, out=out[:, o : o + n] if transpose else out[o : o + n])
+        return out
+
     def w_cat(self) -> Tensor:
+        if self.mx4:
+            return self._mx4_image(False)
         ws = self._weights()
         if self.int8 and self.dynamic:
             return _cached_multi(ws, "cat_i8", lambda: torch.cat([w.detach() for w in ws], 0))
@@ -281,6 +304,8 @@ class GroupPlan:
         return _cached_multi(ws, "cat", lambda: torch.cat([w.detach() for w in ws], 0) if len(ws) > 1 else ws[0].detach())
 
     def wt_cat(self) -> Tensor:
+        if self.mx4:
+            return self._mx4_image(True)
         ws = self._weights()
         return _cached_multi(ws, "cat_t", lambda: K.transpose(torch.cat([w.detach() for w in ws], 0) if len(ws) > 1 else ws[0].detach()))
 
@@ -495,7 +520,7 @@ class GroupPlan:
         gb_i = 0
         for m, nd, ro, no, n in zip(self.members, need, self.r_off, self.n_off, self.Ns):
             j = 0
-            if not m.int8:
+            if not m.int8 and not m.mx4:
                 grads.append(K.gemm_tn(dy[:, no : no + n], x) if nd[j] else None)
                 j += 1
             if m.rank > 0:
@@ -904,7 +929,7 @@ def _head_logits(plan: LinearPlan, rows_in: Tensor, route: HeadRoute, cnt: Optio
             cnt_c = cnt
             m_expect = float(cnt.item()) if K.GEMM_TRACE is not None else None
         logits = torch.empty(r1 - r0, plan.N, device=rows_in.device, dtype=BF16)
-        K.gemm_nt(rows_in[r0:r1], plan.weight.detach(), out=logits, m_valid=cnt_c, m_expect=m_expect)
+        K.gemm_nt(rows_in[r0:r1], plan.w_image(), out=logits, m_valid=cnt_c, m_expect=m_expect)
         yield r0, r1, logits, cnt_c, None, m_expect
 
 
@@ -914,7 +939,7 @@ def _head_dhidden(route: HeadRoute, plan: LinearPlan, dlogits, cnt, inv: Optiona
     3071 labelled rows) still fill the chip with full rounds of short tiles.  Every route uses the same split, so they stay
     bit-identical to each other.  Chunked rows: dlogits and cnt are tuples with one entry per chunk - a product per chunk into one
     buffer, then one scatter / scale over all rows."""
-    wt = weight_t(plan.weight)
+    wt = plan.wt_image()
     split = wt.shape[1] % (64 * _HEAD_SPLITK) == 0
     if route.chunk:
         dxc = torch.empty(sum(dl.shape[0] for dl in dlogits), wt.shape[0], device=wt.device, dtype=BF16)
