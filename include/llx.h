@@ -255,6 +255,23 @@ int llx_kv_scatter(const void* k, const void* v, int64_t s_sb, int64_t s_sh, int
 int llx_kv_scatter_rows(const void* k, const void* v, int64_t s_sb, int64_t s_sh, int64_t s_ss, void* k_cache, void* v_cache, int64_t c_sb,
                         int64_t c_sh, int64_t c_ss, const int64_t* input_pos, int64_t p_sb, int64_t B, int64_t KVH, int64_t L, int64_t Smax,
                         int64_t head_dim, llx_stream_t s);
+/* ---- FP8 KV cache: a cache is uint8 [B, KVH, Smax, 128] of OCP E4M3 codes (e4m3fn: bias 7, normals from 2^-6, subnormals
+ * in steps of 2^-9, no infinities), no scale; every cache stride below is in BYTES.  q(x), on the bf16 value x the bf16 cache would have
+ * held: clamp to [-448, 448], round to nearest even on the E4M3 grid, the sign bit is the input's (zero too), +-inf saturates, NaN stays
+ * a NaN code.  dq(code) is exact in bf16.  An FP8 cache behaves as a bf16 cache that holds dq(q(x)) wherever the bf16 cache holds x.
+ * The two scatters are llx_kv_scatter / llx_kv_scatter_rows with q() on the way (an out-of-range position writes nothing); sources
+ * bf16 through element strides (% 8), cache strides % 16, all pointers 16-byte aligned. */
+int llx_kv_scatter_f8(const void* k, const void* v, int64_t s_sb, int64_t s_sh, int64_t s_ss, void* k_cache, void* v_cache, int64_t c_sb, int64_t c_sh,
+                      int64_t c_ss, const int64_t* input_pos, int64_t B, int64_t KVH, int64_t L, int64_t Smax, int64_t head_dim, llx_stream_t s);
+int llx_kv_scatter_rows_f8(const void* k, const void* v, int64_t s_sb, int64_t s_sh, int64_t s_ss, void* k_cache, void* v_cache, int64_t c_sb,
+                           int64_t c_sh, int64_t c_ss, const int64_t* input_pos, int64_t p_sb, int64_t B, int64_t KVH, int64_t L, int64_t Smax,
+                           int64_t head_dim, llx_stream_t s);
+/* out bf16 [B, KVH, S, 128] contiguous = dq(cache [B, KVH, S, 128] through byte strides % 16): the transient image the prefill kernels read. */
+int llx_kv_dequantize_f8(const void* cache, int64_t c_sb, int64_t c_sh, int64_t c_ss, void* out, int64_t B, int64_t KVH, int64_t S,
+                         int64_t head_dim, llx_stream_t s);
+/* The weight streams write an FP8 cache through epilogue 4: epilogue 2 (q|k|v) of every llx_gemv_* / llx_gemm_rows16_* entry point with
+ * k_cache / v_cache pointing at codes and c_sb / c_sh / c_ss in bytes (% 4, pointers 4-byte aligned); the k / v branch stores q() of the
+ * bf16 values epilogue 2 would have stored, the q rows are unchanged. */
 /* The product of llx_gemv_bf16 for 2 <= M <= 16 activation rows (a batch of sequences, one token each) on the matrix pipe:
  * out = epilogue( [rmsnorm(x) | x][M, K] . [W0; W1; W2]^T ) with v_mfma_f32_16x16x32_bf16 (rows padded to 16 with zeros in registers),
  * fp32 accumulation, every weight element read from HBM once whatever M is.  bf16 weights without adapters; W_s [n_s, K] row-major
@@ -314,6 +331,13 @@ int llx_attn_decode(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, con
                     int64_t c_ss, void* o, int64_t o_sb, int64_t o_sh, int64_t o_ss, const void* mask, int64_t m_sb, int64_t m_sh, int64_t m_sq,
                     const int* extent, float* workspace, int64_t B, int64_t H, int64_t KVH, int64_t M, int64_t Skv, int64_t nsplit,
                     int64_t head_dim, float scale, llx_stream_t s);
+/* llx_attn_decode over FP8 caches: uint8 [B, KVH, Skv, 128] of E4M3 codes through byte strides (% 8, pointers 16-byte aligned), unpacked
+ * with the hardware conversion; the same lane layout, split plan, mask handling, partials, combine launch and workspace, and the result
+ * of llx_attn_decode on the caches' bf16 images. */
+int llx_attn_decode_f8(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, const void* k_cache, const void* v_cache, int64_t c_sb, int64_t c_sh,
+                       int64_t c_ss, void* o, int64_t o_sb, int64_t o_sh, int64_t o_ss, const void* mask, int64_t m_sb, int64_t m_sh, int64_t m_sq,
+                       const int* extent, float* workspace, int64_t B, int64_t H, int64_t KVH, int64_t M, int64_t Skv, int64_t nsplit,
+                       int64_t head_dim, float scale, llx_stream_t s);
 
 /* ---- RoPE: apply_rope at modelling/llama.py:63-73 (in place on the first `nheads` 128-wide heads of each row;
  *      table fp32 [S,64,2] from build_rope :54-60); backward = rotation by -theta. ----------------------------- */

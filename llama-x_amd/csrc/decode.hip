@@ -353,6 +353,7 @@ static int launch_gemv_m(const char* fn, const GemvArgs& a, int epi, int grid, s
     case GV_NONE: return launch_gemv_n<MT, GV_NONE, RPW, WK, DORA>(fn, a, grid, lds, stream);
     case GV_RESIDUAL: return launch_gemv_n<MT, GV_RESIDUAL, RPW, WK, DORA>(fn, a, grid, lds, stream);
     case GV_QKV: return launch_gemv_n<MT, GV_QKV, RPW, WK, DORA>(fn, a, grid, lds, stream);
+    case GV_QKV_F8: return launch_gemv_n<MT, GV_QKV_F8, RPW, WK, DORA>(fn, a, grid, lds, stream);
     default: return launch_gemv_n<MT, GV_SWIGLU, RPW, WK, DORA>(fn, a, grid, lds, stream);
   }
 }
@@ -569,8 +570,14 @@ struct DecodeArgs {
 // the call) share every K / V row read.  A 16-lane group owns one key per load (lane = 16-byte chunk of the 256-byte row): four keys
 // per wave-instruction, sixteen per wave and step (8 x 16-byte loads in flight per lane), 64 per workgroup step.
 // DEC_KPG = keys per lane group and step: 4 for up to 4 query rows (the batch-1 decode step), fewer for more rows (register budget)
-template <int ROWS, int DEC_KPG>
+// F8: the caches hold E4M3 codes (a.kc / a.vc point at bytes, cache strides in bytes).  The lane layout is the bf16 one -
+// a lane owns the same 8 elements of a row, now an 8-byte load, 16 lanes x 8 B = one 128-byte row - so every sum below runs over the
+// same elements in the same order and the kernel computes what the bf16 instance computes on dq(code); the codes are unpacked with
+// v_cvt_pk_f32_fp8 where the bf16 instance shifts.
+template <int ROWS, int DEC_KPG, bool F8 = false>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeArgs a) {
+  using CT = std::conditional_t<F8, uint8_t, bf16_t>;     // a stored cache element
+  using ld_t = std::conditional_t<F8, u32x2_t, u32x4_t>;  // a lane's 8 elements of a row
   // partials that meet in LDS: one per wave after a shuffle merge of its four lane groups, or - for up to 4 rows, where 16 partials fit
   // in 32 KB - one per lane group straight from the registers (the 80 dependent shuffles of the merge cost 1.6 us of a 7.5 us block)
   constexpr int NPART = ROWS <= 4 ? 16 : 4;
@@ -602,21 +609,21 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeArgs a) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[r][e] = 0.f;
   }
-  const bf16_t* kb = a.kc + b * a.c_sb + kvh * a.c_sh + c * 8;
-  const bf16_t* vb = a.vc + b * a.c_sb + kvh * a.c_sh + c * 8;
+  const CT* kb = reinterpret_cast<const CT*>(a.kc) + b * a.c_sb + kvh * a.c_sh + c * 8;
+  const CT* vb = reinterpret_cast<const CT*>(a.vc) + b * a.c_sb + kvh * a.c_sh + c * 8;
   const bool shared_mask = a.m_sh == 0;  // the reference's mask (tril rows gathered at input_pos) is the same for every head
   const uint8_t* mbase = a.mask + b * a.m_sb;
   // Two register sets: the K / V rows and mask bytes of step i+1 are in flight while step i is computed - a wave walks only 2-8
   // steps, so with the loads issued step by step every step paid a full HBM round trip (the kernel ran at 1.5 TB/s).  The mask bytes
   // are only LOADED in the load step, unconditionally and with clamped indices: turning them into bits needs their values and would
   // make the step wait for its own loads.
-  auto load_step = [&](int k0, u32x4_t (&kv)[DEC_KPG], u32x4_t (&vv)[DEC_KPG], uint8_t (&mb)[DEC_KPG][ROWS]) {
+  auto load_step = [&](int k0, ld_t (&kv)[DEC_KPG], ld_t (&vv)[DEC_KPG], uint8_t (&mb)[DEC_KPG][ROWS]) {
 #pragma unroll
     for (int j = 0; j < DEC_KPG; ++j) {
       const int key = k0 + j * 4 + grp;
       const int kk = min(key, a.Skv - 1);
-      kv[j] = *reinterpret_cast<const u32x4_t*>(kb + (int64_t)kk * a.c_ss);
-      vv[j] = *reinterpret_cast<const u32x4_t*>(vb + (int64_t)kk * a.c_ss);
+      kv[j] = *reinterpret_cast<const ld_t*>(kb + (int64_t)kk * a.c_ss);
+      vv[j] = *reinterpret_cast<const ld_t*>(vb + (int64_t)kk * a.c_ss);
 #pragma unroll
       for (int r = 0; r < ROWS; ++r) {
         // shared mask: entry m = token m (expanded to the G heads below); per-head mask: entry r = (head g, token m)
@@ -625,7 +632,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeArgs a) {
       }
     }
   };
-  auto compute_step = [&](int k0, const u32x4_t (&kv)[DEC_KPG], const u32x4_t (&vv)[DEC_KPG], const uint8_t (&mb)[DEC_KPG][ROWS]) {
+  auto compute_step = [&](int k0, const ld_t (&kv)[DEC_KPG], const ld_t (&vv)[DEC_KPG], const uint8_t (&mb)[DEC_KPG][ROWS]) {
     uint32_t allow[DEC_KPG];  // shared mask: bit m = token m; per-head mask: bit r = query row r
 #pragma unroll
     for (int j = 0; j < DEC_KPG; ++j) {
@@ -637,12 +644,21 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeArgs a) {
       }
       allow[j] = (k0 + j * 4 + grp) < k_hi ? w : 0u;
     }
+    float vf[F8 ? DEC_KPG : 1][8];  // F8: the V rows unpacked once per step, not once per query row
+    if constexpr (F8) {
+#pragma unroll
+      for (int j = 0; j < DEC_KPG; ++j) kv8_decode8(vv[j], vf[j]);
+    }
     float s[DEC_KPG][ROWS];
 #pragma unroll
     for (int j = 0; j < DEC_KPG; ++j) {
       float kf[8];
+      if constexpr (F8) {
+        kv8_decode8(kv[j], kf);
+      } else {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) { kf[2 * e] = bflo(kv[j][e]); kf[2 * e + 1] = bfhi(kv[j][e]); }
+        for (int e = 0; e < 4; ++e) { kf[2 * e] = bflo(kv[j][e]); kf[2 * e + 1] = bfhi(kv[j][e]); }
+      }
 #pragma unroll
       for (int r = 0; r < ROWS; ++r) {
         float d = 0.f;
@@ -674,14 +690,17 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeArgs a) {
       for (int e = 0; e < 4; ++e) {
         float lo = o[r][2 * e] * alpha, hi = o[r][2 * e + 1] * alpha;
 #pragma unroll
-        for (int j = 0; j < DEC_KPG; ++j) { lo = __builtin_fmaf(p[j], bflo(vv[j][e]), lo); hi = __builtin_fmaf(p[j], bfhi(vv[j][e]), hi); }
+        for (int j = 0; j < DEC_KPG; ++j) {
+          if constexpr (F8) { lo = __builtin_fmaf(p[j], vf[j][2 * e], lo); hi = __builtin_fmaf(p[j], vf[j][2 * e + 1], hi); }
+          else { lo = __builtin_fmaf(p[j], bflo(vv[j][e]), lo); hi = __builtin_fmaf(p[j], bfhi(vv[j][e]), hi); }
+        }
         o[r][2 * e] = lo; o[r][2 * e + 1] = hi;
       }
     }
   };
   {
     const int kstep = 16 * DEC_KPG;
-    u32x4_t kvA[DEC_KPG], vvA[DEC_KPG], kvB[DEC_KPG], vvB[DEC_KPG];
+    ld_t kvA[DEC_KPG], vvA[DEC_KPG], kvB[DEC_KPG], vvB[DEC_KPG];
     uint8_t mbA[DEC_KPG][ROWS], mbB[DEC_KPG][ROWS];
     int k0 = k_lo + wave * (4 * DEC_KPG);
     if (k0 < k_hi) load_step(k0, kvA, vvA, mbA);
@@ -783,17 +802,18 @@ extern "C" int64_t llx_attn_decode_workspace_bytes(int64_t B, int64_t H, int64_t
 // (modelling/llama.py:126-127,135-137).  q [B,H,M,128], caches [B,KVH,Skv,128], o [B,H,M,128] through (batch, head, position) element
 // strides; mask bool [.., M, Skv] with broadcast strides; extent (nullable device int, llx_mask_extent): bound on the keys any row
 // may attend to; workspace: llx_attn_decode_workspace_bytes(B, H, M, nsplit) bytes of fp32.
-extern "C" int llx_attn_decode(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, const void* k_cache, const void* v_cache, int64_t c_sb,
-                               int64_t c_sh, int64_t c_ss, void* o, int64_t o_sb, int64_t o_sh, int64_t o_ss, const void* mask, int64_t m_sb,
-                               int64_t m_sh, int64_t m_sq, const int* extent, float* workspace, int64_t B, int64_t H, int64_t KVH, int64_t M,
-                               int64_t Skv, int64_t nsplit, int64_t head_dim, float scale, hipStream_t stream) {
-  LLX_REQUIRE(q && k_cache && v_cache && o && mask && workspace, "llx_attn_decode: null pointer");
-  LLX_REQUIRE(head_dim == HD, "llx_attn_decode: head_dim=%lld unsupported (only 128)", (long long)head_dim);
-  LLX_REQUIRE(B > 0 && H > 0 && KVH > 0 && H % KVH == 0 && M > 0 && Skv > 0 && nsplit > 0 && nsplit <= 1024 && B < 65536 && KVH < 65536, "llx_attn_decode: bad sizes");
+// what the two entry points share; f8: the caches hold E4M3 codes, cache strides in bytes
+static int attn_decode_run(const char* fn, bool f8, const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, const void* k_cache, const void* v_cache, int64_t c_sb,
+                           int64_t c_sh, int64_t c_ss, void* o, int64_t o_sb, int64_t o_sh, int64_t o_ss, const void* mask, int64_t m_sb,
+                           int64_t m_sh, int64_t m_sq, const int* extent, float* workspace, int64_t B, int64_t H, int64_t KVH, int64_t M,
+                           int64_t Skv, int64_t nsplit, int64_t head_dim, float scale, hipStream_t stream) {
+  LLX_REQUIRE(q && k_cache && v_cache && o && mask && workspace, "%s: null pointer", fn);
+  LLX_REQUIRE(head_dim == HD, "%s: head_dim=%lld unsupported (only 128)", fn, (long long)head_dim);
+  LLX_REQUIRE(B > 0 && H > 0 && KVH > 0 && H % KVH == 0 && M > 0 && Skv > 0 && nsplit > 0 && nsplit <= 1024 && B < 65536 && KVH < 65536, "%s: bad sizes", fn);
   const int64_t rows = H / KVH * M;
-  LLX_REQUIRE(rows <= 16, "llx_attn_decode: %lld query rows per kv head (heads per group x tokens) exceed 16: use llx_attn_dense_fwd", (long long)rows);
+  LLX_REQUIRE(rows <= 16, "%s: %lld query rows per kv head (heads per group x tokens) exceed 16: use llx_attn_dense_fwd", fn, (long long)rows);
   LLX_REQUIRE(((q_sb | q_sh | q_ss | c_sb | c_sh | c_ss) % 8) == 0 && ((uintptr_t)q | (uintptr_t)k_cache | (uintptr_t)v_cache) % 16 == 0 && (uintptr_t)workspace % 16 == 0,
-              "llx_attn_decode: rows must be 16-byte aligned");
+              "%s: rows must be 16-byte aligned", fn);
   DecodeArgs a;
   a.q = (const bf16_t*)q; a.q_sb = q_sb; a.q_sh = q_sh; a.q_ss = q_ss;
   a.kc = (const bf16_t*)k_cache; a.vc = (const bf16_t*)v_cache; a.c_sb = c_sb; a.c_sh = c_sh; a.c_ss = c_ss;
@@ -801,12 +821,39 @@ extern "C" int llx_attn_decode(const void* q, int64_t q_sb, int64_t q_sh, int64_
   a.B = (int)B; a.H = (int)H; a.KVH = (int)KVH; a.M = (int)M; a.Skv = (int)Skv; a.nsplit = (int)nsplit;
   a.scale_log2 = scale * 1.4426950408889634f;
   const dim3 grid((unsigned)nsplit, (unsigned)KVH, (unsigned)B);
-  if (rows <= 4) hipLaunchKernelGGL((attn_decode_kernel<4, 4>), grid, dim3(256), 0, stream, a);
-  else if (rows <= 8) hipLaunchKernelGGL((attn_decode_kernel<8, 2>), grid, dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL((attn_decode_kernel<16, 1>), grid, dim3(256), 0, stream, a);
-  LLX_LAUNCH_CHECK("llx_attn_decode");
+  if (f8) {
+    if (rows <= 4) hipLaunchKernelGGL((attn_decode_kernel<4, 4, true>), grid, dim3(256), 0, stream, a);
+    else if (rows <= 8) hipLaunchKernelGGL((attn_decode_kernel<8, 2, true>), grid, dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((attn_decode_kernel<16, 1, true>), grid, dim3(256), 0, stream, a);
+  } else {
+    if (rows <= 4) hipLaunchKernelGGL((attn_decode_kernel<4, 4>), grid, dim3(256), 0, stream, a);
+    else if (rows <= 8) hipLaunchKernelGGL((attn_decode_kernel<8, 2>), grid, dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((attn_decode_kernel<16, 1>), grid, dim3(256), 0, stream, a);
+  }
+  LLX_LAUNCH_CHECK(fn);
   hipLaunchKernelGGL(attn_decode_combine_kernel, dim3((unsigned)(B * H * M)), dim3(512), 0, stream, (const float*)workspace, (int)nsplit, (bf16_t*)o, o_sb,
                      o_sh, o_ss, (int)H, (int)M);
-  LLX_LAUNCH_CHECK("llx_attn_decode(combine)");
+  char name[64];
+  snprintf(name, sizeof name, "%s(combine)", fn);
+  LLX_LAUNCH_CHECK(name);
   return LLX_OK;
+}
+
+extern "C" int llx_attn_decode(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, const void* k_cache, const void* v_cache, int64_t c_sb,
+                               int64_t c_sh, int64_t c_ss, void* o, int64_t o_sb, int64_t o_sh, int64_t o_ss, const void* mask, int64_t m_sb,
+                               int64_t m_sh, int64_t m_sq, const int* extent, float* workspace, int64_t B, int64_t H, int64_t KVH, int64_t M,
+                               int64_t Skv, int64_t nsplit, int64_t head_dim, float scale, hipStream_t stream) {
+  return attn_decode_run("llx_attn_decode", false, q, q_sb, q_sh, q_ss, k_cache, v_cache, c_sb, c_sh, c_ss, o, o_sb, o_sh, o_ss, mask, m_sb, m_sh, m_sq, extent,
+                         workspace, B, H, KVH, M, Skv, nsplit, head_dim, scale, stream);
+}
+
+// llx_attn_decode over FP8 caches: caches uint8 [B, KVH, Skv, 128] of E4M3 codes through BYTE strides (multiples of 8, the
+// pointers 16-byte aligned); everything else - the ROWS classes, the split plan, the mask, the partials, the combine launch and the
+// workspace - as llx_attn_decode, and so is the result: what llx_attn_decode computes on the caches' bf16 images.
+extern "C" int llx_attn_decode_f8(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, const void* k_cache, const void* v_cache, int64_t c_sb,
+                                  int64_t c_sh, int64_t c_ss, void* o, int64_t o_sb, int64_t o_sh, int64_t o_ss, const void* mask, int64_t m_sb,
+                                  int64_t m_sh, int64_t m_sq, const int* extent, float* workspace, int64_t B, int64_t H, int64_t KVH, int64_t M,
+                                  int64_t Skv, int64_t nsplit, int64_t head_dim, float scale, hipStream_t stream) {
+  return attn_decode_run("llx_attn_decode_f8", true, q, q_sb, q_sh, q_ss, k_cache, v_cache, c_sb, c_sh, c_ss, o, o_sb, o_sh, o_ss, mask, m_sb, m_sh, m_sq,
+                         extent, workspace, B, H, KVH, M, Skv, nsplit, head_dim, scale, stream);
 }

@@ -336,6 +336,7 @@ static int launch_rows16_epi(const char* fn, const rows16_args_t<AD>& a, int epi
     case GV_NONE: return launch_rows16<GV_NONE, WK, AD>(fn, a, grid, lds, stream);
     case GV_RESIDUAL: return launch_rows16<GV_RESIDUAL, WK, AD>(fn, a, grid, lds, stream);
     case GV_QKV: return launch_rows16<GV_QKV, WK, AD>(fn, a, grid, lds, stream);
+    case GV_QKV_F8: return launch_rows16<GV_QKV_F8, WK, AD>(fn, a, grid, lds, stream);
     default: return launch_rows16<GV_SWIGLU, WK, AD>(fn, a, grid, lds, stream);
   }
 }
@@ -434,7 +435,7 @@ static int rows16_run(const char* fn, int wk, const Rows16Lora* lo, const void* 
       ad = AD_DORA;
     }
   }
-  LLX_REQUIRE(epilogue != GV_QKV || (n_q > 0 && Smax > 0 && Smax < (1ll << 31) && c_sb % 4 == 0),
+  LLX_REQUIRE(!gv_is_qkv(epilogue) || (n_q > 0 && Smax > 0 && Smax < (1ll << 31) && c_sb % 4 == 0),
               "%s: the q|k|v epilogue needs q heads, a cache length below 2^31 and 8-byte aligned cache slots", fn);
   const Rows16Plan p = rows16_plan(M, a.N, K, epilogue, esz);
   LLX_REQUIRE(p.S == 1 || (workspace && (uintptr_t)workspace % 16 == 0 && workspace_bytes >= header + (int64_t)p.ntiles * p.S * 1024),

@@ -369,6 +369,7 @@ static int launch_mx4_m(const Mx4Args& a, int epi, int grid, size_t lds, hipStre
     case GV_NONE: return launch_mx4_n<MT, GV_NONE>(a, grid, lds, stream);
     case GV_RESIDUAL: return launch_mx4_n<MT, GV_RESIDUAL>(a, grid, lds, stream);
     case GV_QKV: return launch_mx4_n<MT, GV_QKV>(a, grid, lds, stream);
+    case GV_QKV_F8: return launch_mx4_n<MT, GV_QKV_F8>(a, grid, lds, stream);
     default: return launch_mx4_n<MT, GV_SWIGLU>(a, grid, lds, stream);
   }
 }

@@ -6,10 +6,13 @@
 // epilogue (one place where the roundings of the four epilogues live) and the host-side checks and fill of the operand block.
 #pragma once
 #include "common.h"  // HD
+#include "kv8.h"     // q() of the FP8 KV cache
 
 // epilogue 0: out [M, N] | 1: + res [M, N] | 2 (q|k|v): rows [0, n_q) RoPE -> out [M, n_q]; [n_q, n_q + n_k) RoPE -> k cache; rest ->
-// v cache | 3 (gate|up = W0|W1, N = 2 n_0): out [M, N/2] = silu(gate) * up
-enum { GV_NONE = 0, GV_RESIDUAL = 1, GV_QKV = 2, GV_SWIGLU = 3 };
+// v cache | 3 (gate|up = W0|W1, N = 2 n_0): out [M, N/2] = silu(gate) * up | 4: epilogue 2 into FP8 caches (uint8 E4M3 codes, DESIGN
+// 8.21; cache strides in bytes): the k / v branch stores q() of the bf16 values epilogue 2 would have stored, q rows are unchanged
+enum { GV_NONE = 0, GV_RESIDUAL = 1, GV_QKV = 2, GV_SWIGLU = 3, GV_QKV_F8 = 4 };
+static inline bool gv_is_qkv(int epilogue) { return epilogue == GV_QKV || epilogue == GV_QKV_F8; }
 // weight kind: bf16 | int8 rows x bf16 activations (weight-only) | int8 rows x int8 activations quantised in the prologue (dynamic)
 enum { WK_BF16 = 0, WK_I8W = 1, WK_I8D = 2 };
 
@@ -23,7 +26,8 @@ struct StreamArgs {
   bf16_t* out; int64_t ldo;                             // NONE / RESIDUAL: [M, N]; QKV: q rows [M, n_q]; SWIGLU: h [M, N / 2]
   const bf16_t* res; int64_t ldr;                       // RESIDUAL: [M, N]
   const float* rope; int n_q, n_k;                      // QKV: rows [0, n_q) = q heads, [n_q, n_q + n_k) = k heads, then v; table [.., 64, 2]
-  bf16_t* kc; bf16_t* vc; int64_t c_sh, c_ss;           //      caches [.., KVH, Smax, 128] through (head, position) strides
+  bf16_t* kc; bf16_t* vc; int64_t c_sh, c_ss;           //      caches [.., KVH, Smax, 128] through (head, position) strides (QKV_F8: uint8
+                                                        //      codes behind the same pointers, strides in bytes)
   const int64_t* pos;                                   //      the cache position of every activation row
 };
 
@@ -94,7 +98,7 @@ __device__ __forceinline__ void stream_epilogue(const StreamArgs& a, int row0, i
       const float sg = bf2f(f2bf(gg * sigmoidf_(gg)));
       if (row0 + j < half) a.out[(int64_t)m * a.ldo + row0 + j] = f2bf(sg * uu);
     }
-  } else if constexpr (EPI == GV_QKV) {
+  } else if constexpr (EPI == GV_QKV || EPI == GV_QKV_F8) {
     // apply_rope on q and k (modelling/llama.py:63-73,122-123), then KVCache.update (:83-90) for k and v
     const bool is_q = row0 < a.n_q, is_k = !is_q && row0 < a.n_q + a.n_k;
     const int hrow = is_q ? row0 : (is_k ? row0 - a.n_q : row0 - a.n_q - a.n_k);
@@ -116,7 +120,17 @@ __device__ __forceinline__ void stream_epilogue(const StreamArgs& a, int row0, i
       store(a.out + (int64_t)m * a.ldo + row0);
     } else {
       const int64_t off = kv_off();
-      if (off >= 0) store((is_k ? a.kc : a.vc) + (int64_t)(hrow >> 7) * a.c_sh + off + d);
+      if constexpr (EPI == GV_QKV_F8) {
+        // the FP8 cache: q() of the rounded values above (fp32 -> bf16 -> E4M3, the double rounding of the format's contract), one 4-byte
+        // (one pair: 2-byte) store at byte offsets
+        if (off >= 0) {
+          uint8_t* dst = reinterpret_cast<uint8_t*>(is_k ? a.kc : a.vc) + (int64_t)(hrow >> 7) * a.c_sh + off + d;
+          if constexpr (NV == 4) *reinterpret_cast<uint32_t*>(dst) = kv8_encode_bf4(pk[0], pk[1]);
+          else *reinterpret_cast<uint16_t*>(dst) = (uint16_t)kv8_encode2(bflo(pk[0]), bfhi(pk[0]));
+        }
+      } else {
+        if (off >= 0) store((is_k ? a.kc : a.vc) + (int64_t)(hrow >> 7) * a.c_sh + off + d);
+      }
     }
   } else {
 #pragma unroll
@@ -143,7 +157,7 @@ static inline int stream_check_fill(const char* fn, StreamArgs& a, int m_lo, int
   LLX_REQUIRE(w0 && x && out, "%s: null pointer", fn);
   LLX_REQUIRE(M >= m_lo && M <= m_hi, "%s: M=%lld outside %d..%d (%s)", fn, (long long)M, m_lo, m_hi, m_note);
   LLX_REQUIRE(K > 0 && K % epl == 0 && K <= 32768, "%s: K=%lld must be a multiple of %d and at most 32768", fn, (long long)K, epl);
-  LLX_REQUIRE(epilogue >= GV_NONE && epilogue <= GV_SWIGLU, "%s: unknown epilogue %d", fn, epilogue);
+  LLX_REQUIRE(epilogue >= GV_NONE && epilogue <= GV_QKV_F8, "%s: unknown epilogue %d", fn, epilogue);
   LLX_REQUIRE(n0 > 0 && n1 >= 0 && n2 >= 0 && (w1 || n1 == 0) && (w2 || n2 == 0) && (n1 > 0 || n2 == 0), "%s: bad segment sizes", fn);
   LLX_REQUIRE((n1 == 0 || n0 % seg_gran == 0) && (n2 == 0 || n1 % seg_gran == 0), "%s: inner segment sizes must be multiples of %d", fn, seg_gran);
   LLX_REQUIRE(ldw0 % epl == 0 && ldw1 % epl == 0 && ldw2 % epl == 0 && ldx % 8 == 0, "%s: row strides must be multiples of 16 bytes", fn);
@@ -152,9 +166,11 @@ static inline int stream_check_fill(const char* fn, StreamArgs& a, int m_lo, int
   LLX_REQUIRE(N < (1 << 30), "%s: too many rows", fn);
   LLX_REQUIRE(epilogue != GV_RESIDUAL || res, "%s: residual missing", fn);
   LLX_REQUIRE(epilogue != GV_SWIGLU || (n0 == n1 && n2 == 0 && w1), "%s: the SwiGLU epilogue takes gate and up weights of equal size", fn);
-  LLX_REQUIRE(epilogue != GV_QKV || (rope && k_cache && v_cache && pos && n_q % HD == 0 && n_k % HD == 0 && (N - n_q - n_k) % HD == 0 && n_q + n_k <= N &&
-                                     (uintptr_t)rope % 8 == 0 && ((uintptr_t)out | (uintptr_t)k_cache | (uintptr_t)v_cache) % 8 == 0 && ldo % 4 == 0 &&
-                                     c_sh % 4 == 0 && c_ss % 4 == 0),
+  // (epilogue 4: the caches hold one byte per element, so the same "4 elements" rule is 4-byte alignment of pointers and byte strides)
+  LLX_REQUIRE(!gv_is_qkv(epilogue) || (rope && k_cache && v_cache && pos && n_q % HD == 0 && n_k % HD == 0 && (N - n_q - n_k) % HD == 0 && n_q + n_k <= N &&
+                                       (uintptr_t)rope % 8 == 0 && (uintptr_t)out % 8 == 0 &&
+                                       ((uintptr_t)k_cache | (uintptr_t)v_cache) % (epilogue == GV_QKV_F8 ? 4 : 8) == 0 && ldo % 4 == 0 && c_sh % 4 == 0 &&
+                                       c_ss % 4 == 0),
               "%s: bad q|k|v epilogue arguments (the RoPE table, both caches and the positions; whole heads of 128; 8-byte aligned rows)", fn);
   a.W[0] = (const bf16_t*)w0; a.W[1] = (const bf16_t*)(w1 ? w1 : w0); a.W[2] = (const bf16_t*)(w2 ? w2 : w0);
   a.ldw[0] = ldw0; a.ldw[1] = w1 ? ldw1 : ldw0; a.ldw[2] = w2 ? ldw2 : ldw0;

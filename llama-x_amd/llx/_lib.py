@@ -48,6 +48,9 @@ SIGNATURES: dict[str, tuple] = {
     "llx_mask_extent":(c_int, [_P, _L, _L, _L, _P, _P]),
     "llx_kv_scatter": (c_int, [_P, _P, _L, _L, _L, _P, _P, _L, _L, _L, _P, _L, _L, _L, _L, _L, _P]),
     "llx_kv_scatter_rows": (c_int, [_P, _P, _L, _L, _L, _P, _P, _L, _L, _L, _P, _L, _L, _L, _L, _L, _L, _P]),
+    "llx_kv_scatter_f8": (c_int, [_P, _P, _L, _L, _L, _P, _P, _L, _L, _L, _P, _L, _L, _L, _L, _L, _P]),
+    "llx_kv_scatter_rows_f8": (c_int, [_P, _P, _L, _L, _L, _P, _P, _L, _L, _L, _P, _L, _L, _L, _L, _L, _L, _P]),
+    "llx_kv_dequantize_f8": (c_int, [_P, _L, _L, _L, _P, _L, _L, _L, _L, _P]),
     "llx_gemm_rows16_workspace_bytes": (c_int64, [_L, _L, _L, _I]),
     "llx_gemm_rows16_bf16": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _F, _I, _P, _L, _P, _L, _P, _L, _L, _P, _P, _L, _L, _L,
                                      _L, _P, _P, _L, _P]),
@@ -60,6 +63,7 @@ SIGNATURES: dict[str, tuple] = {
                                         _L, _P, _P, _L, _P, _P, _P, _P, _P, _P, _L, _L, _L, _P, _L, _F, _P]),
     "llx_attn_decode_workspace_bytes": (c_int64, [_L, _L, _L, _L]),
     "llx_attn_decode": (c_int, [_P, _L, _L, _L, _P, _P, _L, _L, _L, _P, _L, _L, _L, _P, _L, _L, _L, _P, _P, _L, _L, _L, _L, _L, _L, _L, _F, _P]),
+    "llx_attn_decode_f8": (c_int, [_P, _L, _L, _L, _P, _P, _L, _L, _L, _P, _L, _L, _L, _P, _L, _L, _L, _P, _P, _L, _L, _L, _L, _L, _L, _L, _F, _P]),
     "llx_attn_bwd_workspace_bytes": (c_int64, [_L, _L, _L, _L]),
     "llx_attn_bwd_ds_bytes": (c_int64, [_L, _L, _L]),
     "llx_attn_bwd": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _P, _P, _L, _L, _P, _L, _L, _P, _L, _L,

@@ -31,6 +31,9 @@ output row, rebuilt when weight, lora_a, lora_b or m change), so a token costs a
 of a LoRA model.  The factor is built at a linear's first use: prepare(model) builds them all up front, which a caller that
 captures a decode step into a graph must do (or run one warm-up step) before the capture - a tensor first allocated while
 capturing lives in the capture's private pool.  generate() calls prepare().
+An FP8 KV cache (build_cache(..., kv_dtype="fp8")) needs no route of its own here: the uint8 caches ride in the qkv
+tuple, K.gemv / K.gemm_rows16 pick the q|k|v epilogue that stores E4M3 codes and K.attn_decode reads them.  A decode step builds no
+bf16 image of such a cache (only prefill calls do), so nothing of it is allocated inside a captured step.
 """
 from __future__ import annotations
 

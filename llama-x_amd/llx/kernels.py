@@ -844,6 +844,17 @@ def attn_mask_bwd(q: Tensor, k: Tensor, v: Tensor, o: Tensor, do: Tensor, lse: T
 
 # ------------------------------------------------------------------------------------------------- decode path (csrc/decode.hip)
 GV_NONE, GV_RESIDUAL, GV_QKV, GV_SWIGLU = 0, 1, 2, 3  # csrc/wstream.h
+GV_QKV_F8 = 4  # GV_QKV into FP8 caches: callers ask for GV_QKV, the cache dtype picks it (_stream_operands)
+KV_DTYPES = ("bf16", "fp8")
+
+
+def _kv_fp8(k_cache: Tensor, v_cache: Tensor) -> bool:
+    """True for a pair of FP8 caches (uint8 E4M3 codes), False for a bf16 pair; anything else - a mixed pair too - is refused."""
+    if k_cache.dtype is torch.uint8 and v_cache.dtype is torch.uint8:
+        return True
+    if k_cache.dtype is BF16 and v_cache.dtype is BF16:
+        return False
+    raise L.LlxError(f"the k and v caches must both be bf16 or both uint8 (FP8 codes), got {k_cache.dtype} and {v_cache.dtype}")
 
 
 def _workspace(cache: dict, device, nbytes: int, floor: int = 0) -> Tensor:
@@ -858,7 +869,8 @@ def _workspace(cache: dict, device, nbytes: int, floor: int = 0) -> Tensor:
 def _stream_operands(ws, x: Tensor, norm, epilogue: int, out: Optional[Tensor], res: Optional[Tensor], qkv: Optional[tuple], batched: bool,
                      wcols: Optional[int] = None):
     """What gemv and gemm_rows16 share (the StreamArgs of csrc/wstream.h): the checks on the common operands, the output tensor and the
-    leading arguments of the C entry points, w0 .. v_cache.  Returns (arguments, out, N, k_cache, pos).  batched: the q|k|v mode of
+    leading arguments of the C entry points, w0 .. v_cache.  Returns (arguments, out, N, k_cache, pos).  GV_QKV with uint8 (FP8) caches
+    becomes epilogue 4: the caches' strides, which the callers append, are then bytes, as the entry points want them.  batched: the q|k|v mode of
     gemm_rows16 (table row 0 for every row, row m into cache[m]); else row m takes table row m and the cache has batch 1.  wcols: the
     stored columns of a weight row where they are not K (packed MXFP4 rows: K / 2 bytes)."""
     M, Kd = x.shape
@@ -879,6 +891,9 @@ def _stream_operands(ws, x: Tensor, norm, epilogue: int, out: Optional[Tensor], 
         assert rope.dtype is torch.float32 and rope.is_contiguous() and rope.shape[0] >= (1 if batched else M) and rope.shape[1:] == (64, 2)
         assert kc.shape == vc.shape and kc.dim() == 4 and kc.shape[3] == 128 and kc.stride() == vc.stride() and kc.stride(3) == 1
         assert kc.shape[0] >= M if batched else kc.shape[0] == 1
+        L.require_cuda(kc, vc)
+        if _kv_fp8(kc, vc):
+            epilogue = GV_QKV_F8
         assert pos.dtype is torch.int64 and pos.shape == (M,) and pos.is_contiguous() and pos.is_cuda
     if epilogue == GV_RESIDUAL:
         assert res is not None and res.shape == (M, N) and res.stride(1) == 1 and res.dtype is BF16
@@ -1084,20 +1099,38 @@ def mask_extent(mask: Tensor) -> Tensor:
 
 def kv_scatter(k: Tensor, v: Tensor, k_cache: Tensor, v_cache: Tensor, input_pos: Tensor) -> None:
     """k_cache[:, :, input_pos] = k ; v_cache[:, :, input_pos] = v  (KVCache.update, modelling/llama.py:83-90); k / v [B, KVH, L, 128] views.
-    input_pos [L], or [B, L]: sequence b at its own positions, cache[b, :, input_pos[b, l]] = k[b, :, l] (llx_kv_scatter_rows)."""
-    _chk_bf16(k, v, k_cache, v_cache)
-    L.require_cuda(input_pos)
+    input_pos [L], or [B, L]: sequence b at its own positions, cache[b, :, input_pos[b, l]] = k[b, :, l] (llx_kv_scatter_rows).
+    uint8 caches (FP8) take q(k), q(v): llx_kv_scatter_f8 / llx_kv_scatter_rows_f8."""
+    _chk_bf16(k, v)
+    L.require_cuda(input_pos, k_cache, v_cache)
+    f8 = "_f8" if _kv_fp8(k_cache, v_cache) else ""
     B, KVH, Lq, hd = k.shape
     assert v.shape == k.shape and k.stride() == v.stride() and k.stride(3) == 1 and k_cache.stride() == v_cache.stride() and k_cache.stride(3) == 1
     assert k_cache.shape[0] == B and k_cache.shape[1] == KVH and k_cache.shape[3] == hd and input_pos.shape in ((Lq,), (B, Lq))
     pos = input_pos.to(torch.int64).contiguous()
     if pos.dim() == 2:
-        L.check(_lib().llx_kv_scatter_rows(L.ptr(k), L.ptr(v), k.stride(0), k.stride(1), k.stride(2), L.ptr(k_cache), L.ptr(v_cache), k_cache.stride(0),
-                                           k_cache.stride(1), k_cache.stride(2), L.ptr(pos), pos.stride(0), B, KVH, Lq, k_cache.shape[2], hd,
-                                           L.stream()), "llx_kv_scatter_rows")
+        fn = "llx_kv_scatter_rows" + f8
+        L.check(getattr(_lib(), fn)(L.ptr(k), L.ptr(v), k.stride(0), k.stride(1), k.stride(2), L.ptr(k_cache), L.ptr(v_cache), k_cache.stride(0),
+                                    k_cache.stride(1), k_cache.stride(2), L.ptr(pos), pos.stride(0), B, KVH, Lq, k_cache.shape[2], hd, L.stream()), fn)
         return
-    L.check(_lib().llx_kv_scatter(L.ptr(k), L.ptr(v), k.stride(0), k.stride(1), k.stride(2), L.ptr(k_cache), L.ptr(v_cache), k_cache.stride(0),
-                                  k_cache.stride(1), k_cache.stride(2), L.ptr(pos), B, KVH, Lq, k_cache.shape[2], hd, L.stream()), "llx_kv_scatter")
+    fn = "llx_kv_scatter" + f8
+    L.check(getattr(_lib(), fn)(L.ptr(k), L.ptr(v), k.stride(0), k.stride(1), k.stride(2), L.ptr(k_cache), L.ptr(v_cache), k_cache.stride(0),
+                                k_cache.stride(1), k_cache.stride(2), L.ptr(pos), B, KVH, Lq, k_cache.shape[2], hd, L.stream()), fn)
+
+
+def kv_dequantize(cache: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """The bf16 image dq(cache) of an FP8 cache (uint8 [B, KVH, S, 128], any batch / head / position strides; exact): contiguous
+    [B, KVH, S, 128] (llx_kv_dequantize_f8)."""
+    L.require_cuda(cache)
+    if cache.dtype is not torch.uint8 or cache.dim() != 4 or cache.stride(3) != 1:
+        raise L.LlxError("kv_dequantize: an FP8 cache is a uint8 [B, KVH, S, 128] tensor with a dense last dim")
+    B, KVH, S, hd = cache.shape
+    if out is None:
+        out = torch.empty(B, KVH, S, hd, device=cache.device, dtype=BF16)
+    assert out.shape == cache.shape and out.dtype is BF16 and out.is_contiguous()
+    L.check(_lib().llx_kv_dequantize_f8(L.ptr(cache), cache.stride(0), cache.stride(1), cache.stride(2), L.ptr(out), B, KVH, S, hd, L.stream()),
+            "llx_kv_dequantize_f8")
+    return out
 
 
 _DECODE_WS: dict = {}
@@ -1112,9 +1145,11 @@ def _decode_nsplit(B: int, KVH: int, Skv: int) -> int:
 
 def attn_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, mask: Tensor, extent: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
     """SDPA over the cache for a few query tokens: q [B, H, M, 128] (any strides, last dim dense), caches [B, KVH, Skv, 128], bool mask
-    broadcastable to [B, H, M, Skv] -> o [B, H, M, 128] stored as [B, M, H*128] (the layout wo reads).  M * H / KVH <= 16."""
-    _chk_bf16(q, k_cache, v_cache)
-    L.require_cuda(mask)
+    broadcastable to [B, H, M, Skv] -> o [B, H, M, 128] stored as [B, M, H*128] (the layout wo reads).  M * H / KVH <= 16.
+    uint8 caches (FP8) are read as codes (llx_attn_decode_f8): the result of this call on their bf16 images."""
+    _chk_bf16(q)
+    L.require_cuda(mask, k_cache, v_cache)
+    fn = "llx_attn_decode_f8" if _kv_fp8(k_cache, v_cache) else "llx_attn_decode"
     B, H, M, hd = q.shape
     KVH, Skv = k_cache.shape[1], k_cache.shape[2]
     norm = _mask_norm(mask, B, M, Skv, H)
@@ -1126,9 +1161,9 @@ def attn_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, mask: Tensor, exten
     if out is None:
         out = torch.empty(B, M, H * hd, device=q.device, dtype=BF16)
     o4 = out.view(B, M, H, hd)
-    L.check(_lib().llx_attn_decode(L.ptr(q), q.stride(0), q.stride(1), q.stride(2), L.ptr(k_cache), L.ptr(v_cache), k_cache.stride(0), k_cache.stride(1),
-                                   k_cache.stride(2), L.ptr(out), o4.stride(0), o4.stride(2), o4.stride(1), L.ptr(m), m_sb, m_sh, m.stride(2), L.ptr(extent),
-                                   L.ptr(ws), B, H, KVH, M, Skv, nsplit, hd, 1.0 / math.sqrt(hd), L.stream()), "llx_attn_decode")
+    L.check(getattr(_lib(), fn)(L.ptr(q), q.stride(0), q.stride(1), q.stride(2), L.ptr(k_cache), L.ptr(v_cache), k_cache.stride(0), k_cache.stride(1),
+                                k_cache.stride(2), L.ptr(out), o4.stride(0), o4.stride(2), o4.stride(1), L.ptr(m), m_sb, m_sh, m.stride(2), L.ptr(extent),
+                                L.ptr(ws), B, H, KVH, M, Skv, nsplit, hd, 1.0 / math.sqrt(hd), L.stream()), fn)
     return out
 
 
@@ -1280,8 +1315,16 @@ def beam_merge(cand_score: Tensor, cand_token: Tensor, s: Tensor, parent: Tensor
 def kv_cache_table(caches) -> Tensor:
     """The device table of base pointers that kv_reorder_rows takes, for `caches` (bf16 [B, KVH, Smax, 128] tensors of one shape and one
     set of strides, 16-byte aligned: every layer's k and v cache).  Build it once per generate() call; the table keeps the caches' shape
-    and strides and references to them."""
+    and strides and references to them.
+    FP8 caches (uint8 [B, KVH, Smax, 128], Smax even, contiguous) are addressed as bf16 [B, KVH, Smax / 2, 128]: two positions per
+    256-byte row, so llx_kv_reorder_rows moves them unchanged (table.fp8 tells kv_reorder_rows to halve the length)."""
     caches = list(caches)
+    fp8 = caches[0].dtype is torch.uint8
+    if fp8:
+        for c in caches:
+            if c.dtype is not torch.uint8 or c.dim() != 4 or c.shape[3] != 128 or c.shape[2] % 2 or not c.is_contiguous():
+                raise L.LlxError("kv_cache_table: FP8 caches must be contiguous uint8 [B, KVH, Smax, 128] tensors with an even Smax")
+        caches = [c.view(BF16).view(c.shape[0], c.shape[1], c.shape[2] // 2, 128) for c in caches]
     c0 = caches[0]
     for c in caches:
         L.require_cuda(c)
@@ -1290,6 +1333,7 @@ def kv_cache_table(caches) -> Tensor:
                              "16-byte aligned, last dim dense")
     table = torch.tensor([c.data_ptr() for c in caches], dtype=torch.int64).to(c0.device)
     table.caches = caches
+    table.fp8 = fp8
     return table
 
 
@@ -1297,12 +1341,17 @@ def kv_reorder_rows(table: Tensor, parent: Tensor, length: int) -> None:
     """cache[b, :, :length] <- cache[parent[b], :, :length] for b < W = len(parent) (device int32, 2..16) in place, in every cache of
     `table` (kv_cache_table), in one launch.  A thread owns one 16-byte chunk of (head, position) in all W slots, loads the ones that
     move and then stores them, so no slot is read after it was overwritten.  Slots with parent[b] == b, positions >= length and slots
-    >= W are not written."""
+    >= W are not written.
+    A table of FP8 caches moves ceil(length / 2) rows of two positions: when `length` is odd the position at index `length` is copied
+    along.  That position holds nothing a mask allows yet - the next step's q|k|v epilogue writes it in every slot before any mask
+    does - so the extra copy cannot be observed."""
     L.require_cuda(table, parent)
     c0 = table.caches[0]
     if parent.dtype is not torch.int32 or parent.dim() != 1 or not parent.is_contiguous() or parent.numel() > c0.shape[0]:
         raise L.LlxError(f"kv_reorder_rows: parent must be a contiguous device int32 [W] with W <= the caches' batch {c0.shape[0]} "
                          f"(got {parent.dtype} {tuple(parent.shape)})")
+    if getattr(table, "fp8", False):
+        length = (int(length) + 1) // 2
     L.check(_lib().llx_kv_reorder_rows(L.ptr(table), table.numel(), c0.stride(0), c0.stride(1), c0.stride(2), L.ptr(parent), parent.numel(),
                                        c0.shape[1], int(length), c0.shape[2], c0.shape[3], L.stream()), "llx_kv_reorder_rows")
 

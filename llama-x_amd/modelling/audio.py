@@ -40,8 +40,8 @@ class LlamaAudio(Llama):
             nn.GELU(),
         )
 
-    def build_cache(self, inference: bool = False, batch_size: int = 1):
-        super().build_cache(inference, batch_size)
+    def build_cache(self, inference: bool = False, batch_size: int = 1, kv_dtype: str = "bf16"):
+        super().build_cache(inference, batch_size, kv_dtype)
         self.melspec = audio_ops.MelSpectrogram(**self.audio_config._asdict(), norm="slaney", mel_scale="slaney")
 
     def audio_positions(self, samples: int) -> int:

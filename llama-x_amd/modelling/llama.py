@@ -118,16 +118,50 @@ class Embedding(nn.Embedding):
         return _EmbeddingFn.apply(ids, self.weight)
 
 
+def check_kv_dtype(kv_dtype, config: LlamaConfig) -> None:
+    """What build_cache refuses before it allocates: an unknown kv_dtype; for "fp8" a head_dim other than 128 or an odd max_seq_len."""
+    if kv_dtype not in K.KV_DTYPES:
+        raise LlxError(f"build_cache: kv_dtype={kv_dtype!r} must be one of {K.KV_DTYPES}")
+    if kv_dtype == "fp8" and config.head_dim != 128:
+        raise LlxError(f"build_cache: kv_dtype='fp8' needs head_dim 128 (got {config.head_dim})")
+    if kv_dtype == "fp8" and config.max_seq_len % 2 != 0:
+        raise LlxError(f"build_cache: kv_dtype='fp8' needs an even max_seq_len (got {config.max_seq_len}): beams move two positions per 256-byte row")
+
+
 class KVCache(nn.Module):
-    def __init__(self, batch_size: int, config: LlamaConfig, dtype: torch.dtype):
+    """kv_dtype "bf16": the reference's cache in `dtype`.  "fp8": uint8 buffers of OCP E4M3 codes without a scale - uint8,
+    not torch.float8_e4m3fn, so that module.to(dtype) cannot cast them; the cache behaves as a bf16 cache that holds dq(q(x)) wherever
+    that one holds x.  Device only: there is no CPU path."""
+
+    def __init__(self, batch_size: int, config: LlamaConfig, dtype: torch.dtype, kv_dtype: str = "bf16"):
         super().__init__()
+        check_kv_dtype(kv_dtype, config)
+        self.kv_dtype = kv_dtype
         shape = (batch_size, config.num_kv_heads, config.max_seq_len, config.head_dim)
+        if kv_dtype == "fp8":
+            dtype = torch.uint8  # code 0x00 = +0
         self.register_buffer("k_cache", torch.zeros(shape, dtype=dtype), persistent=False)
         self.register_buffer("v_cache", torch.zeros(shape, dtype=dtype), persistent=False)
+
+    def dequantize(self) -> tuple[Tensor, Tensor]:
+        """The bf16 images (dq(k_cache), dq(v_cache)) of an fp8 cache: built for the call, never kept (tests and the prefill branch)."""
+        if self.kv_dtype != "fp8":
+            raise LlxError("KVCache.dequantize: a bf16 cache has no codes to dequantise")
+        return K.kv_dequantize(self.k_cache), K.kv_dequantize(self.v_cache)
 
     def update(self, input_pos: Tensor, k: Tensor, v: Tensor):
         # input_pos: [S], or [B, S] (sequence b at its own positions); k/v: [B, KVH, S, hd]
         assert input_pos.shape[-1] == k.shape[2], (input_pos.shape, k.shape)
+        if self.kv_dtype == "fp8":  # q(k), q(v) into the codes; returns the code tensors
+            if not (k.is_cuda and self.k_cache.is_cuda):
+                raise LlxError("an fp8 KV cache runs on the HIP device only; there is no CPU path")
+            if not (k.dtype is torch.bfloat16 and k.shape[0] == self.k_cache.shape[0] and k.stride(3) == 1 and v.stride(3) == 1):
+                raise LlxError(f"an fp8 KV cache takes bf16 k / v [B = {self.k_cache.shape[0]}, KVH, S, 128] with a dense last dim "
+                               f"(got {k.dtype} {tuple(k.shape)})")
+            if k.stride() != v.stride():
+                k, v = k.contiguous(), v.contiguous()
+            K.kv_scatter(k, v, self.k_cache, self.v_cache, input_pos)
+            return self.k_cache, self.v_cache
         if k.is_cuda and k.dtype is torch.bfloat16 and k.shape[0] == self.k_cache.shape[0] and k.stride() == v.stride() and k.stride(3) == 1:
             K.kv_scatter(k, v, self.k_cache, self.v_cache, input_pos)  # both caches from one HIP launch, straight from the q|k|v buffer's views
         elif input_pos.dim() == 2:
@@ -242,7 +276,12 @@ class Attention(nn.Module):
             k, v = self.kv_cache.update(input_pos, k, v)
         if mask is None:  # no cache, no mask cannot reach here; a cache without mask attends to everything cached
             mask = torch.ones(L_, k.shape[2], dtype=torch.bool, device=x.device)
-        if L_ * (H // KVH) <= 16 and k.stride() == v.stride():  # a few query tokens over a long cache: split-cache decode kernel
+        decode = L_ * (H // KVH) <= 16 and k.stride() == v.stride()
+        if k.dtype is torch.uint8 and not decode:
+            # an fp8 cache past the decode branch (which reads the codes): the existing kernels on a transient bf16 image of the cache,
+            # dequantised for this call and dropped after it (two launches per layer; tools/decode_kv8_bench.py times them)
+            k, v = self.kv_cache.dequantize()
+        if decode:  # a few query tokens over a long cache: split-cache decode kernel
             o2 = K.attn_decode(q, k, v, mask, D.mask_extent(mask)).view(B * L_, H * hd)
         elif K.attn_mask_routable(mask, B, L_, k.shape[2]):
             # prefill / explicit mask broadcast over heads: the MFMA tile loop driven by the mask bytes, o written as rows.  No range of small
@@ -315,15 +354,17 @@ class Llama(nn.Module):
         self.output = Linear(config.embed_dim, config.vocab_size, bias=False)
         self.config = config
 
-    def build_cache(self, inference: bool = False, batch_size: int = 1):
+    def build_cache(self, inference: bool = False, batch_size: int = 1, kv_dtype: str = "bf16"):
         """The RoPE table and, for inference, a KV cache of `batch_size` sequences per layer (the reference's KVCache, update() and
-        Attention.forward are written for a batch; only its build_cache fixes the batch at 1)."""
+        Attention.forward are written for a batch; only its build_cache fixes the batch at 1).  kv_dtype="fp8": caches of E4M3 codes,
+        half the bytes (KVCache); refused, before anything is allocated, for head_dim != 128 or an odd max_seq_len."""
+        check_kv_dtype(kv_dtype, self.config)
         self.register_buffer("rope", build_rope(self.config), persistent=False)
         if inference:
             if not (isinstance(batch_size, int) and batch_size >= 1):
                 raise LlxError(f"build_cache: batch_size={batch_size!r} must be an integer >= 1")
             for layer in self.layers:
-                layer.attention.kv_cache = KVCache(batch_size, self.config, self.tok_embeddings.weight.dtype)
+                layer.attention.kv_cache = KVCache(batch_size, self.config, self.tok_embeddings.weight.dtype, kv_dtype)
             L = self.config.max_seq_len
             self.register_buffer("causal_mask", torch.tril(torch.ones(L, L, dtype=torch.bool)), persistent=False)
 
