@@ -57,7 +57,7 @@ __device__ __forceinline__ int wave_sum_valu_i(int v) {
 // WK_I8D keeps x as int8 (after the optional norm each row is quantised here, the row scales stay in registers).
 // DORA (bf16 rows): a.wscale holds DoRA's per-row factors.  A build of its own, not a test of the pointer: the test cost the existing
 // instances 2-7 SGPRs and the 4-token q|k|v instance four more spilled registers.
-template <int MT, int EPI, bool NORM, int RPW = 4, int WK = WK_BF16, bool DORA = false>
+template <int MT, int EPI, bool NORM, int RPW = 2, int WK = WK_BF16, bool DORA = false>
 __global__ __launch_bounds__(256, 2) void gemv_kernel(const GemvArgs a) {
   static_assert(!DORA || WK == WK_BF16, "DoRA factors ride on bf16 rows only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -339,35 +339,26 @@ __global__ __launch_bounds__(256, 2) void gemv_kernel(const GemvArgs a) {
   }
 }
 
-template <int MT, int EPI, int RPW, int WK, bool DORA>
-static int launch_gemv_n(const char* fn, const GemvArgs& a, int grid, size_t lds, hipStream_t stream) {
-  if (a.norm_w) hipLaunchKernelGGL((gemv_kernel<MT, EPI, true, RPW, WK, DORA>), dim3(grid), dim3(256), lds, stream, a);
-  else hipLaunchKernelGGL((gemv_kernel<MT, EPI, false, RPW, WK, DORA>), dim3(grid), dim3(256), lds, stream, a);
-  LLX_LAUNCH_CHECK(fn);
-  return LLX_OK;
-}
-
-template <int MT, int RPW, int WK, bool DORA>
-static int launch_gemv_m(const char* fn, const GemvArgs& a, int epi, int grid, size_t lds, hipStream_t stream) {
-  switch (epi) {
-    case GV_NONE: return launch_gemv_n<MT, GV_NONE, RPW, WK, DORA>(fn, a, grid, lds, stream);
-    case GV_RESIDUAL: return launch_gemv_n<MT, GV_RESIDUAL, RPW, WK, DORA>(fn, a, grid, lds, stream);
-    case GV_QKV: return launch_gemv_n<MT, GV_QKV, RPW, WK, DORA>(fn, a, grid, lds, stream);
-    case GV_QKV_F8: return launch_gemv_n<MT, GV_QKV_F8, RPW, WK, DORA>(fn, a, grid, lds, stream);
-    default: return launch_gemv_n<MT, GV_SWIGLU, RPW, WK, DORA>(fn, a, grid, lds, stream);
-  }
-}
-
-template <int RPW, int WK, bool DORA = false>
-static int launch_gemv_mt(const char* fn, const GemvArgs& a, int MT, int epi, int grid, size_t lds, hipStream_t stream) {
+// the instance of one pass: MT = 1 | 2 | 4 staged rows of x, two output rows per wave
+template <int WK, bool DORA = false>
+static int launch_gemv(const char* fn, const GemvArgs& a, int MT, int epi, int grid, size_t lds, hipStream_t stream) {
+  auto go = [&](auto mt) {
+    return stream_with_epilogue(epi, [&](auto e) {
+      constexpr int MT_ = decltype(mt)::value, EPI = decltype(e)::value;
+      if (a.norm_w) hipLaunchKernelGGL((gemv_kernel<MT_, EPI, true, 2, WK, DORA>), dim3(grid), dim3(256), lds, stream, a);
+      else hipLaunchKernelGGL((gemv_kernel<MT_, EPI, false, 2, WK, DORA>), dim3(grid), dim3(256), lds, stream, a);
+      LLX_LAUNCH_CHECK(fn);
+      return LLX_OK;
+    });
+  };
   switch (MT) {
-    case 1: return launch_gemv_m<1, RPW, WK, DORA>(fn, a, epi, grid, lds, stream);
-    case 2: return launch_gemv_m<2, RPW, WK, DORA>(fn, a, epi, grid, lds, stream);
+    case 1: return go(std::integral_constant<int, 1>{});
+    case 2: return go(std::integral_constant<int, 2>{});
     default:
       // (weight-only int8 has no 4-token build: 16 fp32 activations per lane and token next to the two weight register sets do not fit
       // the 256 registers of two workgroups per CU without scratch; its callers run 3 and 4 tokens as two passes of the 2-token build)
       if constexpr (WK == WK_I8W) { llx_set_error("llx_gemv_i8: no 4-token build of the weight-only kind"); return LLX_ERR_UNSUPPORTED; }
-      else return launch_gemv_m<4, RPW, WK, DORA>(fn, a, epi, grid, lds, stream);
+      else return go(std::integral_constant<int, 4>{});
   }
 }
 
@@ -377,73 +368,38 @@ static int launch_gemv_mt(const char* fn, const GemvArgs& a, int MT, int epi, in
 // The epilogues are wstream.h's; q|k|v rotates row m by table row m and writes its k / v heads at input_pos[m] (device int64), caches
 // through (head, position) strides.  LoRA (nullable bext_s [n_s, rank_s], t [M, sum rank] bf16 = x . A^T, offsets t_off_s, scale):
 // out += scale * t_s . bext_s[row].
-// the three entry points below: fn = the caller's name for messages, wk = weight kind, ws_s = per-row scales of W_s (int8 kinds) or
-// DoRA's per-row factors (bf16 rows with dora set: every present segment has one)
-static int gemv_run(const char* fn, int wk, bool dora, const void* ws0, const void* ws1, const void* ws2, const void* w0, int64_t ldw0, int64_t n0, const void* w1, int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2,
-                             int64_t n2, const void* x, int64_t ldx, int64_t M, int64_t K, const void* norm_w, float eps, int epilogue,
-                             void* out, int64_t ldo, const void* res, int64_t ldr, const float* rope, int64_t n_q, int64_t n_k, void* k_cache,
-                             void* v_cache, int64_t c_sh, int64_t c_ss, const int64_t* input_pos, const void* bext0, const void* bext1,
-                             const void* bext2, int64_t rank0, int64_t rank1, int64_t rank2, const void* t, int64_t ldt, float lora_scale,
-                    hipStream_t stream) {
+// the three entry points below: fn = the caller's name for messages, wk = weight kind, scales = per-row scales of W_s (int8 kinds) or
+// DoRA's per-row factors (bf16 rows with dora set: every present segment has one), null for plain bf16 rows
+static int gemv_run(const char* fn, int wk, bool dora, const void* const* scales, const StreamCall& c, const StreamLora& lo, hipStream_t stream) {
   const int wa = wk == WK_BF16 ? 8 : 16;  // weight elements per 16-byte lane load
   GemvArgs a;
   // (inner segments in multiples of 4 rows keep a row group inside one weight; SwiGLU pairs gate row i with up row i whatever their count)
-  const int rc0 = stream_check_fill(fn, a, 1, 4, "larger row counts run the MFMA GEMM", wa, epilogue == GV_SWIGLU ? 1 : 4, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps,
-                                    epilogue, out, ldo, res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sh, c_ss, input_pos);
+  const int rc0 = stream_check_fill(fn, a, 1, 4, "larger row counts run the MFMA GEMM", wa, c.epilogue == GV_SWIGLU ? 1 : 4, c);
   if (rc0 != LLX_OK) return rc0;
   if (wk != WK_BF16 || dora) {
-    const int rc1 = stream_check_fill_scales(fn, a, dora ? "DoRA" : "int8", ws0, ws1, ws2, n1, n2);
+    const int rc1 = stream_check_fill_scales(fn, a, dora ? "DoRA" : "int8", c, scales);
     if (rc1 != LLX_OK) return rc1;
   }
-  const int rc2 = gemv_check_fill_lora(fn, a, n1, bext0, bext1, bext2, rank0, rank1, rank2, t, ldt, lora_scale);
+  const int rc2 = gemv_check_fill_lora(fn, a, c, lo);
   if (rc2 != LLX_OK) return rc2;
-  const int64_t N = a.N;
   // rows per wave: 2 (steps of 2048 elements per row: half the dependent steps of the 4-row form on every product of the decode step and
-  // twice the waves where N <= 4096 would fill only half of the 2048 slots: 3.51 -> 3.39 ms per token; one row per wave: 3.43);
-  // LLX_GEMV_RPW=4: the 4-row form
-  static const int rpw_knob = [] { const char* e = getenv("LLX_GEMV_RPW"); return e ? atoi(e) : 0; }();
+  // twice the waves where N <= 4096 would fill only half of the 2048 slots: 3.39 ms per token against the 4-row form's 3.51 and 3.43 with
+  // one row per wave).
   // int8 rows: 2 as well (steps of 4 pieces = 4096 elements per row, so a K = 4096 row is one step and K = 14336 pads its last step
   // by two pieces; the 4-row form with steps of 2048 elements, which tile both K exactly, was measured next to it on the 8B decode
   // step: 2.64 / 2.81 ms per token (weight-only / dynamic, context 4096) against 2.54 / 2.71 with 2 rows - the wider grid of the
   // N = 4096 and 6144 products decides, as for bf16).  Only the 2-row form is built.
-  const int rpw = wk == WK_BF16 ? (rpw_knob == 4 ? 4 : 2) : 2;
-  const int64_t groups = epilogue == GV_SWIGLU ? (N / 2 + rpw / 2 - 1) / (rpw / 2) : (N + rpw - 1) / rpw;
-  // the wave count is trimmed so that every wave gets the same number of row groups where possible
-  constexpr int wave_cap = 2048;
-  const int64_t per_wave = cdiv64(groups, wave_cap);
-  const int grid = (int)cdiv64(cdiv64(groups, per_wave), 4);
-  const int64_t kstep = 64 * wa * (8 / rpw);
-  const int64_t xb = wk == WK_I8D ? 1 : 2;  // bytes per staged activation element
-  const int64_t Kp = wk == WK_BF16 ? cdiv64(K, kstep) * kstep : (cdiv64(K, 64 * wa) + 1) * 64 * wa;  // the kernel's LDS row length
-  // the build for m rows stages MT = 1 | 2 | 4 rows of x in LDS; above 64 KiB the rows go in pairs (two passes over the weights)
-  auto run = [&](int m0, int mc) -> int {
-    GemvArgs b = a;
-    b.M = mc;
-    b.x = a.x + (int64_t)m0 * a.ldx;
-    b.out = a.out + (int64_t)m0 * a.ldo;
-    if (a.res) b.res = a.res + (int64_t)m0 * a.ldr;
-    if (a.rope) b.rope = a.rope + (int64_t)m0 * 128;
-    if (a.pos) b.pos = a.pos + m0;
-    if (a.t) b.t = a.t + (int64_t)m0 * a.ldt;
-    const int MT = mc == 1 ? 1 : (mc == 2 ? 2 : 4);
-    const size_t lds = (size_t)MT * Kp * xb + 64;
-    if (wk == WK_I8W) return launch_gemv_mt<2, WK_I8W>(fn, b, MT, epilogue, grid, lds, stream);
-    if (wk == WK_I8D) return launch_gemv_mt<2, WK_I8D>(fn, b, MT, epilogue, grid, lds, stream);
-    if (dora) return rpw == 2 ? launch_gemv_mt<2, WK_BF16, true>(fn, b, MT, epilogue, grid, lds, stream) : launch_gemv_mt<4, WK_BF16, true>(fn, b, MT, epilogue, grid, lds, stream);
-    return rpw == 2 ? launch_gemv_mt<2, WK_BF16>(fn, b, MT, epilogue, grid, lds, stream) : launch_gemv_mt<4, WK_BF16>(fn, b, MT, epilogue, grid, lds, stream);
-  };
-  // tokens per pass: all of them where their LDS stage fits, else pairs, else one (each pass streams the weights again); the
-  // weight-only int8 kind has no 4-token build
-  auto fits = [&](int64_t mt) { return mt * Kp * xb + 64 <= 64 * 1024; };
-  int per_pass = M > 2 ? 4 : (int)M;
-  if (per_pass == 4 && (wk == WK_I8W || !fits(4))) per_pass = 2;
-  if (per_pass == 2 && !fits(2)) per_pass = 1;
-  LLX_REQUIRE(fits(per_pass), "%s: K too large for the LDS stage", fn);
-  for (int m0 = 0; m0 < (int)M; m0 += per_pass) {
-    const int rc = run(m0, (int)M - m0 < per_pass ? (int)M - m0 : per_pass);
-    if (rc != LLX_OK) return rc;
-  }
-  return LLX_OK;
+  constexpr int rpw = 2;
+  const int grid = gemv_grid(a.N, c.epilogue, rpw);
+  const int64_t piece = 64 * wa, kstep = piece * (8 / rpw);
+  const int64_t Kp = wk == WK_BF16 ? cdiv64(c.K, kstep) * kstep : (cdiv64(c.K, piece) + 1) * piece;  // the kernel's LDS row length
+  // (the weight-only int8 kind has no 4-token build; the dynamic kind stages int8 codes, one byte per element)
+  return gemv_passes(fn, a, wk == WK_I8W ? 2 : 4, Kp, wk == WK_I8D ? 1 : 2, [&](const GemvArgs& b, int MT, size_t lds) {
+    if (wk == WK_I8W) return launch_gemv<WK_I8W>(fn, b, MT, c.epilogue, grid, lds, stream);
+    if (wk == WK_I8D) return launch_gemv<WK_I8D>(fn, b, MT, c.epilogue, grid, lds, stream);
+    if (dora) return launch_gemv<WK_BF16, true>(fn, b, MT, c.epilogue, grid, lds, stream);
+    return launch_gemv<WK_BF16>(fn, b, MT, c.epilogue, grid, lds, stream);
+  });
 }
 
 extern "C" int llx_gemv_bf16(const void* w0, int64_t ldw0, int64_t n0, const void* w1, int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2,
@@ -452,8 +408,10 @@ extern "C" int llx_gemv_bf16(const void* w0, int64_t ldw0, int64_t n0, const voi
                              void* v_cache, int64_t c_sh, int64_t c_ss, const int64_t* input_pos, const void* bext0, const void* bext1,
                              const void* bext2, int64_t rank0, int64_t rank1, int64_t rank2, const void* t, int64_t ldt, float lora_scale,
                              hipStream_t stream) {
-  return gemv_run("llx_gemv_bf16", WK_BF16, false, nullptr, nullptr, nullptr, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue, out, ldo, res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sh,
-                  c_ss, input_pos, bext0, bext1, bext2, rank0, rank1, rank2, t, ldt, lora_scale, stream);
+  const StreamCall c = {{w0, w1, w2}, {ldw0, ldw1, ldw2}, {n0, n1, n2}, x, ldx, M, K, norm_w, eps, epilogue, out, ldo, res, ldr,
+                        rope, n_q, n_k, k_cache, v_cache, 0, c_sh, c_ss, 0, input_pos};
+  const StreamLora lo = {{bext0, bext1, bext2}, {rank0, rank1, rank2}, t, ldt, lora_scale, {}};
+  return gemv_run("llx_gemv_bf16", WK_BF16, false, nullptr, c, lo, stream);
 }
 
 // llx_gemv_bf16 on DoRA linears (modelling/lora.py:51-59) with the row factor c_s = m / ||W_s + s B_s A_s||_row cached by the caller
@@ -465,8 +423,10 @@ extern "C" int llx_gemv_bf16_dora(const void* w0, int64_t ldw0, int64_t n0, cons
                                   void* v_cache, int64_t c_sh, int64_t c_ss, const int64_t* input_pos, const void* bext0, const void* bext1,
                                   const void* bext2, int64_t rank0, int64_t rank1, int64_t rank2, const void* t, int64_t ldt, float lora_scale,
                                   const void* colscale0, const void* colscale1, const void* colscale2, hipStream_t stream) {
-  return gemv_run("llx_gemv_bf16_dora", WK_BF16, true, colscale0, colscale1, colscale2, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue, out, ldo, res, ldr, rope, n_q, n_k,
-                  k_cache, v_cache, c_sh, c_ss, input_pos, bext0, bext1, bext2, rank0, rank1, rank2, t, ldt, lora_scale, stream);
+  const StreamCall c = {{w0, w1, w2}, {ldw0, ldw1, ldw2}, {n0, n1, n2}, x, ldx, M, K, norm_w, eps, epilogue, out, ldo, res, ldr,
+                        rope, n_q, n_k, k_cache, v_cache, 0, c_sh, c_ss, 0, input_pos};
+  const StreamLora lo = {{bext0, bext1, bext2}, {rank0, rank1, rank2}, t, ldt, lora_scale, {colscale0, colscale1, colscale2}};
+  return gemv_run("llx_gemv_bf16_dora", WK_BF16, true, lo.colscale, c, lo, stream);
 }
 
 // The same product on int8 weight rows (subclasses/int8.py:106-121): W_s [n_s, K] int8 row-major (ldw_s in bytes, multiples of 16),
@@ -481,8 +441,11 @@ extern "C" int llx_gemv_i8(const void* w0, int64_t ldw0, int64_t n0, const void*
                            void* v_cache, int64_t c_sh, int64_t c_ss, const int64_t* input_pos, const void* bext0, const void* bext1,
                            const void* bext2, int64_t rank0, int64_t rank1, int64_t rank2, const void* t, int64_t ldt, float lora_scale,
                            const void* scale0, const void* scale1, const void* scale2, int dynamic, hipStream_t stream) {
-  return gemv_run("llx_gemv_i8", dynamic ? WK_I8D : WK_I8W, false, scale0, scale1, scale2, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue, out, ldo, res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sh,
-                  c_ss, input_pos, bext0, bext1, bext2, rank0, rank1, rank2, t, ldt, lora_scale, stream);
+  const StreamCall c = {{w0, w1, w2}, {ldw0, ldw1, ldw2}, {n0, n1, n2}, x, ldx, M, K, norm_w, eps, epilogue, out, ldo, res, ldr,
+                        rope, n_q, n_k, k_cache, v_cache, 0, c_sh, c_ss, 0, input_pos};
+  const StreamLora lo = {{bext0, bext1, bext2}, {rank0, rank1, rank2}, t, ldt, lora_scale, {}};
+  const void* const scales[3] = {scale0, scale1, scale2};
+  return gemv_run("llx_gemv_i8", dynamic ? WK_I8D : WK_I8W, false, scales, c, lo, stream);
 }
 
 // ------------------------------------------------------------------------------------------------- mask extent / cache scatter

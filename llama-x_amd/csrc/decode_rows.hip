@@ -316,29 +316,21 @@ __global__ __launch_bounds__(256) void rows16_combine_kernel(const rows16_args_t
 }
 
 // fn = the entry point's name for messages
-template <int EPI, int WK, int AD>
-static int launch_rows16(const char* fn, const rows16_args_t<AD>& a, int grid, size_t lds, hipStream_t stream) {
-  if (a.norm_w) hipLaunchKernelGGL((rows16_kernel<EPI, true, WK, AD>), dim3(grid), dim3(256), lds, stream, a);
-  else hipLaunchKernelGGL((rows16_kernel<EPI, false, WK, AD>), dim3(grid), dim3(256), lds, stream, a);
-  LLX_LAUNCH_CHECK(fn);
-  if (a.S > 1) {
-    hipLaunchKernelGGL((rows16_combine_kernel<EPI, WK, AD>), dim3((a.ntiles + 3) / 4), dim3(256), 0, stream, a);
-    char name[64];
-    snprintf(name, sizeof name, "%s(combine)", fn);
-    LLX_LAUNCH_CHECK(name);
-  }
-  return LLX_OK;
-}
-
 template <int WK, int AD>
-static int launch_rows16_epi(const char* fn, const rows16_args_t<AD>& a, int epi, int grid, size_t lds, hipStream_t stream) {
-  switch (epi) {
-    case GV_NONE: return launch_rows16<GV_NONE, WK, AD>(fn, a, grid, lds, stream);
-    case GV_RESIDUAL: return launch_rows16<GV_RESIDUAL, WK, AD>(fn, a, grid, lds, stream);
-    case GV_QKV: return launch_rows16<GV_QKV, WK, AD>(fn, a, grid, lds, stream);
-    case GV_QKV_F8: return launch_rows16<GV_QKV_F8, WK, AD>(fn, a, grid, lds, stream);
-    default: return launch_rows16<GV_SWIGLU, WK, AD>(fn, a, grid, lds, stream);
-  }
+static int launch_rows16(const char* fn, const rows16_args_t<AD>& a, int epi, int grid, size_t lds, hipStream_t stream) {
+  return stream_with_epilogue(epi, [&](auto e) {
+    constexpr int EPI = decltype(e)::value;
+    if (a.norm_w) hipLaunchKernelGGL((rows16_kernel<EPI, true, WK, AD>), dim3(grid), dim3(256), lds, stream, a);
+    else hipLaunchKernelGGL((rows16_kernel<EPI, false, WK, AD>), dim3(grid), dim3(256), lds, stream, a);
+    LLX_LAUNCH_CHECK(fn);
+    if (a.S > 1) {
+      hipLaunchKernelGGL((rows16_combine_kernel<EPI, WK, AD>), dim3((a.ntiles + 3) / 4), dim3(256), 0, stream, a);
+      char name[64];
+      snprintf(name, sizeof name, "%s(combine)", fn);
+      LLX_LAUNCH_CHECK(name);
+    }
+    return LLX_OK;
+  });
 }
 
 // The launcher's dispatch decisions, all of them.  esz = bytes per weight / staged activation element (2: bf16, 1: the dynamic int8
@@ -386,33 +378,23 @@ extern "C" int64_t llx_gemm_rows16_i8_workspace_bytes(int64_t M, int64_t N, int6
   return rows16_workspace(M, N, K, epilogue, 1, ROWS16_I8_HEADER);
 }
 
-// the adapter operands of the two _lora entry points: bext_s bf16 [n_s, rank_s] row-major, t bf16 [M, sum rank] (row stride ldt),
-// colscale_s bf16 [n_s] = DoRA's cached row factors (all null: LoRA)
-struct Rows16Lora {
-  const void* bext[3]; int64_t rank[3]; const void* t; int64_t ldt; float scale; const void* colscale[3];
-};
-
-// the four entry points below: fn = the caller's name for messages, wk = WK_BF16 | WK_I8D, ws_s = per-row scales of W_s (WK_I8D),
+// the four entry points below: fn = the caller's name for messages, wk = WK_BF16 | WK_I8D, scales = per-row scales of W_s (WK_I8D),
 // lo = the adapter operands (null: the un-adapted entry points)
-static int rows16_run(const char* fn, int wk, const Rows16Lora* lo, const void* ws0, const void* ws1, const void* ws2, const void* w0, int64_t ldw0, int64_t n0, const void* w1,
-                      int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2, int64_t n2, const void* x, int64_t ldx, int64_t M, int64_t K,
-                      const void* norm_w, float eps, int epilogue, void* out, int64_t ldo, const void* res, int64_t ldr, const float* rope, int64_t n_q,
-                      int64_t n_k, void* k_cache, void* v_cache, int64_t c_sb, int64_t c_sh, int64_t c_ss, int64_t Smax, const int64_t* pos,
-                      void* workspace, int64_t workspace_bytes, hipStream_t stream) {
+static int rows16_run(const char* fn, int wk, const void* const* scales, const StreamCall& c, const StreamLora* lo, void* workspace, int64_t workspace_bytes,
+                      hipStream_t stream) {
   const int esz = wk == WK_BF16 ? 2 : 1;
   const int64_t header = wk == WK_BF16 ? 0 : ROWS16_I8_HEADER;
   Rows16LoraArgs a;
   const int rc = stream_check_fill(fn, a, 2, 16, wk == WK_BF16 ? "one row runs llx_gemv_bf16, more than 16 the MFMA GEMM" : "one row runs llx_gemv_i8, more than 16 the MFMA GEMM",
-                                   16 / esz, epilogue == GV_SWIGLU ? 1 : 16, w0, ldw0, n0, w1, ldw1,
-                                   n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue, out, ldo, res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sh, c_ss, pos);
+                                   16 / esz, c.epilogue == GV_SWIGLU ? 1 : 16, c);
   if (rc != LLX_OK) return rc;
   if (wk != WK_BF16) {
-    const int rc1 = stream_check_fill_scales(fn, a, "int8", ws0, ws1, ws2, n1, n2);
+    const int rc1 = stream_check_fill_scales(fn, a, "int8", c, scales);
     if (rc1 != LLX_OK) return rc1;
   }
   int ad = AD_NONE;
   if (lo) {
-    const void* w[3] = {w0, n1 > 0 ? w1 : nullptr, n2 > 0 ? w2 : nullptr};
+    const void* w[3] = {c.w[0], c.n[1] > 0 ? c.w[1] : nullptr, c.n[2] > 0 ? c.w[2] : nullptr};
     int64_t off = 0;
     for (int s = 0; s < 3; ++s) {
       LLX_REQUIRE((w[s] != nullptr) == (lo->bext[s] != nullptr), "%s: every present weight needs its B factor, and only those (segment %d)", fn, s);
@@ -430,28 +412,28 @@ static int rows16_run(const char* fn, int wk, const Rows16Lora* lo, const void* 
     ad = AD_LORA;
     if (lo->colscale[0] || lo->colscale[1] || lo->colscale[2]) {
       LLX_REQUIRE(wk == WK_BF16, "%s: DoRA factors ride on bf16 rows only", fn);
-      const int rc2 = stream_check_fill_scales(fn, a, "DoRA", lo->colscale[0], lo->colscale[1], lo->colscale[2], n1, n2);
+      const int rc2 = stream_check_fill_scales(fn, a, "DoRA", c, lo->colscale);
       if (rc2 != LLX_OK) return rc2;
       ad = AD_DORA;
     }
   }
-  LLX_REQUIRE(!gv_is_qkv(epilogue) || (n_q > 0 && Smax > 0 && Smax < (1ll << 31) && c_sb % 4 == 0),
+  LLX_REQUIRE(!gv_is_qkv(c.epilogue) || (c.n_q > 0 && c.Smax > 0 && c.Smax < (1ll << 31) && c.c_sb % 4 == 0),
               "%s: the q|k|v epilogue needs q heads, a cache length below 2^31 and 8-byte aligned cache slots", fn);
-  const Rows16Plan p = rows16_plan(M, a.N, K, epilogue, esz);
+  const Rows16Plan p = rows16_plan(c.M, a.N, c.K, c.epilogue, esz);
   LLX_REQUIRE(p.S == 1 || (workspace && (uintptr_t)workspace % 16 == 0 && workspace_bytes >= header + (int64_t)p.ntiles * p.S * 1024),
               "%s: workspace missing or smaller than %s()", fn, wk == WK_BF16 ? "llx_gemm_rows16_workspace_bytes" : "llx_gemm_rows16_i8_workspace_bytes");
-  a.c_sb = c_sb; a.Smax = (int)Smax;
+  a.c_sb = c.c_sb; a.Smax = (int)c.Smax;
   a.S = p.S; a.KS = p.KS; a.ntiles = p.ntiles; a.wgs = p.wgs;
   a.xscale = (float*)workspace;
   a.slab = (float*)((char*)workspace + header);
   const int grid = p.wgs * p.S;
-  const size_t lds = (size_t)M * p.KS * esz;
+  const size_t lds = (size_t)c.M * p.KS * esz;
   if (ad == AD_NONE) {
     const Rows16Args& b = a;  // the un-adapted instances take the base block
-    return wk == WK_BF16 ? launch_rows16_epi<WK_BF16, AD_NONE>(fn, b, epilogue, grid, lds, stream) : launch_rows16_epi<WK_I8D, AD_NONE>(fn, b, epilogue, grid, lds, stream);
+    return wk == WK_BF16 ? launch_rows16<WK_BF16, AD_NONE>(fn, b, c.epilogue, grid, lds, stream) : launch_rows16<WK_I8D, AD_NONE>(fn, b, c.epilogue, grid, lds, stream);
   }
-  if (ad == AD_DORA) return launch_rows16_epi<WK_BF16, AD_DORA>(fn, a, epilogue, grid, lds, stream);
-  return wk == WK_BF16 ? launch_rows16_epi<WK_BF16, AD_LORA>(fn, a, epilogue, grid, lds, stream) : launch_rows16_epi<WK_I8D, AD_LORA>(fn, a, epilogue, grid, lds, stream);
+  if (ad == AD_DORA) return launch_rows16<WK_BF16, AD_DORA>(fn, a, c.epilogue, grid, lds, stream);
+  return wk == WK_BF16 ? launch_rows16<WK_BF16, AD_LORA>(fn, a, c.epilogue, grid, lds, stream) : launch_rows16<WK_I8D, AD_LORA>(fn, a, c.epilogue, grid, lds, stream);
 }
 
 extern "C" int llx_gemm_rows16_bf16(const void* w0, int64_t ldw0, int64_t n0, const void* w1, int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2,
@@ -459,8 +441,9 @@ extern "C" int llx_gemm_rows16_bf16(const void* w0, int64_t ldw0, int64_t n0, co
                                     void* out, int64_t ldo, const void* res, int64_t ldr, const float* rope, int64_t n_q, int64_t n_k,
                                     void* k_cache, void* v_cache, int64_t c_sb, int64_t c_sh, int64_t c_ss, int64_t Smax, const int64_t* pos,
                                     void* workspace, int64_t workspace_bytes, hipStream_t stream) {
-  return rows16_run("llx_gemm_rows16_bf16", WK_BF16, nullptr, nullptr, nullptr, nullptr, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue, out, ldo,
-                    res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sb, c_sh, c_ss, Smax, pos, workspace, workspace_bytes, stream);
+  const StreamCall c = {{w0, w1, w2}, {ldw0, ldw1, ldw2}, {n0, n1, n2}, x, ldx, M, K, norm_w, eps, epilogue, out, ldo, res, ldr,
+                        rope, n_q, n_k, k_cache, v_cache, c_sb, c_sh, c_ss, Smax, pos};
+  return rows16_run("llx_gemm_rows16_bf16", WK_BF16, nullptr, c, nullptr, workspace, workspace_bytes, stream);
 }
 
 // The same product on int8 weight rows of the DYNAMIC kind (subclasses/int8.py:112-113, int8_mm.py:93-118; the weight-only kind has
@@ -474,8 +457,10 @@ extern "C" int llx_gemm_rows16_i8(const void* w0, int64_t ldw0, int64_t n0, cons
                                   void* k_cache, void* v_cache, int64_t c_sb, int64_t c_sh, int64_t c_ss, int64_t Smax, const int64_t* pos,
                                   void* workspace, int64_t workspace_bytes, const void* scale0, const void* scale1, const void* scale2,
                                   hipStream_t stream) {
-  return rows16_run("llx_gemm_rows16_i8", WK_I8D, nullptr, scale0, scale1, scale2, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue, out, ldo,
-                    res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sb, c_sh, c_ss, Smax, pos, workspace, workspace_bytes, stream);
+  const StreamCall c = {{w0, w1, w2}, {ldw0, ldw1, ldw2}, {n0, n1, n2}, x, ldx, M, K, norm_w, eps, epilogue, out, ldo, res, ldr,
+                        rope, n_q, n_k, k_cache, v_cache, c_sb, c_sh, c_ss, Smax, pos};
+  const void* const scales[3] = {scale0, scale1, scale2};
+  return rows16_run("llx_gemm_rows16_i8", WK_I8D, scales, c, nullptr, workspace, workspace_bytes, stream);
 }
 
 // llx_gemm_rows16_bf16 on LoRA linears (modelling/lora.py:43): bext_s bf16 [n_s, rank_s] row-major for every present weight, ranks
@@ -490,9 +475,10 @@ extern "C" int llx_gemm_rows16_bf16_lora(const void* w0, int64_t ldw0, int64_t n
                                          void* workspace, int64_t workspace_bytes, const void* bext0, const void* bext1, const void* bext2,
                                          int64_t rank0, int64_t rank1, int64_t rank2, const void* t, int64_t ldt, float lora_scale,
                                          const void* colscale0, const void* colscale1, const void* colscale2, hipStream_t stream) {
-  const Rows16Lora lo = {{bext0, bext1, bext2}, {rank0, rank1, rank2}, t, ldt, lora_scale, {colscale0, colscale1, colscale2}};
-  return rows16_run("llx_gemm_rows16_bf16_lora", WK_BF16, &lo, nullptr, nullptr, nullptr, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue,
-                    out, ldo, res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sb, c_sh, c_ss, Smax, pos, workspace, workspace_bytes, stream);
+  const StreamCall c = {{w0, w1, w2}, {ldw0, ldw1, ldw2}, {n0, n1, n2}, x, ldx, M, K, norm_w, eps, epilogue, out, ldo, res, ldr,
+                        rope, n_q, n_k, k_cache, v_cache, c_sb, c_sh, c_ss, Smax, pos};
+  const StreamLora lo = {{bext0, bext1, bext2}, {rank0, rank1, rank2}, t, ldt, lora_scale, {colscale0, colscale1, colscale2}};
+  return rows16_run("llx_gemm_rows16_bf16_lora", WK_BF16, nullptr, c, &lo, workspace, workspace_bytes, stream);
 }
 
 // llx_gemm_rows16_i8 on LoRA linears: out = epilogue(bf16(bf16(((float)acc * x_scale[m]) * scale[row]) + lora_scale * t_s . bext_s[row])),
@@ -505,7 +491,9 @@ extern "C" int llx_gemm_rows16_i8_lora(const void* w0, int64_t ldw0, int64_t n0,
                                        void* workspace, int64_t workspace_bytes, const void* scale0, const void* scale1, const void* scale2,
                                        const void* bext0, const void* bext1, const void* bext2, int64_t rank0, int64_t rank1, int64_t rank2,
                                        const void* t, int64_t ldt, float lora_scale, hipStream_t stream) {
-  const Rows16Lora lo = {{bext0, bext1, bext2}, {rank0, rank1, rank2}, t, ldt, lora_scale, {nullptr, nullptr, nullptr}};
-  return rows16_run("llx_gemm_rows16_i8_lora", WK_I8D, &lo, scale0, scale1, scale2, w0, ldw0, n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue,
-                    out, ldo, res, ldr, rope, n_q, n_k, k_cache, v_cache, c_sb, c_sh, c_ss, Smax, pos, workspace, workspace_bytes, stream);
+  const StreamCall c = {{w0, w1, w2}, {ldw0, ldw1, ldw2}, {n0, n1, n2}, x, ldx, M, K, norm_w, eps, epilogue, out, ldo, res, ldr,
+                        rope, n_q, n_k, k_cache, v_cache, c_sb, c_sh, c_ss, Smax, pos};
+  const StreamLora lo = {{bext0, bext1, bext2}, {rank0, rank1, rank2}, t, ldt, lora_scale, {}};
+  const void* const scales[3] = {scale0, scale1, scale2};
+  return rows16_run("llx_gemm_rows16_i8_lora", WK_I8D, scales, c, &lo, workspace, workspace_bytes, stream);
 }

@@ -355,25 +355,6 @@ __global__ __launch_bounds__(256, 2) void gemv_mx4_kernel(const Mx4Args a) {
   }
 }
 
-template <int MT, int EPI>
-static int launch_mx4_n(const Mx4Args& a, int grid, size_t lds, hipStream_t stream) {
-  if (a.norm_w) hipLaunchKernelGGL((gemv_mx4_kernel<MT, EPI, true>), dim3(grid), dim3(256), lds, stream, a);
-  else hipLaunchKernelGGL((gemv_mx4_kernel<MT, EPI, false>), dim3(grid), dim3(256), lds, stream, a);
-  LLX_LAUNCH_CHECK("llx_gemv_mxfp4");
-  return LLX_OK;
-}
-
-template <int MT>
-static int launch_mx4_m(const Mx4Args& a, int epi, int grid, size_t lds, hipStream_t stream) {
-  switch (epi) {
-    case GV_NONE: return launch_mx4_n<MT, GV_NONE>(a, grid, lds, stream);
-    case GV_RESIDUAL: return launch_mx4_n<MT, GV_RESIDUAL>(a, grid, lds, stream);
-    case GV_QKV: return launch_mx4_n<MT, GV_QKV>(a, grid, lds, stream);
-    case GV_QKV_F8: return launch_mx4_n<MT, GV_QKV_F8>(a, grid, lds, stream);
-    default: return launch_mx4_n<MT, GV_SWIGLU>(a, grid, lds, stream);
-  }
-}
-
 // llx_gemv_bf16 on MXFP4 weights: W_s = packed rows [n_s, K/2] (ldw_s in bytes, multiples of 16), scale_s = their scale bytes
 // [n_s, K/32] (row stride lds_s bytes), K % 32 == 0, M in 1..4.  Segments, norm, epilogues and LoRA operands as llx_gemv_bf16, and its
 // rounding points: out = epilogue(bf16(x . dq(W)^T + lora_scale * t . bext[row])), fp32 sums.  The kernel is built for one and two
@@ -386,12 +367,13 @@ extern "C" int llx_gemv_mxfp4(const void* w0, int64_t ldw0, int64_t n0, const vo
                               int64_t rank1, int64_t rank2, const void* t, int64_t ldt, float lora_scale, const void* scale0, int64_t lds0,
                               const void* scale1, int64_t lds1, const void* scale2, int64_t lds2, hipStream_t stream) {
   const char* fn = "llx_gemv_mxfp4";
+  const StreamCall c = {{w0, w1, w2}, {ldw0, ldw1, ldw2}, {n0, n1, n2}, x, ldx, M, K, norm_w, eps, epilogue, out, ldo, res, ldr,
+                        rope, n_q, n_k, k_cache, v_cache, 0, c_sh, c_ss, 0, input_pos};
+  const StreamLora lo = {{bext0, bext1, bext2}, {rank0, rank1, rank2}, t, ldt, lora_scale, {}};
   Mx4Args a;
   LLX_REQUIRE(K > 0 && K % 32 == 0, "%s: K=%lld must be a multiple of 32 (one scale per block of 32)", fn, (long long)K);
   // (the common checks see the packed rows in bytes: strides in multiples of 16; K in multiples of 32 is checked above)
-  const int rc0 = stream_check_fill(fn, a, 1, 4, "larger row counts run the MFMA GEMM on the dequantised image", 16, epilogue == GV_SWIGLU ? 1 : 4, w0, ldw0,
-                                    n0, w1, ldw1, n1, w2, ldw2, n2, x, ldx, M, K, norm_w, eps, epilogue, out, ldo, res, ldr, rope, n_q, n_k, k_cache,
-                                    v_cache, c_sh, c_ss, input_pos);
+  const int rc0 = stream_check_fill(fn, a, 1, 4, "larger row counts run the MFMA GEMM on the dequantised image", 16, epilogue == GV_SWIGLU ? 1 : 4, c);
   if (rc0 != LLX_OK) return rc0;
   LLX_REQUIRE(scale0 && (scale1 || n1 == 0) && (scale2 || n2 == 0), "%s: null scale (every MXFP4 weight needs its scale bytes)", fn);
   LLX_REQUIRE(ldw0 >= K / 2 && (n1 == 0 || ldw1 >= K / 2) && (n2 == 0 || ldw2 >= K / 2), "%s: a packed row stride shorter than K / 2 bytes", fn);
@@ -399,33 +381,22 @@ extern "C" int llx_gemv_mxfp4(const void* w0, int64_t ldw0, int64_t n0, const vo
   LLX_REQUIRE(ldx >= K || M == 1, "%s: activation row stride shorter than K", fn);
   a.sc[0] = (const uint8_t*)scale0; a.sc[1] = (const uint8_t*)(scale1 ? scale1 : scale0); a.sc[2] = (const uint8_t*)(scale2 ? scale2 : scale0);
   a.lds[0] = lds0; a.lds[1] = scale1 ? lds1 : lds0; a.lds[2] = scale2 ? lds2 : lds0;
-  const int rc1 = gemv_check_fill_lora(fn, a, n1, bext0, bext1, bext2, rank0, rank1, rank2, t, ldt, lora_scale);
+  const int rc1 = gemv_check_fill_lora(fn, a, c, lo);
   if (rc1 != LLX_OK) return rc1;
-  const int64_t N = a.N;
-  const int64_t groups = epilogue == GV_SWIGLU ? (N / 2 + 1) / 2 : (N + 3) / 4;
-  // the wave count is trimmed so that every wave gets the same number of row groups where possible
-  constexpr int wave_cap = 2048;
-  const int64_t per_wave = cdiv64(groups, wave_cap);
-  const int grid = (int)cdiv64(cdiv64(groups, per_wave), 4);
-  const int64_t Kp = cdiv64(K, 2048) * 2048;  // the kernel's LDS row length
-  auto fits = [&](int64_t mt) { return mt * Kp * 2 + 64 <= 64 * 1024; };
-  // rows per pass: two where their LDS stage fits, else one (each pass streams the weights again).  There is no 4-row build: next to
-  // the two weight register sets its 64 activation registers put 80 bytes of scratch into every instance
-  const int per_pass = M >= 2 && fits(2) ? 2 : 1;
-  LLX_REQUIRE(fits(per_pass), "%s: K too large for the LDS stage", fn);
-  for (int m0 = 0; m0 < (int)M; m0 += per_pass) {
-    const int mc = (int)M - m0 < per_pass ? (int)M - m0 : per_pass;
-    Mx4Args b = a;
-    b.M = mc;
-    b.x = a.x + (int64_t)m0 * a.ldx;
-    b.out = a.out + (int64_t)m0 * a.ldo;
-    if (a.res) b.res = a.res + (int64_t)m0 * a.ldr;
-    if (a.rope) b.rope = a.rope + (int64_t)m0 * 128;
-    if (a.pos) b.pos = a.pos + m0;
-    if (a.t) b.t = a.t + (int64_t)m0 * a.ldt;
-    const size_t lds = (size_t)mc * Kp * 2 + 64;
-    const int rc = mc == 1 ? launch_mx4_m<1>(b, epilogue, grid, lds, stream) : launch_mx4_m<2>(b, epilogue, grid, lds, stream);
-    if (rc != LLX_OK) return rc;
-  }
-  return LLX_OK;
+  const int grid = gemv_grid(a.N, epilogue, 4);  // four rows per wave
+  const int64_t Kp = cdiv64(K, 2048) * 2048;     // the kernel's LDS row length, bf16
+  // at most two rows per pass.  There is no 4-row build: next to the two weight register sets its 64 activation registers put 80 bytes
+  // of scratch into every instance
+  return gemv_passes(fn, a, 2, Kp, 2, [&](const Mx4Args& b, int MT, size_t lds) {
+    auto go = [&](auto mt) {
+      return stream_with_epilogue(epilogue, [&](auto e) {
+        constexpr int MT_ = decltype(mt)::value, EPI = decltype(e)::value;
+        if (b.norm_w) hipLaunchKernelGGL((gemv_mx4_kernel<MT_, EPI, true>), dim3(grid), dim3(256), lds, stream, b);
+        else hipLaunchKernelGGL((gemv_mx4_kernel<MT_, EPI, false>), dim3(grid), dim3(256), lds, stream, b);
+        LLX_LAUNCH_CHECK(fn);
+        return LLX_OK;
+      });
+    };
+    return MT == 1 ? go(std::integral_constant<int, 1>{}) : go(std::integral_constant<int, 2>{});
+  });
 }

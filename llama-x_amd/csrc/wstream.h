@@ -7,6 +7,7 @@
 #pragma once
 #include "common.h"  // HD
 #include "kv8.h"     // q() of the FP8 KV cache
+#include <type_traits>
 
 // epilogue 0: out [M, N] | 1: + res [M, N] | 2 (q|k|v): rows [0, n_q) RoPE -> out [M, n_q]; [n_q, n_q + n_k) RoPE -> k cache; rest ->
 // v cache | 3 (gate|up = W0|W1, N = 2 n_0): out [M, N/2] = silu(gate) * up | 4: epilogue 2 into FP8 caches (uint8 E4M3 codes, DESIGN
@@ -144,70 +145,130 @@ __device__ __forceinline__ void stream_epilogue(const StreamArgs& a, int row0, i
   }
 }
 
+// ---- host: the operands the eight entry points of the two streams have in common, as they arrive over the C ABI (include/llx.h); c_sb
+// and Smax are the batched stream's, 0 for the GEMVs.  Every entry point fills one of these, once, and hands it on.
+struct StreamCall {
+  const void* w[3]; int64_t ldw[3], n[3];
+  const void* x; int64_t ldx, M, K;
+  const void* norm_w; float eps; int epilogue;
+  void* out; int64_t ldo; const void* res; int64_t ldr;
+  const float* rope; int64_t n_q, n_k;
+  void* k_cache; void* v_cache; int64_t c_sb, c_sh, c_ss, Smax; const int64_t* pos;
+};
+// the adapter operands of both streams: bext_s bf16 [n_s, rank_s] row-major, t bf16 [M, sum rank] (row stride ldt), colscale_s bf16 [n_s]
+// = DoRA's cached row factors where they come with the adapter (the _lora entry points of the batched stream; all null: LoRA)
+struct StreamLora {
+  const void* bext[3]; int64_t rank[3]; const void* t; int64_t ldt; float scale; const void* colscale[3];
+};
+
 // ---- host: the checks every entry point of the two streams makes on the common operands, then their fill into `a`.  fn = the entry
 // point's name (every message begins with it); m_lo .. m_hi = its row counts (m_note says where other counts go); epl = weight
 // elements per 16-byte load (K and the weight row strides are multiples of it); seg_gran = what the inner segments' row counts must
 // be multiples of (a row group or tile never straddles two weights).  W[] / ldw[] of absent segments repeat segment 0, seg_end[] of
 // the last present segment is N.
-static inline int stream_check_fill(const char* fn, StreamArgs& a, int m_lo, int m_hi, const char* m_note, int epl, int seg_gran, const void* w0,
-                                    int64_t ldw0, int64_t n0, const void* w1, int64_t ldw1, int64_t n1, const void* w2, int64_t ldw2, int64_t n2,
-                                    const void* x, int64_t ldx, int64_t M, int64_t K, const void* norm_w, float eps, int epilogue, void* out, int64_t ldo,
-                                    const void* res, int64_t ldr, const float* rope, int64_t n_q, int64_t n_k, void* k_cache, void* v_cache, int64_t c_sh,
-                                    int64_t c_ss, const int64_t* pos) {
-  LLX_REQUIRE(w0 && x && out, "%s: null pointer", fn);
-  LLX_REQUIRE(M >= m_lo && M <= m_hi, "%s: M=%lld outside %d..%d (%s)", fn, (long long)M, m_lo, m_hi, m_note);
-  LLX_REQUIRE(K > 0 && K % epl == 0 && K <= 32768, "%s: K=%lld must be a multiple of %d and at most 32768", fn, (long long)K, epl);
-  LLX_REQUIRE(epilogue >= GV_NONE && epilogue <= GV_QKV_F8, "%s: unknown epilogue %d", fn, epilogue);
+static inline int stream_check_fill(const char* fn, StreamArgs& a, int m_lo, int m_hi, const char* m_note, int epl, int seg_gran, const StreamCall& c) {
+  const int64_t n0 = c.n[0], n1 = c.n[1], n2 = c.n[2], N = n0 + n1 + n2;
+  const void *w0 = c.w[0], *w1 = c.w[1], *w2 = c.w[2];
+  LLX_REQUIRE(w0 && c.x && c.out, "%s: null pointer", fn);
+  LLX_REQUIRE(c.M >= m_lo && c.M <= m_hi, "%s: M=%lld outside %d..%d (%s)", fn, (long long)c.M, m_lo, m_hi, m_note);
+  LLX_REQUIRE(c.K > 0 && c.K % epl == 0 && c.K <= 32768, "%s: K=%lld must be a multiple of %d and at most 32768", fn, (long long)c.K, epl);
+  LLX_REQUIRE(c.epilogue >= GV_NONE && c.epilogue <= GV_QKV_F8, "%s: unknown epilogue %d", fn, c.epilogue);
   LLX_REQUIRE(n0 > 0 && n1 >= 0 && n2 >= 0 && (w1 || n1 == 0) && (w2 || n2 == 0) && (n1 > 0 || n2 == 0), "%s: bad segment sizes", fn);
   LLX_REQUIRE((n1 == 0 || n0 % seg_gran == 0) && (n2 == 0 || n1 % seg_gran == 0), "%s: inner segment sizes must be multiples of %d", fn, seg_gran);
-  LLX_REQUIRE(ldw0 % epl == 0 && ldw1 % epl == 0 && ldw2 % epl == 0 && ldx % 8 == 0, "%s: row strides must be multiples of 16 bytes", fn);
-  LLX_REQUIRE(((uintptr_t)w0 | (uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)x | (uintptr_t)norm_w) % 16 == 0, "%s: pointers must be 16-byte aligned", fn);
-  const int64_t N = n0 + n1 + n2;
+  LLX_REQUIRE(c.ldw[0] % epl == 0 && c.ldw[1] % epl == 0 && c.ldw[2] % epl == 0 && c.ldx % 8 == 0, "%s: row strides must be multiples of 16 bytes", fn);
+  LLX_REQUIRE(((uintptr_t)w0 | (uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)c.x | (uintptr_t)c.norm_w) % 16 == 0, "%s: pointers must be 16-byte aligned", fn);
   LLX_REQUIRE(N < (1 << 30), "%s: too many rows", fn);
-  LLX_REQUIRE(epilogue != GV_RESIDUAL || res, "%s: residual missing", fn);
-  LLX_REQUIRE(epilogue != GV_SWIGLU || (n0 == n1 && n2 == 0 && w1), "%s: the SwiGLU epilogue takes gate and up weights of equal size", fn);
+  LLX_REQUIRE(c.epilogue != GV_RESIDUAL || c.res, "%s: residual missing", fn);
+  LLX_REQUIRE(c.epilogue != GV_SWIGLU || (n0 == n1 && n2 == 0 && w1), "%s: the SwiGLU epilogue takes gate and up weights of equal size", fn);
   // (epilogue 4: the caches hold one byte per element, so the same "4 elements" rule is 4-byte alignment of pointers and byte strides)
-  LLX_REQUIRE(!gv_is_qkv(epilogue) || (rope && k_cache && v_cache && pos && n_q % HD == 0 && n_k % HD == 0 && (N - n_q - n_k) % HD == 0 && n_q + n_k <= N &&
-                                       (uintptr_t)rope % 8 == 0 && (uintptr_t)out % 8 == 0 &&
-                                       ((uintptr_t)k_cache | (uintptr_t)v_cache) % (epilogue == GV_QKV_F8 ? 4 : 8) == 0 && ldo % 4 == 0 && c_sh % 4 == 0 &&
-                                       c_ss % 4 == 0),
+  LLX_REQUIRE(!gv_is_qkv(c.epilogue) ||
+                  (c.rope && c.k_cache && c.v_cache && c.pos && c.n_q % HD == 0 && c.n_k % HD == 0 && (N - c.n_q - c.n_k) % HD == 0 && c.n_q + c.n_k <= N &&
+                   (uintptr_t)c.rope % 8 == 0 && (uintptr_t)c.out % 8 == 0 &&
+                   ((uintptr_t)c.k_cache | (uintptr_t)c.v_cache) % (c.epilogue == GV_QKV_F8 ? 4 : 8) == 0 && c.ldo % 4 == 0 && c.c_sh % 4 == 0 && c.c_ss % 4 == 0),
               "%s: bad q|k|v epilogue arguments (the RoPE table, both caches and the positions; whole heads of 128; 8-byte aligned rows)", fn);
   a.W[0] = (const bf16_t*)w0; a.W[1] = (const bf16_t*)(w1 ? w1 : w0); a.W[2] = (const bf16_t*)(w2 ? w2 : w0);
-  a.ldw[0] = ldw0; a.ldw[1] = w1 ? ldw1 : ldw0; a.ldw[2] = w2 ? ldw2 : ldw0;
+  a.ldw[0] = c.ldw[0]; a.ldw[1] = w1 ? c.ldw[1] : c.ldw[0]; a.ldw[2] = w2 ? c.ldw[2] : c.ldw[0];
   a.seg_end[0] = (int)n0; a.seg_end[1] = (int)(n0 + n1); a.seg_end[2] = (int)N;
   if (n1 == 0) { a.seg_end[0] = a.seg_end[1] = (int)N; }  // single source: every row is segment 0
   else if (n2 == 0) { a.seg_end[1] = (int)N; }
-  a.x = (const bf16_t*)x; a.ldx = ldx; a.norm_w = (const bf16_t*)norm_w; a.eps = eps;
-  a.M = (int)M; a.N = (int)N; a.K = (int)K;
-  a.out = (bf16_t*)out; a.ldo = ldo; a.res = (const bf16_t*)res; a.ldr = ldr;
-  a.rope = rope; a.n_q = (int)n_q; a.n_k = (int)n_k; a.kc = (bf16_t*)k_cache; a.vc = (bf16_t*)v_cache;
-  a.c_sh = c_sh; a.c_ss = c_ss; a.pos = pos;
+  a.x = (const bf16_t*)c.x; a.ldx = c.ldx; a.norm_w = (const bf16_t*)c.norm_w; a.eps = c.eps;
+  a.M = (int)c.M; a.N = (int)N; a.K = (int)c.K;
+  a.out = (bf16_t*)c.out; a.ldo = c.ldo; a.res = (const bf16_t*)c.res; a.ldr = c.ldr;
+  a.rope = c.rope; a.n_q = (int)c.n_q; a.n_k = (int)c.n_k; a.kc = (bf16_t*)c.k_cache; a.vc = (bf16_t*)c.v_cache;
+  a.c_sh = c.c_sh; a.c_ss = c.c_ss; a.pos = c.pos;
   a.wscale[0] = a.wscale[1] = a.wscale[2] = nullptr;
   return LLX_OK;
 }
 
-// ---- host: the per-row scales of int8 weights, or the per-row DoRA factors of bf16 weights (bf16 [n_s]; what = "int8" | "DoRA"), after
-// stream_check_fill; scales of absent segments repeat segment 0
-static inline int stream_check_fill_scales(const char* fn, StreamArgs& a, const char* what, const void* ws0, const void* ws1, const void* ws2, int64_t n1,
-                                           int64_t n2) {
-  LLX_REQUIRE(ws0 && (ws1 || n1 == 0) && (ws2 || n2 == 0), "%s: null scale (every %s weight needs its per-row scales)", fn, what);
-  LLX_REQUIRE(((uintptr_t)ws0 | (uintptr_t)ws1 | (uintptr_t)ws2) % 2 == 0, "%s: scale pointers must be 2-byte aligned", fn);
-  a.wscale[0] = (const bf16_t*)ws0; a.wscale[1] = (const bf16_t*)(ws1 ? ws1 : ws0); a.wscale[2] = (const bf16_t*)(ws2 ? ws2 : ws0);
+// ---- host: the per-row scales ws[0..2] of int8 weights, or the per-row DoRA factors of bf16 weights (bf16 [n_s]; what = "int8" | "DoRA"),
+// after stream_check_fill; scales of absent segments repeat segment 0
+static inline int stream_check_fill_scales(const char* fn, StreamArgs& a, const char* what, const StreamCall& c, const void* const* ws) {
+  LLX_REQUIRE(ws[0] && (ws[1] || c.n[1] == 0) && (ws[2] || c.n[2] == 0), "%s: null scale (every %s weight needs its per-row scales)", fn, what);
+  LLX_REQUIRE(((uintptr_t)ws[0] | (uintptr_t)ws[1] | (uintptr_t)ws[2]) % 2 == 0, "%s: scale pointers must be 2-byte aligned", fn);
+  for (int s = 0; s < 3; ++s) a.wscale[s] = (const bf16_t*)(ws[s] ? ws[s] : ws[0]);
   return LLX_OK;
 }
 
 // ---- host: the LoRA operands of a GEMV (nullable bext_s [n_s, rank_s], t [M, sum rank] bf16, offsets into t by segment), after stream_check_fill
-static inline int gemv_check_fill_lora(const char* fn, GemvArgs& a, int64_t n1, const void* bext0, const void* bext1, const void* bext2, int64_t rank0,
-                                       int64_t rank1, int64_t rank2, const void* t, int64_t ldt, float lora_scale) {
-  const bool lora = bext0 || bext1 || bext2;
-  LLX_REQUIRE(!lora || (t && ldt % 8 == 0 && (uintptr_t)t % 16 == 0 && rank0 % 8 == 0 && rank1 % 8 == 0 && rank2 % 8 == 0 && rank0 <= 512 && rank1 <= 512 &&
-                        rank2 <= 512 && ((uintptr_t)bext0 | (uintptr_t)bext1 | (uintptr_t)bext2) % 16 == 0),
+static inline int gemv_check_fill_lora(const char* fn, GemvArgs& a, const StreamCall& c, const StreamLora& lo) {
+  const int64_t* rank = lo.rank;
+  const bool lora = lo.bext[0] || lo.bext[1] || lo.bext[2];
+  LLX_REQUIRE(!lora || (lo.t && lo.ldt % 8 == 0 && (uintptr_t)lo.t % 16 == 0 && rank[0] % 8 == 0 && rank[1] % 8 == 0 && rank[2] % 8 == 0 && rank[0] <= 512 &&
+                        rank[1] <= 512 && rank[2] <= 512 && ((uintptr_t)lo.bext[0] | (uintptr_t)lo.bext[1] | (uintptr_t)lo.bext[2]) % 16 == 0),
               "%s: bad LoRA operands (ranks must be multiples of 8, at most 512)", fn);
-  a.bext[0] = (const bf16_t*)bext0; a.bext[1] = (const bf16_t*)bext1; a.bext[2] = (const bf16_t*)bext2;
-  a.ldb[0] = rank0; a.ldb[1] = rank1; a.ldb[2] = rank2;
-  a.rank[0] = (int)rank0; a.rank[1] = (int)rank1; a.rank[2] = (int)rank2;
-  a.t_off[0] = 0; a.t_off[1] = (int)rank0; a.t_off[2] = (int)(rank0 + rank1);
-  a.t = (const bf16_t*)t; a.ldt = ldt; a.lora_scale = lora_scale;
-  if (n1 == 0 && lora) { a.bext[1] = a.bext[2] = a.bext[0]; a.ldb[1] = a.ldb[2] = a.ldb[0]; a.rank[1] = a.rank[2] = a.rank[0]; a.t_off[1] = a.t_off[2] = 0; }
+  for (int s = 0; s < 3; ++s) { a.bext[s] = (const bf16_t*)lo.bext[s]; a.ldb[s] = rank[s]; a.rank[s] = (int)rank[s]; }
+  a.t_off[0] = 0; a.t_off[1] = (int)rank[0]; a.t_off[2] = (int)(rank[0] + rank[1]);
+  a.t = (const bf16_t*)lo.t; a.ldt = lo.ldt; a.lora_scale = lo.scale;
+  if (c.n[1] == 0 && lora) { a.bext[1] = a.bext[2] = a.bext[0]; a.ldb[1] = a.ldb[2] = a.ldb[0]; a.rank[1] = a.rank[2] = a.rank[0]; a.t_off[1] = a.t_off[2] = 0; }
+  return LLX_OK;
+}
+
+// ---- host: the run-time epilogue of a call as a compile-time constant: f(std::integral_constant<int, GV_*>{}) launches the instance
+// and returns the entry point's status (stream_check_fill has checked the range before a call comes here)
+template <class F>
+static inline int stream_with_epilogue(int epilogue, F&& f) {
+  switch (epilogue) {
+    case GV_NONE: return f(std::integral_constant<int, GV_NONE>{});
+    case GV_RESIDUAL: return f(std::integral_constant<int, GV_RESIDUAL>{});
+    case GV_QKV: return f(std::integral_constant<int, GV_QKV>{});
+    case GV_QKV_F8: return f(std::integral_constant<int, GV_QKV_F8>{});
+    default: return f(std::integral_constant<int, GV_SWIGLU>{});
+  }
+}
+
+// ---- host: the launches of a GEMV (gemv_kernel, gemv_mx4_kernel), after the checks.
+// Grid: rpw output rows (SwiGLU: rpw / 2 hidden units) make a row group, a wave walks row groups, four waves a workgroup; the wave count
+// is trimmed so that every wave gets the same number of row groups where possible.
+static inline int gemv_grid(int64_t N, int epilogue, int rpw) {
+  const int64_t groups = epilogue == GV_SWIGLU ? cdiv64(N / 2, rpw / 2) : cdiv64(N, rpw);
+  constexpr int wave_cap = 2048;
+  const int64_t per_wave = cdiv64(groups, wave_cap);
+  return (int)cdiv64(cdiv64(groups, per_wave), 4);
+}
+// Passes: the build for m rows stages MT = 1 | 2 | 4 rows of x in LDS, Kp elements of xb bytes each (the kernel's LDS row length).  Rows per
+// pass: all of them where the kind has that build (max_pass = 4 | 2) and their stage fits 64 KiB, else pairs, else one; each pass streams
+// the weights again, on its own rows of x / out / res / rope / pos / t.  launch(b, MT, lds): the launch of one pass.
+template <class Args, class Launch>
+static inline int gemv_passes(const char* fn, const Args& a, int max_pass, int64_t Kp, int64_t xb, Launch&& launch) {
+  auto stage = [&](int64_t mt) { return mt * Kp * xb + 64; };
+  auto fits = [&](int64_t mt) { return stage(mt) <= 64 * 1024; };
+  int per_pass = a.M > 2 ? 4 : a.M;
+  if (per_pass == 4 && (max_pass < 4 || !fits(4))) per_pass = 2;
+  if (per_pass == 2 && !fits(2)) per_pass = 1;
+  LLX_REQUIRE(fits(per_pass), "%s: K too large for the LDS stage", fn);
+  for (int m0 = 0; m0 < a.M; m0 += per_pass) {
+    const int mc = a.M - m0 < per_pass ? a.M - m0 : per_pass;
+    Args b = a;
+    b.M = mc;
+    b.x = a.x + (int64_t)m0 * a.ldx;
+    b.out = a.out + (int64_t)m0 * a.ldo;
+    if (a.res) b.res = a.res + (int64_t)m0 * a.ldr;
+    if (a.rope) b.rope = a.rope + (int64_t)m0 * 128;
+    if (a.pos) b.pos = a.pos + m0;
+    if (a.t) b.t = a.t + (int64_t)m0 * a.ldt;
+    const int MT = mc == 1 ? 1 : (mc == 2 ? 2 : 4);
+    const int rc = launch(b, MT, (size_t)stage(MT));
+    if (rc != LLX_OK) return rc;
+  }
   return LLX_OK;
 }

@@ -18,6 +18,12 @@ _lib = None
 
 # name -> (restype, argtypes). Kept in step with include/llx.h (tests/test_abi.py checks both ways).
 _P, _I, _L, _F = c_void_p, c_int, c_int64, c_float
+# the weight-stream entry points (csrc/wstream.h) are built from these pieces
+_STREAM = [_P, _L, _L] * 3 + [_P, _L, _L, _L, _P, _F, _I, _P, _L, _P, _L, _P, _L, _L, _P, _P]  # w0, ldw0, n0 .. x .. epilogue .. rope, n_q, n_k, k_cache, v_cache
+_LORA = [_P, _P, _P, _L, _L, _L, _P, _L, _F]        # bext0-2, rank0-2, t, ldt, lora_scale
+_SCALES = [_P, _P, _P]                              # per-row scales (int8) or DoRA factors of the three segments
+_GEMV = _STREAM + [_L, _L, _P] + _LORA              # .. c_sh, c_ss, input_pos, the LoRA operands
+_ROWS16 = _STREAM + [_L, _L, _L, _L, _P, _P, _L]    # .. c_sb, c_sh, c_ss, Smax, pos, workspace, workspace_bytes
 SIGNATURES: dict[str, tuple] = {
     "llx_version": (c_int, []),
     "llx_last_error_string": (c_char_p, []),
@@ -35,16 +41,12 @@ SIGNATURES: dict[str, tuple] = {
     "llx_attn_mask_flags_bytes": (c_int64, [_L, _L, _L]),
     "llx_attn_mask_tile_flags": (c_int, [_P, _L, _L, _P, _L, _L, _L, _P]),
     "llx_attn_mask_fwd": (c_int, [_P, _L, _L, _P, _L, _L, _L, _P, _L, _L, _L, _P, _L, _L, _P, _P, _L, _L, _P, _L, _L, _L, _L, _L, _L, _F, _P]),
-    "llx_gemv_bf16": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _F, _I, _P, _L, _P, _L, _P, _L, _L, _P, _P, _L, _L, _P,
-                              _P, _P, _P, _L, _L, _L, _P, _L, _F, _P]),
-    "llx_gemv_i8": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _F, _I, _P, _L, _P, _L, _P, _L, _L, _P, _P, _L, _L, _P,
-                            _P, _P, _P, _L, _L, _L, _P, _L, _F, _P, _P, _P, _I, _P]),
-    "llx_gemv_bf16_dora": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _F, _I, _P, _L, _P, _L, _P, _L, _L, _P, _P, _L, _L, _P,
-                                   _P, _P, _P, _L, _L, _L, _P, _L, _F, _P, _P, _P, _P]),
+    "llx_gemv_bf16": (c_int, _GEMV + [_P]),
+    "llx_gemv_i8": (c_int, _GEMV + _SCALES + [_I, _P]),
+    "llx_gemv_bf16_dora": (c_int, _GEMV + _SCALES + [_P]),
     "llx_quantize_mxfp4": (c_int, [_P, _L, _I, _L, _L, _P, _P, _P]),
     "llx_dequantize_mxfp4": (c_int, [_P, _L, _P, _L, _L, _L, _P, _L, _I, _P]),
-    "llx_gemv_mxfp4": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _F, _I, _P, _L, _P, _L, _P, _L, _L, _P, _P, _L, _L, _P,
-                               _P, _P, _P, _L, _L, _L, _P, _L, _F, _P, _L, _P, _L, _P, _L, _P]),
+    "llx_gemv_mxfp4": (c_int, _GEMV + [_P, _L] * 3 + [_P]),
     "llx_mask_extent":(c_int, [_P, _L, _L, _L, _P, _P]),
     "llx_kv_scatter": (c_int, [_P, _P, _L, _L, _L, _P, _P, _L, _L, _L, _P, _L, _L, _L, _L, _L, _P]),
     "llx_kv_scatter_rows": (c_int, [_P, _P, _L, _L, _L, _P, _P, _L, _L, _L, _P, _L, _L, _L, _L, _L, _L, _P]),
@@ -52,15 +54,11 @@ SIGNATURES: dict[str, tuple] = {
     "llx_kv_scatter_rows_f8": (c_int, [_P, _P, _L, _L, _L, _P, _P, _L, _L, _L, _P, _L, _L, _L, _L, _L, _L, _P]),
     "llx_kv_dequantize_f8": (c_int, [_P, _L, _L, _L, _P, _L, _L, _L, _L, _P]),
     "llx_gemm_rows16_workspace_bytes": (c_int64, [_L, _L, _L, _I]),
-    "llx_gemm_rows16_bf16": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _F, _I, _P, _L, _P, _L, _P, _L, _L, _P, _P, _L, _L, _L,
-                                     _L, _P, _P, _L, _P]),
+    "llx_gemm_rows16_bf16": (c_int, _ROWS16 + [_P]),
     "llx_gemm_rows16_i8_workspace_bytes": (c_int64, [_L, _L, _L, _I]),
-    "llx_gemm_rows16_i8": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _F, _I, _P, _L, _P, _L, _P, _L, _L, _P, _P, _L, _L, _L,
-                                   _L, _P, _P, _L, _P, _P, _P, _P]),
-    "llx_gemm_rows16_bf16_lora": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _F, _I, _P, _L, _P, _L, _P, _L, _L, _P, _P, _L, _L, _L,
-                                          _L, _P, _P, _L, _P, _P, _P, _L, _L, _L, _P, _L, _F, _P, _P, _P, _P]),
-    "llx_gemm_rows16_i8_lora": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _L, _P, _F, _I, _P, _L, _P, _L, _P, _L, _L, _P, _P, _L, _L, _L,
-                                        _L, _P, _P, _L, _P, _P, _P, _P, _P, _P, _L, _L, _L, _P, _L, _F, _P]),
+    "llx_gemm_rows16_i8": (c_int, _ROWS16 + _SCALES + [_P]),
+    "llx_gemm_rows16_bf16_lora": (c_int, _ROWS16 + _LORA + _SCALES + [_P]),
+    "llx_gemm_rows16_i8_lora": (c_int, _ROWS16 + _SCALES + _LORA + [_P]),
     "llx_attn_decode_workspace_bytes": (c_int64, [_L, _L, _L, _L]),
     "llx_attn_decode": (c_int, [_P, _L, _L, _L, _P, _P, _L, _L, _L, _P, _L, _L, _L, _P, _L, _L, _L, _P, _P, _L, _L, _L, _L, _L, _L, _L, _F, _P]),
     "llx_attn_decode_f8": (c_int, [_P, _L, _L, _L, _P, _P, _L, _L, _L, _P, _L, _L, _L, _P, _L, _L, _L, _P, _P, _L, _L, _L, _L, _L, _L, _L, _F, _P]),

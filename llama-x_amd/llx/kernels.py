@@ -902,10 +902,28 @@ def _stream_operands(ws, x: Tensor, norm, epilogue: int, out: Optional[Tensor], 
     return args, out, N, kc, pos
 
 
-def _gemv_operands(ws, x: Tensor, norm, epilogue: int, out, res, qkv, lora, wcols: Optional[int] = None):
-    """The arguments every GEMV entry point begins with (those of llx_gemv_bf16 before the stream), and the output tensor."""
-    args, out, _, kc, pos = _stream_operands(ws, x, norm, epilogue, out, res, qkv, batched=False, wcols=wcols)
-    args += [kc.stride(1), kc.stride(2)] if kc is not None else [0, 0]
+def _chk_colscale(fn: str, ws, colscale) -> None:
+    """DoRA's cached row factors as gemv and gemm_rows16 (fn: the caller, whose name begins the message) both take them."""
+    if len(colscale) != len(ws) or not all(c.dtype is BF16 and c.shape == (w.shape[0],) and c.is_contiguous() for c, w in zip(colscale, ws)):
+        raise L.LlxError(f"{fn}: colscale must hold one contiguous bf16 [n_s] tensor per weight")
+    L.require_cuda(*colscale)
+
+
+def _chk_int8_weights(fn: str, ws, x: Tensor, wscale, i8) -> None:
+    """What gemv and gemm_rows16 (fn) both ask of a call with int8 weights; i8: which of ws are int8."""
+    if not all(i8):
+        raise L.LlxError(f"{fn}: bf16 and int8 weights in one call (all members of a fused group must be of one kind)")
+    if x.shape[1] % 16 != 0:
+        raise L.LlxError(f"{fn}: K={x.shape[1]} must be a multiple of 16 for int8 weights")
+    assert wscale is not None and len(wscale) == len(ws), "int8 weights need their per-row scales"
+    assert all(sc.shape == (w.shape[0],) and sc.is_contiguous() for sc, w in zip(wscale, ws))
+    _chk_bf16(x, *wscale)
+    L.require_cuda(*ws)
+
+
+def _lora_operands(ws, x: Tensor, lora):
+    """The adapter operands of both streams, lora = (b factors, t [M, sum r], scale) or None: (bs, ranks, t, ldt, scale) as the entry points
+    take them, absent segments and an absent adapter as null / 0."""
     bs, ranks, t, ldt, lscale = [None] * 3, [0] * 3, None, 0, 0.0
     if lora is not None:
         b_list, t, lscale = lora
@@ -915,7 +933,15 @@ def _gemv_operands(ws, x: Tensor, norm, epilogue: int, out, res, qkv, lora, wcol
             bs[i], ranks[i] = b, b.shape[1]
         assert t.shape[1] == sum(ranks)
         ldt = t.stride(0)
-    args += [L.ptr(pos), L.ptr(bs[0]), L.ptr(bs[1]), L.ptr(bs[2]), ranks[0], ranks[1], ranks[2], L.ptr(t), ldt, float(lscale)]
+    return bs, ranks, t, ldt, float(lscale)
+
+
+def _gemv_operands(ws, x: Tensor, norm, epilogue: int, out, res, qkv, lora, wcols: Optional[int] = None):
+    """The arguments every GEMV entry point begins with (those of llx_gemv_bf16 before the stream), and the output tensor."""
+    args, out, _, kc, pos = _stream_operands(ws, x, norm, epilogue, out, res, qkv, batched=False, wcols=wcols)
+    args += [kc.stride(1), kc.stride(2)] if kc is not None else [0, 0]
+    bs, ranks, t, ldt, lscale = _lora_operands(ws, x, lora)
+    args += [L.ptr(pos), L.ptr(bs[0]), L.ptr(bs[1]), L.ptr(bs[2]), ranks[0], ranks[1], ranks[2], L.ptr(t), ldt, lscale]
     return args, out
 
 
@@ -989,18 +1015,9 @@ def gemv(ws: Sequence[Tensor], x: Tensor, *, norm: Optional[tuple[Tensor, float]
     if colscale is not None:
         if any(i8):
             raise L.LlxError("gemv: colscale (DoRA) on int8 weights is not supported")
-        if len(colscale) != len(ws) or not all(c.dtype is BF16 and c.shape == (w.shape[0],) and c.is_contiguous() for c, w in zip(colscale, ws)):
-            raise L.LlxError("gemv: colscale must hold one contiguous bf16 [n_s] tensor per weight")
-        L.require_cuda(*colscale)
+        _chk_colscale("gemv", ws, colscale)
     if any(i8):
-        if not all(i8):
-            raise L.LlxError("gemv: bf16 and int8 weights in one call (all members of a fused group must be of one kind)")
-        if x.shape[1] % 16 != 0:
-            raise L.LlxError(f"gemv: K={x.shape[1]} must be a multiple of 16 for int8 weights")
-        assert wscale is not None and len(wscale) == len(ws), "int8 weights need their per-row scales"
-        assert all(sc.shape == (w.shape[0],) and sc.is_contiguous() for sc, w in zip(wscale, ws))
-        _chk_bf16(x, *wscale)
-        L.require_cuda(*ws)
+        _chk_int8_weights("gemv", ws, x, wscale, i8)
     else:
         assert wscale is None and not dynamic, "wscale / dynamic belong to int8 weights"
         _chk_bf16(x, *ws)
@@ -1038,18 +1055,9 @@ def gemm_rows16(ws: Sequence[Tensor], x: Tensor, *, norm: Optional[tuple[Tensor,
             raise L.LlxError("gemm_rows16: colscale (DoRA) on int8 weights is not supported")
         if lora is None:
             raise L.LlxError("gemm_rows16: colscale (DoRA) needs the lora operands")
-        if len(colscale) != len(ws) or not all(c.dtype is BF16 and c.shape == (w.shape[0],) and c.is_contiguous() for c, w in zip(colscale, ws)):
-            raise L.LlxError("gemm_rows16: colscale must hold one contiguous bf16 [n_s] tensor per weight")
-        L.require_cuda(*colscale)
+        _chk_colscale("gemm_rows16", ws, colscale)
     if any(i8):
-        if not all(i8):
-            raise L.LlxError("gemm_rows16: bf16 and int8 weights in one call (all members of a fused group must be of one kind)")
-        if x.shape[1] % 16 != 0:
-            raise L.LlxError(f"gemm_rows16: K={x.shape[1]} must be a multiple of 16 for int8 weights")
-        assert wscale is not None and len(wscale) == len(ws), "int8 weights need their per-row scales"
-        assert all(sc.shape == (w.shape[0],) and sc.is_contiguous() for sc, w in zip(wscale, ws))
-        _chk_bf16(x, *wscale)
-        L.require_cuda(*ws)
+        _chk_int8_weights("gemm_rows16", ws, x, wscale, i8)
     else:
         assert wscale is None, "wscale belongs to int8 weights"
         _chk_bf16(x, *ws)
@@ -1057,15 +1065,9 @@ def gemm_rows16(ws: Sequence[Tensor], x: Tensor, *, norm: Optional[tuple[Tensor,
     args += [kc.stride(0), kc.stride(1), kc.stride(2), kc.shape[2]] if kc is not None else [0, 0, 0, 0]
     largs = None
     if lora is not None:
-        b_list, t, lscale = lora
-        assert len(b_list) == len(ws) and t.dtype is BF16 and t.shape[0] == x.shape[0] and t.stride(1) == 1
-        bs, ranks = [None] * 3, [0] * 3
-        for i, b in enumerate(b_list):
-            assert b.dtype is BF16 and b.is_contiguous() and b.shape[0] == ws[i].shape[0]
-            bs[i], ranks[i] = b, b.shape[1]
-        assert t.shape[1] == sum(ranks)
-        L.require_cuda(t, *b_list)
-        largs = [L.ptr(bs[0]), L.ptr(bs[1]), L.ptr(bs[2]), ranks[0], ranks[1], ranks[2], L.ptr(t), t.stride(0), float(lscale)]
+        bs, ranks, t, ldt, lscale = _lora_operands(ws, x, lora)
+        L.require_cuda(t, *lora[0])
+        largs = [L.ptr(bs[0]), L.ptr(bs[1]), L.ptr(bs[2]), ranks[0], ranks[1], ranks[2], L.ptr(t), ldt, lscale]
     if any(i8):
         wsp = _workspace(_ROWS16_WS, x.device, _lib().llx_gemm_rows16_i8_workspace_bytes(x.shape[0], N, x.shape[1], epilogue), 1 << 20)
         sp = [L.ptr(sc) for sc in wscale] + [None] * (3 - len(ws))

@@ -39,7 +39,7 @@ Operand families.
     (+-1/2, +-1/2)} per (token, pair): products by them are exact, so the rotation is one rounding however it is contracted.
 `reference` asserts all of it: representable in fp32 at every fp32 intermediate, in bf16 at the linear's sum, |S| <= 256.
 
-Dispatch, re-derived from gemv_run / gemv_kernel (two rows per wave; the LLX_GEMV_RPW=4 build is out of scope here):
+Dispatch, re-derived from gemv_run / gemv_kernel (two rows per wave):
   elements per 16-byte lane load EPL = 8 (bf16) | 16 (int8); PIECE = 64 EPL = 512 | 1024; STEP = 4 PIECE = 2048 | 4096;
   LDS row Kp = ceil(K / STEP) STEP (bf16) | (ceil(K / PIECE) + 1) PIECE (int8); staged bytes per element xb = 2, 1 for dynamic int8;
   a pass of mt in {4, 2, 1} staged rows fits when mt Kp xb + 64 <= 65536:
